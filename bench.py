@@ -26,6 +26,22 @@ each rank encodes/decodes its own batch with no data-path collective ("weak"
 scaling). The only cross-rank traffic is the gloo barrier and the max-reduce of the
 timer.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline figure
+needs and no more: it sets the batch and the two plans up, tunes their tile orders, warms
+up, times the N steps, writes the outputs if --dump-outputs is given and prints the line.
+Everything else the benchmark measures or checks -- the device round trip and the
+rebuilt-shard check, the traffic ceilings (`roofline.copy_ceiling`, `roofline.nolookup`),
+the layout A/B (`layout_ab`) and the CPU baseline with its bit-exact comparison
+(`cpu_baseline`) -- runs with `--full` only; a plain line carries null there.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step computed,
+as float32 .npy files: `encode_parity.npy` (the m parity shards of every stripe,
+[stripe][parity][byte]) and `decode_rebuilt.npy` (the rebuilt erased shards,
+[stripe][erased][byte]). An output of more than DUMP_MAX_VALUES bytes is written as a fixed
+sample: its bytes at DUMP_MAX_VALUES sorted flat indices drawn from a CPU generator seeded
+with DUMP_SEED, so two builds given the same arguments write the same positions of the
+same inputs (the batch is filled from a seeded device generator).
+
 roofline: the encode kernel's (rs_apply_lds for k >= 4) algorithmic bytes per launch
 ((k+m)*S per stripe) over its average HIP-event duration on the launch stream, against
 8.0 TB/s HBM3E. The events are recorded by the kernel dispatches themselves
@@ -33,7 +49,7 @@ roofline: the encode kernel's (rs_apply_lds for k >= 4) algorithmic bytes per la
 stop when its last ends), i.e. the kernel time rocprofv3's kernel trace reports; the
 stream's gap between one launch and the next is in ms_per_step (and `launch_gap_ms`),
 not in the per-kernel time.
-cpu_baseline: rank 0 at N=1 only — the C port of the reference CPU algorithm
+cpu_baseline (--full): rank 0 at N=1 only — the C port of the reference CPU algorithm
 (oracle/rs_oracle.c orc_bench_codec: upstream GFNI/AVX2 kernels, one native loop,
 stripe-parallel and byte-range threadings, the faster reported) over >= 2 GiB of the
 same stripes copied to the host; the same leg checks the GPU parity and
@@ -57,6 +73,9 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.
 # host threads per GPU on the driver's boxes: a 1-GPU box grants 16 CPUs though
 # sched_getaffinity / nproc list every CPU of the host
 CPU_SHARE = 16
+# --dump-outputs: values written per output at the most (float32: 16 MiB a file, two files)
+DUMP_MAX_VALUES = 4 << 20
+DUMP_SEED = 0xD0C5
 
 
 def parse_args(argv=None):
@@ -64,6 +83,15 @@ def parse_args(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the device round-trip "
+                        "and rebuilt-shard checks, the traffic ceilings (--ceiling), the layout "
+                        "A/B (--layout-ab) and the CPU baseline with its bit-exact comparison "
+                        "(--cpu-seconds); without it those options have no effect")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last step's parity and rebuilt shards "
+                        "as DIR/encode_parity.npy and DIR/decode_rebuilt.npy (float32; a fixed "
+                        "seeded sample of an output above DUMP_MAX_VALUES bytes)")
     p.add_argument("--k", type=int, default=10)
     p.add_argument("--m", type=int, default=4)
     p.add_argument("--shard-bytes", type=int, default=1 << 20)
@@ -386,6 +414,24 @@ def nolookup_entry(ceil, name, nbytes, achieved):
             "frac": round(achieved / gbs, 4), "ms": round(ceil[name]["nolookup"], 4)}
 
 
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: each (name, tensor) of `outputs` -- a [stripe][shard][byte] uint8
+    device tensor or view -- as dirname/name.npy in float32: whole when it has at most
+    DUMP_MAX_VALUES bytes, else its bytes at DUMP_MAX_VALUES sorted flat indices drawn from
+    a CPU generator seeded with DUMP_SEED (the same positions for the same shape)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs:
+        if t.numel() > DUMP_MAX_VALUES:
+            g = torch.Generator()
+            g.manual_seed(DUMP_SEED)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_VALUES,), generator=g).sort().values
+            idx = idx.to(t.device)
+            _, r, s = t.shape
+            t = t[idx // (r * s), idx // s % r, idx % s]
+        np.save(os.path.join(dirname, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def main(argv=None):
     args = parse_args(argv)
     rank, world, local = dist_env()
@@ -403,6 +449,7 @@ def main(argv=None):
         import torch.distributed as dist
         dist.init_process_group("gloo", rank=rank, world_size=world)
 
+    from callfs_amd import _native as N
     from callfs_amd.device import Plan, StripeBatch
 
     k, m, S, B = args.k, args.m, args.shard_bytes, args.stripes
@@ -447,9 +494,12 @@ def main(argv=None):
         want = sb.gather()[:, erase]
         return torch.equal(rebuilt[:, :, :S], want)
 
-    # untimed device-side round-trip check: encode, erase, decode, compare
+    # untimed: the parity the decode plan reads, then (--full) the device-side round-trip
+    # check: erase, decode, compare
     enc.launch(stream)
-    if fresh:
+    if not args.full:
+        pass
+    elif fresh:
         rebuilt.zero_()
         dec.launch(stream)
         if dec.corrupt(stream) or not rebuilt_ok():
@@ -514,14 +564,24 @@ def main(argv=None):
     user_step = 2 * B * k * (S_obj if S_obj else S * world)
     value = args.steps * user_step / elapsed / 2**30
 
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, before anything launches again
+        if fresh:
+            out_dec = rebuilt[:, :, :S]
+        else:  # rebuilt in place: the erased shards' own slots, [stripe][erased][byte]
+            out_dec = torch.stack([sb.shard(slice(None), i) for i in erase], dim=1) \
+                if erase else sb.parity()[:, :0]
+        dump_outputs(args.dump_outputs,
+                     [("encode_parity", sb.parity()), ("decode_rebuilt", out_dec)])
+        del out_dec
     if dec.corrupt(stream):
         raise SystemExit("verify flagged corruption during the timed run")
-    if fresh:
+    if fresh and args.full:
         rebuilt.zero_()
         dec.launch(stream)
         if not rebuilt_ok():
             raise SystemExit("rebuilt shards differ from the originals after the timed run")
-    ceil = plan_ceilings(enc, dec, stream) if args.ceiling else None
+    ceil = plan_ceilings(enc, dec, stream) if args.full and args.ceiling else None
     cfg = {"k": k, "m": m, "shard_bytes": S, "stripes": B}
     if layout != "pitch":
         cfg["layout"] = layout
@@ -605,7 +665,7 @@ def main(argv=None):
         },
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         visible = len(os.sched_getaffinity(0))
         threads = args.cpu_threads or max(1, min(CPU_SHARE, visible))
         line["cpu_baseline"] = cpu_baseline(sb, k, m, erase, args.cpu_seconds,
@@ -618,7 +678,7 @@ def main(argv=None):
                 f"{CPU_SHARE} (its affinity mask shows the whole host); --cpu-threads "
                 "overrides")
     wrong = None
-    if layout == "planar" and args.layout_ab and world == 1 and not S_obj:
+    if args.full and layout == "planar" and args.layout_ab and world == 1 and not S_obj:
         # (one process only: a second resident batch beside the first; freed buffers first)
         del rebuilt
         torch.cuda.empty_cache()

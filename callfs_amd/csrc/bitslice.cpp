@@ -291,21 +291,26 @@ int auto_waves(int R, int prefetch) {
   return std::max(1, std::min(8, 512 / need));
 }
 constexpr int kSpillLimit = 16;  // VGPRs spilled that a floor may cost before it is lowered
+
+std::vector<std::string> compile_options(const std::string& arch) {
+  return {"--offload-arch=" + arch, "-O3", "-std=c++17", "-fno-gpu-rdc",
+          "-Rpass-analysis=kernel-resource-usage"};
+}
 }  // namespace
 
 void Worker::warm_compiler() {
-  // the constructs the generated kernels use (a bit-select, non-temporal 16-B loads and stores)
-  static const char* src =
-      "typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));\n"
-      "extern \"C\" __global__ void warm(const u32x4* a, u32x4* b) {\n"
-      "  u32x4 x = __builtin_nontemporal_load(a + threadIdx.x);\n"
-      "  x.x = __builtin_amdgcn_bitop3_b32(x.x, x.y, x.z, 0xCA);\n"
-      "  __builtin_nontemporal_store(x, b + threadIdx.x);\n"
-      "}\n";
+  // a generated kernel (the smallest network with two input shards) under the options of the
+  // real compiles: a hand-written stand-in with a bit-select and non-temporal accesses left
+  // two of comgr's lazy statics to the first real compile, which registered their destructors
+  // after drain(), and a compile in flight at exit then read what they had freed (a process
+  // whose comgr cache was cold: tests/native/bs_worker.cpp from a fresh home directory)
+  const uint8_t coef[2] = {2, 3};
+  GenOptions opt;
+  opt.min_waves = auto_waves(1, opt.prefetch);
   std::string err;
   int spills = 0;
-  (void)rtc_compile(src, {"--offload-arch=" + target_arch(), "-O3", "-std=c++17", "-fno-gpu-rdc"},
-                    &err, &spills);
+  (void)rtc_compile(kernel_source(build_network(2, 1, coef), "rs_bs", opt, sizeof(Args)),
+                    compile_options(target_arch()), &err, &spills);
 }
 
 void Kernel::compile_locked(std::unique_lock<std::mutex>& lk) {
@@ -322,8 +327,7 @@ void Kernel::compile_locked(std::unique_lock<std::mutex>& lk) {
   std::string src = kernel_source(net, "rs_bs", opt, sizeof(Args));
   int ver_major = 0, ver_minor = 0;
   (void)hiprtcVersion(&ver_major, &ver_minor);
-  const std::vector<std::string> opts = {"--offload-arch=" + arch, "-O3", "-std=c++17",
-                                         "-fno-gpu-rdc", "-Rpass-analysis=kernel-resource-usage"};
+  const std::vector<std::string> opts = compile_options(arch);
   // keyed by the first source tried: the cache holds the code object the search accepted
   std::string keytxt = src + arch + std::to_string(ver_major) + "." + std::to_string(ver_minor);
   for (const auto& o : opts) keytxt += o;

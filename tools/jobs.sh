@@ -11,10 +11,10 @@ JOBS="$(cd "$(dirname "$0")" && pwd)/$(basename "$0")"
 # K below its depth). Usage: bash tools/jobs.sh bench_r06 <tag>
 job_bench_r06() {
 T=${1:-bench}; O=gpurun_out/r06/$T; mkdir -p $O
-timeout -k 10 300 python3 -u bench.py > $O/bench.log 2> $O/bench.err || exit $?
+timeout -k 10 300 python3 -u bench.py --full > $O/bench.log 2> $O/bench.err || exit $?
 echo "bench ok"; tail -c 600 $O/bench.log
 timeout -k 10 300 python3 -u bench.py --k 20 --m 16 --erase 0,1,2,3,4,5,6,7,20,21,22,23,24,25,26,27 \
-  --layout-ab 0 --cpu-seconds 3 > $O/bench_rs20_16.log 2> $O/bench_rs20_16.err || exit $?
+  --full --layout-ab 0 --cpu-seconds 3 > $O/bench_rs20_16.log 2> $O/bench_rs20_16.err || exit $?
 echo "wide bench ok"
 timeout -k 10 900 python3 callfs_amd/build.py --ab > /dev/null 2> $O/build_ab.err || exit $?
 CALLFS_RS_LIB=$PWD/build/ab/libcallfs_rs_ab.so timeout -k 10 300 python3 -u -m pytest -x -q --timeout 120 \
@@ -428,7 +428,7 @@ find "$OUT" -name "*.csv" | head -20
 # place) and the planar layout; plus the bench shape. Usage: bash tools/jobs.sh readall_bench <tag>
 job_readall_bench() {
 R="$GRAFT_REPO_ROOT"; TAG="${1:-readall}"; O="$R/gpurun_out/$TAG"; mkdir -p "$O"; cd "$R"
-run() { timeout -k 10 300 python3 -u bench.py --steps 20 --cpu-seconds 0 --layout-ab 0 "$@"; }
+run() { timeout -k 10 300 python3 -u bench.py --full --steps 20 --cpu-seconds 0 --layout-ab 0 "$@"; }
 run --shard-bytes 6710887 --split-layout readall > "$O/readall_fresh.log" 2>&1 || exit $?
 run --shard-bytes 6710887 --split-layout readall --decode-into inplace > "$O/readall_inplace.log" 2>&1 || exit $?
 run --shard-bytes 6710887 > "$O/planar_cfg12.log" 2>&1 || exit $?
@@ -473,12 +473,12 @@ job_rehearse_ranks() {
 cd "$GRAFT_REPO_ROOT"; OUT="gpurun_out/${1:-ranks}"; mkdir -p "$OUT"
 export MASTER_ADDR=127.0.0.1
 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29511 \
-  bench.py --gpus 4 --steps 10 --warmup 2 > "$OUT/weak4.log" 2>&1 || exit $?
+  bench.py --full --gpus 4 --steps 10 --warmup 2 > "$OUT/weak4.log" 2>&1 || exit $?
 grep '^{' "$OUT/weak4.log" | cut -c1-160
-timeout -k 10 300 python3 bench.py --object-bytes 1073741824 --steps 5 --warmup 1 --cpu-seconds 0 > "$OUT/obj1.log" 2>&1 || exit $?
+timeout -k 10 300 python3 bench.py --full --object-bytes 1073741824 --steps 5 --warmup 1 --cpu-seconds 0 > "$OUT/obj1.log" 2>&1 || exit $?
 grep '^{' "$OUT/obj1.log" | cut -c1-160
 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29512 \
-  bench.py --gpus 4 --object-bytes 1073741824 --steps 5 --warmup 1 > "$OUT/obj4.log" 2>&1 || exit $?
+  bench.py --full --gpus 4 --object-bytes 1073741824 --steps 5 --warmup 1 > "$OUT/obj4.log" 2>&1 || exit $?
 grep '^{' "$OUT/obj4.log" | cut -c1-160
 }
 
