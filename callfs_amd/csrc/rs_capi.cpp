@@ -35,6 +35,7 @@
 #include "copy_pool.hpp"
 #include "dispatch.hpp"
 #include "gf256.hpp"
+#include "mixed_tables.hpp"
 #include "rs_kernels.hpp"
 #include "sha256.hpp"
 #include "tune_table.hpp"
@@ -1566,6 +1567,14 @@ int rs_reconstruct_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* s
 
 // ---- device-resident ----------------------------------------------------------------
 
+// A mixed plan (rs_plan_create_mixed): the pattern tables and where each
+// piece sits in the plan's device buffer.
+struct MixedPlan {
+  MixedTables t;
+  size_t in_off = 0, pat_off = 0;
+  std::vector<size_t> out_off, vmask_off, arena_off;  // per launch group
+};
+
 struct rs_plan {
   int device = 0;
   size_t S = 0;
@@ -1577,7 +1586,47 @@ struct rs_plan {
   LayoutHint hint;
   std::vector<int> orders;  // per launch group: tile order from rs_plan_tune, -1 = rule
   std::mutex mu;            // orders are written by rs_plan_tune, read by rs_plan_launch
+  // set for a mixed plan, whose `tables` is null; layout.status_off is valid for both kinds
+  std::unique_ptr<MixedPlan> mixed;
 };
+
+namespace {
+
+ApplyArgs mixed_group_args(const rs_plan& plan, size_t gi, MixedArgs& x) {
+  const MixedPlan& mp = *plan.mixed;
+  const MixedGroup& g = mp.t.groups[gi];
+  auto* d = static_cast<uint8_t*>(plan.dmeta);
+  ApplyArgs a{};
+  a.in_tab = reinterpret_cast<const uint8_t* const*>(d + mp.in_off);
+  a.out_tab = reinterpret_cast<uint8_t* const*>(d + mp.out_off[gi]);
+  a.ltabs = d + mp.arena_off[gi];
+  a.S = plan.S;
+  a.status = reinterpret_cast<int*>(d + plan.layout.status_off);
+  a.status_stride = 1;
+  a.K = mp.t.k;
+  a.R = g.R;
+  a.batch = plan.batch;
+  x.pat = reinterpret_cast<const uint32_t*>(d + mp.pat_off);
+  x.vmask = reinterpret_cast<const uint32_t*>(d + mp.vmask_off[gi]);
+  x.tab_stride = static_cast<uint32_t>(g.tab_stride);
+  return a;
+}
+
+hipError_t launch_mixed_groups(const rs_plan& plan, hipStream_t s, LaunchEvents ev) {
+  const size_t ng = plan.mixed->t.groups.size();
+  for (size_t gi = 0; gi < ng; ++gi) {
+    MixedArgs x{};
+    const ApplyArgs a = mixed_group_args(plan, gi, x);
+    LaunchEvents g;
+    g.start = gi == 0 ? ev.start : nullptr;
+    g.stop = gi + 1 == ng ? ev.stop : nullptr;
+    const hipError_t e = launch_mixed(a, x, s, g);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace
 
 int rs_plan_create(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                    const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
@@ -1664,6 +1713,10 @@ int rs_plan_launch_timed(rs_plan* plan, void* stream, void* start_event, void* s
   LaunchEvents ev;
   ev.start = static_cast<hipEvent_t>(start_event);
   ev.stop = static_cast<hipEvent_t>(stop_event);
+  if (plan->mixed) {
+    HIPCHK(launch_mixed_groups(*plan, static_cast<hipStream_t>(stream), ev));
+    return RS_OK;
+  }
   HIPCHK(launch_groups(*plan->tables, plan->layout, plan->batch,
                        static_cast<uint8_t*>(plan->dmeta), plan->S,
                        static_cast<hipStream_t>(stream), /*status_stride=*/1, plan->hint,
@@ -1679,6 +1732,7 @@ int rs_plan_launch_ceiling_timed(rs_plan* plan, void* stream, int mode, void* st
                                  void* stop_event) {
   DeviceGuard dg;
   if (!plan || mode < 0 || mode > 8) return RS_E_ARG;
+  if (plan->mixed) return RS_E_ARG;  // no traffic ceilings for mixed plans
   // the product implements RS_CEIL_READ / RS_CEIL_WRITE; the other modes are the A/B build's
   // (tools/callfs_rs_ab.h)
   if (!kAbInstances && mode != RS_CEIL_READ && mode != RS_CEIL_WRITE) return RS_E_ARG;
@@ -1743,6 +1797,10 @@ bool tune_log() {
 int rs_plan_tune(rs_plan* plan, void* stream, int reps, int* orders, int max_groups) {
   DeviceGuard dg;
   if (!plan || reps < 1 || max_groups < 0 || (max_groups > 0 && !orders)) return RS_E_ARG;
+  if (plan->mixed) {  // one form, one tile order: nothing to time
+    for (int i = 0; i < max_groups; ++i) orders[i] = -1;
+    return RS_OK;
+  }
   HIPCHK(hipSetDevice(plan->device));
   auto s = static_cast<hipStream_t>(stream);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1835,6 +1893,12 @@ int rs_plan_tune(rs_plan* plan, void* stream, int reps, int* orders, int max_gro
 // tests that run every instance.
 int rs_plan_set_orders(rs_plan* plan, const int* orders, int n) {
   if (!plan || n < 0 || (n > 0 && !orders)) return RS_E_ARG;
+  if (plan->mixed) {  // only "the rule" (-1) for every group
+    if (static_cast<size_t>(n) > plan->mixed->t.groups.size()) return RS_E_ARG;
+    for (int gi = 0; gi < n; ++gi)
+      if (orders[gi] != -1) return RS_E_ARG;
+    return RS_OK;
+  }
   const Tables& t = *plan->tables;
   if (static_cast<size_t>(n) > t.groups.size()) return RS_E_ARG;
   auto* d = static_cast<uint8_t*>(plan->dmeta);
@@ -1860,6 +1924,12 @@ int rs_tune_table_entries(void) { return static_cast<int>(tune_table().size()); 
 
 int rs_plan_forms(const rs_plan* plan, int* forms, int max_groups) {
   if (!plan || max_groups < 0 || (max_groups > 0 && !forms)) return RS_E_ARG;
+  if (plan->mixed) {
+    const int ng = static_cast<int>(plan->mixed->t.groups.size());
+    for (int gi = 0; gi < ng && gi < max_groups; ++gi)
+      forms[gi] = kOrderMixed + RS_ORDER_CONSECUTIVE;
+    return ng;
+  }
   auto* p = const_cast<rs_plan*>(plan);
   std::vector<int> orders;
   {
@@ -1901,7 +1971,8 @@ int rs_plan_status(rs_plan* plan, void* stream, int* corrupt) {
 uint64_t rs_plan_bytes(const rs_plan* plan) { return plan ? plan->bytes : 0; }
 
 int rs_plan_groups(const rs_plan* plan) {
-  return plan ? static_cast<int>(plan->tables->groups.size()) : 0;
+  if (!plan) return 0;
+  return static_cast<int>(plan->mixed ? plan->mixed->t.groups.size() : plan->tables->groups.size());
 }
 
 void rs_plan_destroy(rs_plan* plan) {
@@ -1934,6 +2005,99 @@ int rs_decode_dev(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                   const uint8_t* present, uint8_t* const* shards, void* stream) {
   if (!present) return RS_E_ARG;
   return one_shot(ctx, device, k, m, S, batch, present, shards, stream);
+}
+
+int rs_plan_create_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
+                         const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shards || !out || !present || batch < 1) return RS_E_ARG;
+  *out = nullptr;
+  const int n = k + m;
+  // every stripe needs k present shards, whichever path the plan takes
+  for (int b = 0; b < batch; ++b) {
+    int np = 0;
+    for (int i = 0; i < n; ++i) np += present[static_cast<size_t>(b) * n + i] != 0;
+    if (np < k) return RS_E_TOO_FEW_SHARDS;
+  }
+  // all masks equal: exactly the uniform plan (its forms, bit-sliced kernels included)
+  if (mixed_masks_equal(n, batch, present))
+    return rs_plan_create(ctx, device, k, m, S, batch, present, shards, out);
+  Device* dev = ctx->device(device);
+  if (!dev) return RS_E_ARG;
+  auto plan = std::make_unique<rs_plan>();
+  plan->mixed = std::make_unique<MixedPlan>();
+  MixedPlan& mp = *plan->mixed;
+  switch (build_mixed_tables(k, m, batch, present, mp.t)) {
+    case MixedError::kOk: break;
+    case MixedError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
+    case MixedError::kSingular: return RS_E_SINGULAR;
+  }
+  plan->device = device;
+  plan->S = S;
+  plan->batch = batch;
+  // reads: k valid shards + the compared shards; writes: the missing ones = n per stripe
+  plan->bytes = static_cast<uint64_t>(batch) * S * static_cast<uint64_t>(n);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off = round_up(off + bytes, 256);
+    return o;
+  };
+  const size_t P = mp.t.patterns.size();
+  plan->layout.status_off = take(sizeof(int) * static_cast<size_t>(batch));
+  mp.in_off = take(sizeof(void*) * static_cast<size_t>(batch) * k);
+  mp.pat_off = take(sizeof(uint32_t) * static_cast<size_t>(batch));
+  for (const MixedGroup& g : mp.t.groups) {
+    mp.out_off.push_back(take(sizeof(void*) * static_cast<size_t>(batch) * g.R));
+    mp.vmask_off.push_back(take(sizeof(uint32_t) * P));
+    mp.arena_off.push_back(take(g.arena.size()));
+  }
+  plan->layout.total = off;
+  std::vector<uint8_t> h(off, 0);
+  auto shard_ptr = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
+  auto* in = reinterpret_cast<const uint8_t**>(h.data() + mp.in_off);
+  for (int b = 0; b < batch; ++b) {
+    const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
+    for (int i = 0; i < k; ++i) in[static_cast<size_t>(b) * k + i] = shard_ptr(b, pt.valid[i]);
+  }
+  std::memcpy(h.data() + mp.pat_off, mp.t.pat.data(), sizeof(uint32_t) * mp.t.pat.size());
+  for (size_t gi = 0; gi < mp.t.groups.size(); ++gi) {
+    const MixedGroup& g = mp.t.groups[gi];
+    auto* o = reinterpret_cast<uint8_t**>(h.data() + mp.out_off[gi]);
+    for (int b = 0; b < batch; ++b) {
+      const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
+      for (int r = 0; r < g.R; ++r)
+        o[static_cast<size_t>(b) * g.R + r] = shard_ptr(b, pt.rows[g.row0 + r]);
+    }
+    std::memcpy(h.data() + mp.vmask_off[gi], g.vmask.data(), sizeof(uint32_t) * P);
+    std::memcpy(h.data() + mp.arena_off[gi], g.arena.data(), g.arena.size());
+  }
+  HIPCHK(hipSetDevice(device));
+  if (hipMalloc(&plan->dmeta, off) != hipSuccess) return RS_E_NOMEM;
+  if (hipMemcpy(plan->dmeta, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(plan->dmeta);
+    return RS_E_HIP;
+  }
+  // the device copy is all a launch reads: the host arenas can go
+  for (MixedGroup& g : mp.t.groups) std::vector<uint8_t>().swap(g.arena);
+  *out = plan.release();
+  return RS_OK;
+}
+
+int rs_decode_dev_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
+                        const uint8_t* present, uint8_t* const* shards, void* stream) {
+  if (!present) return RS_E_ARG;
+  rs_plan* p = nullptr;
+  int rc = rs_plan_create_mixed(ctx, device, k, m, S, batch, present, shards, &p);
+  if (rc) return rc;
+  rc = rs_plan_launch(p, stream);
+  int corrupt = 0;
+  if (!rc) rc = rs_plan_status(p, stream, &corrupt);
+  rs_plan_destroy(p);
+  if (!rc && corrupt) rc = RS_E_CORRUPT;
+  return rc;
 }
 
 // ---- batched SHA-256 (ShardChecksum) ------------------------------------------------

@@ -457,6 +457,8 @@ void set_slice_tiles_for_tuning(long long tiles) {
   g_slice_tiles_override.store(tiles, std::memory_order_relaxed);
 }
 
+uint32_t launch_slice_tiles(int streams) { return slice_tiles(streams); }
+
 namespace {
 
 TileOrder lds_rule(const ApplyArgs& a) {

@@ -194,6 +194,29 @@ hipError_t launch_ceiling(ApplyArgs a, hipStream_t stream, int order, int mode,
                           LaunchEvents ev = {});
 
 
+// ---- mixed launches (rs_mixed.hip) --------------------------------------
+// One launch group of a batch whose stripes have different erasure patterns: stripe b runs
+// pattern p = pat[b], whose nibble tables sit at a.ltabs + p * tab_stride and whose compare
+// mask is vmask[p] (a.verify_mask is not read; a.tabs and a.bs are unused). Host side:
+// mixed_tables.hpp.
+struct MixedArgs {
+  const uint32_t* pat;    // [batch] pattern of each stripe
+  const uint32_t* vmask;  // [P] verify mask of each pattern for this launch group
+  uint32_t tab_stride;    // bytes between two patterns' tables (a multiple of 256)
+};
+
+// (kOrderMixed + the TileOrder it runs in, always consecutive: rs_plan_forms of a mixed plan)
+constexpr int kOrderMixed = 512;
+
+// Enqueues the launch group: the mixed nibble-table kernel over [0, S) for S >= 16 (the
+// S % 16 tail inside it, unaligned 16-B accesses on misaligned shards), the mixed byte
+// kernel for S < 16. Consecutive tile order, sliced like launch_apply; never the bit-sliced
+// path, the tune table or a tile-order rule. ev as for launch_apply.
+hipError_t launch_mixed(ApplyArgs a, const MixedArgs& x, hipStream_t stream, LaunchEvents ev = {});
+
+// Tiles per slice of a sliced launch (launch_apply's rule) for `streams` shard streams.
+uint32_t launch_slice_tiles(int streams);
+
 // Tuning hook for tools/kbench.hip (not part of the C ABI): tiles per launch slice for
 // every later launch_apply in the process; 0 = never slice, < 0 = the built-in rule
 // (CALLFS_RS_MAX_TILES_PER_LAUNCH or ~4 GiB of traffic per slice).

@@ -1,0 +1,254 @@
+// Mixed launches: one launch group over a batch in which every stripe has
+// its own erasure pattern. The kernels are the nibble-table LDS kernel of rs_apply.hpp with
+// the tables and the compare mask chosen per block: tiles never straddle stripes, so a
+// block reads its stripe's pattern p = pat[stripe] (a wave-uniform scalar load), stages
+// pattern p's tables from the launch group's arena into LDS and takes vmask[p] as its
+// verify mask. Input loop, lookups, accumulation, stores and compares are the helpers of
+// rs_apply.hpp; existing kernel instances are untouched.
+#include <algorithm>
+#include <array>
+
+#include <hip/hip_ext.h>
+
+#include "dispatch.hpp"
+#include "rs_apply.hpp"
+
+namespace callfs {
+
+namespace dev {
+
+// Ring of three input vectors for RT <= 8 (as LdsPolicy), with the Verify rows' compare
+// loads issued 4 shards before the end of the loop for RT <= 4 (as LdsVerifyPolicy: almost
+// every mixed launch compares rows); the unrolled 5-slot ring with SDWA table addresses for
+// RT 9..16 (as LdsWidePolicy). Consecutive tile order.
+using MixedPolicy4 = Policy<2, 1, true, true, false, 512, 2, 0, 0, false, 0, false, 0, 4>;
+using MixedPolicy8 = Policy<2, 1, true, true, false, 512, 2, 0>;
+using MixedPolicy16 = Policy<2, 1, true, true, false, 512, 4, 0, 1, false, false, true>;
+template <int RT>
+using MixedPolicy = typename std::conditional<
+    (RT > 8), MixedPolicy16, typename std::conditional<(RT > 4), MixedPolicy8, MixedPolicy4>::type>::type;
+
+// An RT instance serves every R <= RT (rows >= R are computed and dropped). One tile of
+// P::TILE_VECS vectors per block; block b works on tile a.t_base + b in consecutive order.
+// (Blocks that work on 2..16 consecutive tiles of a stripe, to pay the table prologue once,
+// measured 6-15 % slower: DESIGN.md §5.8.)
+template <int RT, class P>
+__global__ __launch_bounds__(P::BS) __attribute__((amdgpu_waves_per_eu(P::WPE, lds_max_waves<RT>())))
+void rs_apply_mixed(ApplyArgs a, MixedArgs x) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  constexpr int BS = P::BS;
+  constexpr int W = LdsAcc<RT>::W;
+  constexpr int TV = P::TILE_VECS;
+  static_assert(P::REALIGN == 0 && P::WIX == 0 && P::DMA == 0 && !P::NOMATH && !P::PERSIST && P::ORD == 0,
+                "the plain ring forms in consecutive order only");
+  using AccT = typename LdsAcc<RT>::T;
+  const int K = a.K;
+  const int R = a.R;
+  const uint32_t tps = static_cast<uint32_t>((a.nvec + TV - 1) / TV);
+  const uint32_t ntiles = tps * static_cast<uint32_t>(a.batch);
+  const uint32_t t = a.t_base + blockIdx.x;
+  if (t >= ntiles) return;  // block-uniform
+  const uint32_t stripe = t / tps, tile = t - stripe * tps;
+  // the stripe's pattern: its tables and its compare mask (all wave-uniform)
+  const uint32_t p = as_const(x.pat)[stripe];
+  a.verify_mask = as_const(x.vmask)[p];
+  const uint64_t v0 = static_cast<uint64_t>(tile) * BS + threadIdx.x;
+  cptr<const uint8_t*> in = as_const(a.in_tab) + static_cast<size_t>(stripe) * K;
+  cptr<uint8_t*> out = as_const(a.out_tab) + static_cast<size_t>(stripe) * R;
+  const bool active = v0 < a.nvec;
+  auto ld = [&](int i) { return load16<P>(reinterpret_cast<const uint4*>(in[i]) + v0); };
+  // The first input vectors go out before the table prologue: the prologue is a global
+  // load that depends on pat[stripe], and a block has one tile to hide it behind.
+  constexpr int NPRE = P::RING == 0 ? 2 : P::PD;
+  uint4 xr[P::RING == 0 ? 3 : P::PD + 1];
+#pragma unroll
+  for (int s = 0; s < NPRE; ++s) xr[s] = make_uint4(0, 0, 0, 0);
+  if (active) {
+#pragma unroll
+    for (int s = 0; s < NPRE; ++s)
+      if (s < K) xr[s] = ld(s);
+  }
+  {
+    const uint4* src = reinterpret_cast<const uint4*>(a.ltabs + static_cast<size_t>(p) * x.tab_stride);
+    uint4* dst = reinterpret_cast<uint4*>(smem);
+    for (int j = threadIdx.x; j < K * 2 * W; j += BS) dst[j] = src[j];
+  }
+  __syncthreads();
+  const uint32_t lds0 = static_cast<uint32_t>(
+      reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*)smem));
+  if (a.tail_in_vec) {
+    const uint32_t j = tail_lane<BS>(a.tail_in_vec, tile);
+    if (j != ~0u) lds_tail<RT>(a, in, out, stripe, lds0, j);
+  }
+  if (!active) return;
+  AccT acc[4][4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[w][j] = lds_zero<RT>();
+  constexpr bool kVpf = P::VPF > 0 && RT <= 4;
+  uint4 vpre[kVpf ? RT : 1];
+#pragma unroll
+  for (int r = 0; r < (kVpf ? RT : 1); ++r) vpre[r] = make_uint4(0, 0, 0, 0);
+
+  if constexpr (P::RING == 0) {
+    // ring of three shard vectors: shard i is consumed while i+1, i+2 load
+    if (K < 2) xr[1] = xr[0];
+    xr[2] = xr[0];
+#pragma unroll 1
+    for (int i = 0; i < K; ++i) {
+      if (i + 2 < K) xr[2] = ld(i + 2);
+      if constexpr (kVpf) {
+        if (i == (K > P::VPF ? K - P::VPF : 0)) {
+#pragma unroll
+          for (int r = 0; r < RT; ++r)
+            if (r < R && ((a.verify_mask >> r) & 1u))
+              vpre[r] = load16<P>(reinterpret_cast<const uint4*>(out[r]) + v0);
+        }
+      }
+      lds_mac<RT, P::SDWA>(acc, xr[0], lds0 + static_cast<uint32_t>(i) * 32u * W);
+      xr[0] = xr[1];
+      xr[1] = xr[2];
+    }
+  } else {
+    // PD+1 slots, shard i in slot i % NR; shard i+PD loads into the slot shard i-1 left
+    constexpr int PD = P::PD, NR = P::PD + 1;
+#pragma unroll 1
+    for (int i0 = 0; i0 < K; i0 += NR) {
+#pragma unroll
+      for (int s = 0; s < NR; ++s) {
+        const int i = i0 + s;
+        if (i < K) {
+          if (i + PD < K) xr[(s + PD) % NR] = ld(i + PD);
+          lds_mac<RT, P::SDWA>(acc, xr[s], lds0 + static_cast<uint32_t>(i) * 32u * W);
+        }
+      }
+    }
+  }
+
+  bool bad = false;
+#pragma unroll
+  for (int r = 0; r < RT; ++r) {
+    if (r >= R) continue;  // wave-uniform
+    const uint4 o = make_uint4(lds_row<RT>(acc[0], r), lds_row<RT>(acc[1], r),
+                               lds_row<RT>(acc[2], r), lds_row<RT>(acc[3], r));
+    uint4* dst = reinterpret_cast<uint4*>(out[r]) + v0;
+    if ((a.verify_mask >> r) & 1u) {
+      uint4 y;
+      if constexpr (kVpf) y = vpre[r];
+      else y = load16<P>(dst);
+      bad |= ((y.x ^ o.x) | (y.y ^ o.y) | (y.z ^ o.z) | (y.w ^ o.w)) != 0;
+    } else {
+      store16<P>(dst, o);
+    }
+  }
+  if (bad) atomicOr(a.status + static_cast<size_t>(stripe) * a.status_stride, 1);
+}
+
+// S < 16: one byte position per thread, 16 threads per stripe; the nibble tables are read
+// from the arena in global memory (a launch of batch * S bytes has nothing to amortise an
+// LDS prologue over). An RT instance (8 or 16: the entry width) serves every R <= RT.
+template <int RT>
+__global__ __launch_bounds__(kBlock) void rs_apply_mixed_bytes(ApplyArgs a, MixedArgs x) {
+  constexpr int W = LdsAcc<RT>::W;
+  using AccT = typename LdsAcc<RT>::T;
+  const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t stripe = g >> 4, b = g & 15u;
+  if (stripe >= static_cast<uint32_t>(a.batch) || b >= a.S) return;
+  const uint32_t p = x.pat[stripe];
+  const uint32_t vm = x.vmask[p];
+  const uint8_t* tabs = a.ltabs + static_cast<size_t>(p) * x.tab_stride;
+  const uint8_t* const* in = a.in_tab + static_cast<size_t>(stripe) * a.K;
+  uint8_t* const* out = a.out_tab + static_cast<size_t>(stripe) * a.R;
+  AccT t = lds_zero<RT>();
+  for (int i = 0; i < a.K; ++i) {
+    const uint32_t v = in[i][b];
+    const uint8_t* ti = tabs + static_cast<size_t>(i) * 32u * W;
+    t = t ^ *reinterpret_cast<const AccT*>(ti + (v & 15u) * W) ^
+        *reinterpret_cast<const AccT*>(ti + 16u * W + (v >> 4) * W);
+  }
+  bool bad = false;
+  for (int r = 0; r < a.R && r < RT; ++r) {
+    const uint8_t v = static_cast<uint8_t>(lds_byte<RT>(t, r));
+    if ((vm >> r) & 1u) bad |= out[r][b] != v;
+    else out[r][b] = v;
+  }
+  if (bad) atomicOr(a.status + static_cast<size_t>(stripe) * a.status_stride, 1);
+}
+
+}  // namespace dev
+
+namespace {
+
+using MixedFn = void (*)(ApplyArgs, MixedArgs);
+
+// [0]: R <= 4, [1]: R 5..8, [2]: R 9..16
+const std::array<MixedFn, 3> kMixed = {&dev::rs_apply_mixed<4, dev::MixedPolicy<4>>,
+                                       &dev::rs_apply_mixed<8, dev::MixedPolicy<8>>,
+                                       &dev::rs_apply_mixed<16, dev::MixedPolicy<16>>};
+const std::array<MixedFn, 2> kMixedBytes = {&dev::rs_apply_mixed_bytes<8>,
+                                            &dev::rs_apply_mixed_bytes<16>};
+static_assert(dev::MixedPolicy<4>::BS == 512 && dev::MixedPolicy<8>::BS == 512 &&
+                  dev::MixedPolicy<16>::BS == 512 && dev::MixedPolicy<4>::TILE_VECS == 512 &&
+                  dev::MixedPolicy<8>::TILE_VECS == 512 && dev::MixedPolicy<16>::TILE_VECS == 512,
+              "one grid shape for every mixed instance");
+constexpr uint32_t kMixedBlock = 512, kMixedTileVecs = 512;
+
+// 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
+// per-device attribute (dispatch.hpp DeviceOnce)
+DeviceOnce g_mixed_wide_lds;
+
+template <class... Args>
+void dispatch(void (*fn)(Args...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+              const LaunchEvents& ev, bool first, bool last, Args... args) {
+  if (ev.start || ev.stop)
+    hipExtLaunchKernelGGL(fn, grid, block, static_cast<uint32_t>(lds), stream,
+                          first ? ev.start : nullptr, last ? ev.stop : nullptr, 0, args...);
+  else
+    hipLaunchKernelGGL(fn, grid, block, lds, stream, args...);
+}
+
+}  // namespace
+
+hipError_t launch_mixed(ApplyArgs a, const MixedArgs& x, hipStream_t stream, LaunchEvents ev) {
+  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
+      !x.pat || !x.vmask || !a.in_tab || !a.out_tab || !a.status)
+    return hipErrorInvalidValue;
+  if (a.S == 0) return hipSuccess;
+  a.t_base = 0;
+  a.nvec = a.S / 16;
+  if (a.nvec == 0) {
+    const uint64_t threads = static_cast<uint64_t>(a.batch) * 16u;
+    dispatch(kMixedBytes[a.R > 8 ? 1 : 0], dim3(static_cast<unsigned>((threads + dev::kBlock - 1) / dev::kBlock)),
+             dim3(dev::kBlock), 0, stream, ev, true, true, a, x);
+    return hipGetLastError();
+  }
+  // the S % 16 tail: wave 0 of each stripe's first tile (rs_apply.hpp tail_lane)
+  a.tail_in_vec = a.nvec * 16 < a.S ? 1u : 0u;
+  const size_t lds = dev::lds_bytes(a.K, a.R > 8 ? 16 : 8);
+  const MixedFn fn = kMixed[a.R > 8 ? 2 : a.R > 4 ? 1 : 0];
+  if (lds > (64u << 10)) {
+    int device = -1;
+    if (hipGetDevice(&device) != hipSuccess) return hipErrorInvalidDevice;
+    g_mixed_wide_lds.run(device, 0, [fn] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+    });
+  }
+  const uint64_t tps = (a.nvec + kMixedTileVecs - 1) / kMixedTileVecs;
+  const uint64_t ntiles = tps * static_cast<uint64_t>(a.batch);
+  if (ntiles > 0x7fffffffull) return hipErrorInvalidValue;
+  const uint32_t grid = static_cast<uint32_t>(ntiles);
+  // long grids in equal consecutive slices, as launch_apply cuts them
+  const uint32_t lim = launch_slice_tiles(a.K + a.R);
+  const uint32_t nsl = grid / 2 > lim ? (grid + lim - 1) / lim : 1;
+  const uint32_t per = (grid + nsl - 1) / nsl;
+  for (uint32_t t0 = 0; t0 < grid; t0 += per) {
+    a.t_base = t0;
+    dispatch(fn, dim3(std::min(per, grid - t0)), dim3(kMixedBlock), lds, stream, ev, t0 == 0,
+             t0 + per >= grid, a, x);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace callfs

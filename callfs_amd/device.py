@@ -140,12 +140,33 @@ class StripeBatch:
             t.random_(0, 256, generator=g)
 
 
+def _mask_rows(present):
+    """The rows of a per-stripe presence mask (a batch x n sequence or array), or None
+    when `present` is None or a flat sequence of flags."""
+    if present is None:
+        return None
+    if hasattr(present, "ndim"):  # numpy array or torch tensor
+        if present.ndim == 1:
+            return None
+        if present.ndim != 2:
+            raise ValueError("present: n flags, or batch rows of n flags")
+        return present.tolist()
+    rows = list(present)
+    if rows and all(hasattr(r, "__len__") for r in rows):
+        return [list(r) for r in rows]
+    if any(hasattr(r, "__len__") for r in rows):
+        raise ValueError("present: n flags, or batch rows of n flags")
+    return None
+
+
 class Plan:
     """rs_plan over explicit device shard pointers (batch*n of them, stripe-major).
 
     present=None is an encode plan (data present, parity missing); otherwise the
     missing shards are reconstructed from the first k present ones and the remaining
-    present parity is re-verified (codec.go:55,59).
+    present parity is re-verified (codec.go:55,59). A flat sequence of k+m flags is one
+    mask for the whole batch; a batch x (k+m) sequence or array gives every stripe its own
+    mask (a mixed plan, DESIGN.md §5.8: one launch repairs stripes with different erasures).
     """
 
     def __init__(self, k: int, m: int, S: int, batch: int, pointers: Sequence[int],
@@ -158,11 +179,22 @@ class Plan:
         self.k, self.m, self.S, self.batch, self.device = k, m, S, batch, device
         ptrs = (ctypes.c_void_p * len(pointers))(*pointers)
         pres = None
+        h = ctypes.c_void_p()
+        rows = _mask_rows(present)
+        if rows is not None:
+            # batch x n flags: a mixed plan, every stripe its own mask (rs_plan_create_mixed)
+            if len(rows) != batch or any(len(r) != n for r in rows):
+                raise ValueError("a per-stripe present needs batch rows of k+m flags")
+            flat = [1 if p else 0 for r in rows for p in r]
+            pres = (ctypes.c_uint8 * (batch * n))(*flat)
+            N.check(N.lib.rs_plan_create_mixed(self.ctx.handle, device, k, m, S, batch, pres, ptrs,
+                                               ctypes.byref(h)), "rs_plan_create_mixed")
+            self.handle = h
+            return
         if present is not None:
             if len(present) != n:
                 raise ValueError("present needs k+m flags")
             pres = (ctypes.c_uint8 * n)(*[1 if p else 0 for p in present])
-        h = ctypes.c_void_p()
         N.check(N.lib.rs_plan_create(self.ctx.handle, device, k, m, S, batch, pres, ptrs,
                                      ctypes.byref(h)), "rs_plan_create")
         self.handle = h
@@ -224,7 +256,8 @@ class Plan:
                    134: "realign-tri-x32", 160: "realign64", 165: "realign64-x8",
                    166: "realign64-x32", 192: "dma", 194: "dma-g2", 195: "dma-q8",
                    198: "dma-x32", 224: "tridb-g4", 225: "tridb-g8", 256: "bs", 257: "bs-g8",
-                   258: "bs-g2", 259: "bs-q8", 260: "bs-q16", 261: "bs-x8", 262: "bs-x32"}
+                   258: "bs-g2", 259: "bs-q8", 260: "bs-q16", 261: "bs-x8", 262: "bs-x32",
+                   512: "mixed"}
 
     def tune(self, reps: int = 5, stream: Optional[torch.cuda.Stream] = None) -> list:
         """rs_plan_tune: time each launch group in every tile order its kernel offers

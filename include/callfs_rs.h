@@ -247,6 +247,32 @@ int rs_encode_dev(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
 int rs_decode_dev(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                   const uint8_t* present, uint8_t* const* shards, void* stream);
 
+/* ---- mixed plans: every stripe its own presence mask ----------
+ * present holds batch*(k+m) flags, stripe b's mask at present + b*(k+m) (nonzero =
+ * present); shards as for rs_plan_create. One launch per launch group reconstructs and
+ * verifies the whole batch: each stripe's missing shards are computed from its own first
+ * k present shards and its remaining present shards are compared, bit-exact with a
+ * uniform plan of that stripe's mask. Any stripe with fewer than k present shards fails
+ * the call with RS_E_TOO_FEW_SHARDS and creates nothing (filter such stripes out first).
+ * When every stripe has the same mask the call builds exactly what rs_plan_create builds
+ * (same kernel forms, bit-sliced ones included). Otherwise the plan runs the mixed
+ * nibble-table kernels: no bit-sliced kernel, no hiprtc compile, no tune-table entry, one
+ * tile order. The returned plan works with rs_plan_launch, _launch_timed, _status,
+ * _stripe_status, _bytes, _groups, _forms and _destroy as any plan does (launches only
+ * enqueue: no allocation, no sync; graph-capturable). For a mixed plan
+ *   rs_plan_bytes   returns batch*(k+m)*S (every shard of every stripe is read, compared or written);
+ *   rs_plan_forms   reports RS_ORDER_MIXED + the tile order (RS_ORDER_CONSECUTIVE);
+ *   rs_plan_tune    returns RS_OK, times nothing and fills orders with -1;
+ *   rs_plan_set_orders accepts only -1 entries (RS_E_ARG for anything else);
+ *   rs_plan_launch_ceiling / _ceiling_timed return RS_E_ARG.
+ * rs_decode_dev_mixed is the one-shot form (build + launch + status + free; synchronous on
+ * `stream`); it returns RS_E_CORRUPT when any stripe's compared shards mismatch. */
+#define RS_ORDER_MIXED 512
+int rs_plan_create_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
+                         const uint8_t* present, uint8_t* const* shards, rs_plan** out);
+int rs_decode_dev_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
+                        const uint8_t* present, uint8_t* const* shards, void* stream);
+
 /* ---- ShardChecksum on device-resident shards (codec.go:81-84; §8(f) of SURVEY.md) ----
  * SHA-256 of `count` messages already in HBM, one digest per message written to
  * `digests` (device memory, 32*count bytes, FIPS 180-4 byte order — hex-encode it for
