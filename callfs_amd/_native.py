@@ -96,6 +96,10 @@ SIGNATURES = {
     "rs_plan_create_mixed": (_int, [_vp, _int, _int, _int, _sz, _int, _u8p, ctypes.POINTER(_vp),
                                     ctypes.POINTER(_vp)]),
     "rs_decode_dev_mixed": (_int, [_vp, _int, _int, _int, _sz, _int, _u8p, ctypes.POINTER(_vp), _vp]),
+    "rs_plan_create_ragged": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
+                                     ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rs_decode_dev_ragged": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
+                                    ctypes.POINTER(_vp), _vp]),
     "rs_sha256_plan_create": (_int, [_vp, _int, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64),
                                      _int, ctypes.POINTER(_vp)]),
     "rs_sha256_plan_launch": (_int, [_vp, _vp, _vp]),

@@ -36,11 +36,14 @@
 #include "dispatch.hpp"
 #include "gf256.hpp"
 #include "mixed_tables.hpp"
+#include "ragged_tables.hpp"
 #include "rs_kernels.hpp"
 #include "sha256.hpp"
 #include "tune_table.hpp"
 
 using namespace callfs;
+
+static_assert(kRaggedTileVecs == kRaggedLaunchTileVecs, "the tile map counts the kernel's tiles");
 
 namespace {
 
@@ -1569,10 +1572,17 @@ int rs_reconstruct_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* s
 
 // A mixed plan (rs_plan_create_mixed): the pattern tables and where each
 // piece sits in the plan's device buffer.
+// A ragged plan (rs_plan_create_ragged) is a mixed plan with a tile map:
+// `ragged` is set, the plan's S is the largest shard size (never 0) and each stripe's own
+// size sits in the device buffer with tile0 and tile_stripe (ragged_tables.hpp).
 struct MixedPlan {
   MixedTables t;
   size_t in_off = 0, pat_off = 0;
   std::vector<size_t> out_off, vmask_off, arena_off;  // per launch group
+  bool ragged = false;
+  bool any_tail = false;  // some stripe's size is no multiple of 16
+  uint32_t ntiles = 0;
+  size_t size_off = 0, tile0_off = 0, tile_stripe_off = 0;
 };
 
 struct rs_plan {
@@ -1620,7 +1630,22 @@ hipError_t launch_mixed_groups(const rs_plan& plan, hipStream_t s, LaunchEvents 
     LaunchEvents g;
     g.start = gi == 0 ? ev.start : nullptr;
     g.stop = gi + 1 == ng ? ev.stop : nullptr;
-    const hipError_t e = launch_mixed(a, x, s, g);
+    hipError_t e;
+    if (plan.mixed->ragged) {
+      const MixedPlan& mp = *plan.mixed;
+      auto* d = static_cast<uint8_t*>(plan.dmeta);
+      RaggedArgs r{};
+      r.pat = x.pat;
+      r.vmask = x.vmask;
+      r.size = reinterpret_cast<const uint64_t*>(d + mp.size_off);
+      r.tile0 = reinterpret_cast<const uint32_t*>(d + mp.tile0_off);
+      r.tile_stripe = reinterpret_cast<const uint32_t*>(d + mp.tile_stripe_off);
+      r.tab_stride = x.tab_stride;
+      r.ntiles = mp.ntiles;
+      e = launch_ragged(a, r, mp.any_tail, s, g);
+    } else {
+      e = launch_mixed(a, x, s, g);
+    }
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -1732,7 +1757,7 @@ int rs_plan_launch_ceiling_timed(rs_plan* plan, void* stream, int mode, void* st
                                  void* stop_event) {
   DeviceGuard dg;
   if (!plan || mode < 0 || mode > 8) return RS_E_ARG;
-  if (plan->mixed) return RS_E_ARG;  // no traffic ceilings for mixed plans
+  if (plan->mixed) return RS_E_ARG;  // no traffic ceilings for mixed and ragged plans
   // the product implements RS_CEIL_READ / RS_CEIL_WRITE; the other modes are the A/B build's
   // (tools/callfs_rs_ab.h)
   if (!kAbInstances && mode != RS_CEIL_READ && mode != RS_CEIL_WRITE) return RS_E_ARG;
@@ -1927,7 +1952,7 @@ int rs_plan_forms(const rs_plan* plan, int* forms, int max_groups) {
   if (plan->mixed) {
     const int ng = static_cast<int>(plan->mixed->t.groups.size());
     for (int gi = 0; gi < ng && gi < max_groups; ++gi)
-      forms[gi] = kOrderMixed + RS_ORDER_CONSECUTIVE;
+      forms[gi] = (plan->mixed->ragged ? kOrderRagged : kOrderMixed) + RS_ORDER_CONSECUTIVE;
     return ng;
   }
   auto* p = const_cast<rs_plan*>(plan);
@@ -1983,17 +2008,22 @@ void rs_plan_destroy(rs_plan* plan) {
   delete plan;
 }
 
-static int one_shot(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
-                    const uint8_t* present, uint8_t* const* shards, void* stream) {
-  rs_plan* p = nullptr;
-  int rc = rs_plan_create(ctx, device, k, m, S, batch, present, shards, &p);
-  if (rc) return rc;
-  rc = rs_plan_launch(p, stream);
+// The one-shot calls' second half: launch, status, free; RS_E_CORRUPT when a stripe mismatched.
+static int launch_once(rs_plan* p, void* stream) {
+  int rc = rs_plan_launch(p, stream);
   int corrupt = 0;
   if (!rc) rc = rs_plan_status(p, stream, &corrupt);
   rs_plan_destroy(p);
   if (!rc && corrupt) rc = RS_E_CORRUPT;
   return rc;
+}
+
+static int one_shot(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
+                    const uint8_t* present, uint8_t* const* shards, void* stream) {
+  rs_plan* p = nullptr;
+  const int rc = rs_plan_create(ctx, device, k, m, S, batch, present, shards, &p);
+  if (rc) return rc;
+  return launch_once(p, stream);
 }
 
 int rs_encode_dev(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
@@ -2005,6 +2035,71 @@ int rs_decode_dev(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                   const uint8_t* present, uint8_t* const* shards, void* stream) {
   if (!present) return RS_E_ARG;
   return one_shot(ctx, device, k, m, S, batch, present, shards, stream);
+}
+
+// Lays out and uploads the device buffer of a mixed plan (plan.mixed->t built, plan.device
+// and plan.batch set): the status words, the shard-pointer tables, pat and per launch group
+// the compare masks and the table arena, each piece 256-B aligned. With `rg` (a ragged plan)
+// also the stripes' sizes, tile0 and tile_stripe.
+static int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rg) {
+  MixedPlan& mp = *plan.mixed;
+  const int k = mp.t.k, n = mp.t.k + mp.t.m, batch = plan.batch;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off = round_up(off + bytes, 256);
+    return o;
+  };
+  const size_t P = mp.t.patterns.size();
+  plan.layout.status_off = take(sizeof(int) * static_cast<size_t>(batch));
+  mp.in_off = take(sizeof(void*) * static_cast<size_t>(batch) * k);
+  mp.pat_off = take(sizeof(uint32_t) * static_cast<size_t>(batch));
+  for (const MixedGroup& g : mp.t.groups) {
+    mp.out_off.push_back(take(sizeof(void*) * static_cast<size_t>(batch) * g.R));
+    mp.vmask_off.push_back(take(sizeof(uint32_t) * P));
+    mp.arena_off.push_back(take(g.arena.size()));
+  }
+  if (rg) {
+    mp.size_off = take(sizeof(uint64_t) * rg->size.size());
+    mp.tile0_off = take(sizeof(uint32_t) * rg->tile0.size());
+    mp.tile_stripe_off = take(sizeof(uint32_t) * rg->tile_stripe.size());
+  }
+  plan.layout.total = off;
+  std::vector<uint8_t> h(off, 0);
+  auto shard_ptr = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
+  auto* in = reinterpret_cast<const uint8_t**>(h.data() + mp.in_off);
+  for (int b = 0; b < batch; ++b) {
+    const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
+    for (int i = 0; i < k; ++i) in[static_cast<size_t>(b) * k + i] = shard_ptr(b, pt.valid[i]);
+  }
+  std::memcpy(h.data() + mp.pat_off, mp.t.pat.data(), sizeof(uint32_t) * mp.t.pat.size());
+  for (size_t gi = 0; gi < mp.t.groups.size(); ++gi) {
+    const MixedGroup& g = mp.t.groups[gi];
+    auto* o = reinterpret_cast<uint8_t**>(h.data() + mp.out_off[gi]);
+    for (int b = 0; b < batch; ++b) {
+      const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
+      for (int r = 0; r < g.R; ++r)
+        o[static_cast<size_t>(b) * g.R + r] = shard_ptr(b, pt.rows[g.row0 + r]);
+    }
+    std::memcpy(h.data() + mp.vmask_off[gi], g.vmask.data(), sizeof(uint32_t) * P);
+    std::memcpy(h.data() + mp.arena_off[gi], g.arena.data(), g.arena.size());
+  }
+  if (rg) {
+    std::memcpy(h.data() + mp.size_off, rg->size.data(), sizeof(uint64_t) * rg->size.size());
+    std::memcpy(h.data() + mp.tile0_off, rg->tile0.data(), sizeof(uint32_t) * rg->tile0.size());
+    std::memcpy(h.data() + mp.tile_stripe_off, rg->tile_stripe.data(),
+                sizeof(uint32_t) * rg->tile_stripe.size());
+  }
+  HIPCHK(hipSetDevice(plan.device));
+  if (hipMalloc(&plan.dmeta, off) != hipSuccess) return RS_E_NOMEM;
+  if (hipMemcpy(plan.dmeta, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(plan.dmeta);
+    plan.dmeta = nullptr;
+    return RS_E_HIP;
+  }
+  // the device copy is all a launch reads: the host arenas can go
+  for (MixedGroup& g : mp.t.groups) std::vector<uint8_t>().swap(g.arena);
+  return RS_OK;
 }
 
 int rs_plan_create_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
@@ -2039,49 +2134,8 @@ int rs_plan_create_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int ba
   plan->batch = batch;
   // reads: k valid shards + the compared shards; writes: the missing ones = n per stripe
   plan->bytes = static_cast<uint64_t>(batch) * S * static_cast<uint64_t>(n);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = round_up(off + bytes, 256);
-    return o;
-  };
-  const size_t P = mp.t.patterns.size();
-  plan->layout.status_off = take(sizeof(int) * static_cast<size_t>(batch));
-  mp.in_off = take(sizeof(void*) * static_cast<size_t>(batch) * k);
-  mp.pat_off = take(sizeof(uint32_t) * static_cast<size_t>(batch));
-  for (const MixedGroup& g : mp.t.groups) {
-    mp.out_off.push_back(take(sizeof(void*) * static_cast<size_t>(batch) * g.R));
-    mp.vmask_off.push_back(take(sizeof(uint32_t) * P));
-    mp.arena_off.push_back(take(g.arena.size()));
-  }
-  plan->layout.total = off;
-  std::vector<uint8_t> h(off, 0);
-  auto shard_ptr = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
-  auto* in = reinterpret_cast<const uint8_t**>(h.data() + mp.in_off);
-  for (int b = 0; b < batch; ++b) {
-    const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
-    for (int i = 0; i < k; ++i) in[static_cast<size_t>(b) * k + i] = shard_ptr(b, pt.valid[i]);
-  }
-  std::memcpy(h.data() + mp.pat_off, mp.t.pat.data(), sizeof(uint32_t) * mp.t.pat.size());
-  for (size_t gi = 0; gi < mp.t.groups.size(); ++gi) {
-    const MixedGroup& g = mp.t.groups[gi];
-    auto* o = reinterpret_cast<uint8_t**>(h.data() + mp.out_off[gi]);
-    for (int b = 0; b < batch; ++b) {
-      const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
-      for (int r = 0; r < g.R; ++r)
-        o[static_cast<size_t>(b) * g.R + r] = shard_ptr(b, pt.rows[g.row0 + r]);
-    }
-    std::memcpy(h.data() + mp.vmask_off[gi], g.vmask.data(), sizeof(uint32_t) * P);
-    std::memcpy(h.data() + mp.arena_off[gi], g.arena.data(), g.arena.size());
-  }
-  HIPCHK(hipSetDevice(device));
-  if (hipMalloc(&plan->dmeta, off) != hipSuccess) return RS_E_NOMEM;
-  if (hipMemcpy(plan->dmeta, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(plan->dmeta);
-    return RS_E_HIP;
-  }
-  // the device copy is all a launch reads: the host arenas can go
-  for (MixedGroup& g : mp.t.groups) std::vector<uint8_t>().swap(g.arena);
+  rc = upload_mixed(*plan, shards, nullptr);
+  if (rc) return rc;
   *out = plan.release();
   return RS_OK;
 }
@@ -2090,14 +2144,66 @@ int rs_decode_dev_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int bat
                         const uint8_t* present, uint8_t* const* shards, void* stream) {
   if (!present) return RS_E_ARG;
   rs_plan* p = nullptr;
-  int rc = rs_plan_create_mixed(ctx, device, k, m, S, batch, present, shards, &p);
+  const int rc = rs_plan_create_mixed(ctx, device, k, m, S, batch, present, shards, &p);
   if (rc) return rc;
-  rc = rs_plan_launch(p, stream);
-  int corrupt = 0;
-  if (!rc) rc = rs_plan_status(p, stream, &corrupt);
-  rs_plan_destroy(p);
-  if (!rc && corrupt) rc = RS_E_CORRUPT;
-  return rc;
+  return launch_once(p, stream);
+}
+
+int rs_plan_create_ragged(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                          const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !sizes || !shards || !out || batch < 1) return RS_E_ARG;
+  *out = nullptr;
+  const int n = k + m;
+  for (int b = 0; b < batch; ++b)
+    if (sizes[b] == 0) return RS_E_NO_DATA;  // upstream Encode: ErrShardNoData
+  // no masks: every stripe is an encode
+  std::vector<uint8_t> encode;
+  if (!present) {
+    encode.resize(static_cast<size_t>(batch) * n);
+    for (size_t j = 0; j < encode.size(); ++j) encode[j] = static_cast<int>(j % n) < k;
+    present = encode.data();
+  }
+  // all sizes equal: exactly the mixed plan of that size (the uniform plan when the masks
+  // are equal too)
+  if (ragged_sizes_equal(batch, sizes))
+    return rs_plan_create_mixed(ctx, device, k, m, sizes[0], batch, present, shards, out);
+  Device* dev = ctx->device(device);
+  if (!dev) return RS_E_ARG;
+  RaggedTables rt;
+  switch (build_ragged_tables(k, m, batch, sizes, present, rt)) {
+    case RaggedError::kOk: break;
+    case RaggedError::kNoData: return RS_E_NO_DATA;
+    case RaggedError::kTooManyTiles: return RS_E_ARG;  // a grid past 2^31 - 1 tiles
+    case RaggedError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
+    case RaggedError::kSingular: return RS_E_SINGULAR;
+  }
+  auto plan = std::make_unique<rs_plan>();
+  plan->mixed = std::make_unique<MixedPlan>();
+  MixedPlan& mp = *plan->mixed;
+  mp.t = std::move(rt.mixed);
+  mp.ragged = true;
+  mp.any_tail = rt.any_tail;
+  mp.ntiles = rt.ntiles;
+  plan->device = device;
+  plan->S = *std::max_element(sizes, sizes + batch);
+  plan->batch = batch;
+  // every shard of every stripe is read, compared or written
+  plan->bytes = rt.total * static_cast<uint64_t>(n);
+  rc = upload_mixed(*plan, shards, &rt);
+  if (rc) return rc;
+  *out = plan.release();
+  return RS_OK;
+}
+
+int rs_decode_dev_ragged(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                         const uint8_t* present, uint8_t* const* shards, void* stream) {
+  rs_plan* p = nullptr;
+  const int rc = rs_plan_create_ragged(ctx, device, k, m, batch, sizes, present, shards, &p);
+  if (rc) return rc;
+  return launch_once(p, stream);
 }
 
 // ---- batched SHA-256 (ShardChecksum) ------------------------------------------------

@@ -214,6 +214,35 @@ constexpr int kOrderMixed = 512;
 // path, the tune table or a tile-order rule. ev as for launch_apply.
 hipError_t launch_mixed(ApplyArgs a, const MixedArgs& x, hipStream_t stream, LaunchEvents ev = {});
 
+// ---- ragged launches (rs_mixed.hip) -------------------------------------
+// One launch group of a batch whose stripes have different shard sizes as well as different
+// erasure patterns. Tile t of the launch belongs to stripe s = tile_stripe[t] and is tile
+// t - tile0[s] of it; the stripe's shard size is size[s] and its pattern pat[s], with tables
+// and compare mask as in MixedArgs (a.S, a.nvec and a.verify_mask are not read). Host side:
+// ragged_tables.hpp.
+struct RaggedArgs {
+  const uint32_t* pat;          // [batch] pattern of each stripe
+  const uint32_t* vmask;        // [P] verify mask of each pattern for this launch group
+  const uint64_t* size;         // [batch] shard bytes of each stripe (>= 1)
+  const uint32_t* tile0;        // [batch + 1] first tile of each stripe
+  const uint32_t* tile_stripe;  // [ntiles] owning stripe of each tile
+  uint32_t tab_stride;          // bytes between two patterns' tables (a multiple of 256)
+  uint32_t ntiles;              // tile0[batch]
+};
+
+// (kOrderRagged + the TileOrder it runs in, always consecutive: rs_plan_forms of a ragged plan)
+constexpr int kOrderRagged = 1024;
+// 16-byte vectors per tile of the tile map (the mixed instances' tile)
+constexpr uint32_t kRaggedLaunchTileVecs = 512;
+
+// Enqueues the launch group: the ragged nibble-table kernel over every stripe's [0, size),
+// each stripe's size % 16 tail inside it when any_tail (a stripe shorter than 16 bytes is one
+// tile that is all tail), unaligned 16-B accesses on misaligned shards. Consecutive tile
+// order, sliced like launch_mixed; never the bit-sliced path, the tune table or a tile-order
+// rule. ev as for launch_apply.
+hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, bool any_tail, hipStream_t stream,
+                         LaunchEvents ev = {});
+
 // Tiles per slice of a sliced launch (launch_apply's rule) for `streams` shard streams.
 uint32_t launch_slice_tiles(int streams);
 

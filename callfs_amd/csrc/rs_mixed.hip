@@ -5,6 +5,9 @@
 // pattern p's tables from the launch group's arena into LDS and takes vmask[p] as its
 // verify mask. Input loop, lookups, accumulation, stores and compares are the helpers of
 // rs_apply.hpp; existing kernel instances are untouched.
+// Ragged launches run the same block body with the stripe, its tile and
+// its shard size read per block from a tile map: one launch group over stripes of
+// different shard sizes.
 #include <algorithm>
 #include <array>
 
@@ -28,30 +31,20 @@ template <int RT>
 using MixedPolicy = typename std::conditional<
     (RT > 8), MixedPolicy16, typename std::conditional<(RT > 4), MixedPolicy8, MixedPolicy4>::type>::type;
 
-// An RT instance serves every R <= RT (rows >= R are computed and dropped). One tile of
-// P::TILE_VECS vectors per block; block b works on tile a.t_base + b in consecutive order.
-// (Blocks that work on 2..16 consecutive tiles of a stripe, to pay the table prologue once,
-// measured 6-15 % slower: DESIGN.md §5.8.)
+// One tile of one stripe: the body every mixed and ragged block runs once it knows its
+// stripe, its tile within the stripe, the stripe's pattern p and (in `a`) the stripe's S,
+// nvec and verify mask. Stages pattern p's tables into LDS, runs the S % 16 tail where
+// a.tail_in_vec places it, then the input ring, lookups, stores and compares.
 template <int RT, class P>
-__global__ __launch_bounds__(P::BS) __attribute__((amdgpu_waves_per_eu(P::WPE, lds_max_waves<RT>())))
-void rs_apply_mixed(ApplyArgs a, MixedArgs x) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+__device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t stripe, uint32_t tile,
+                                           uint32_t p, uint32_t tab_stride) {
   constexpr int BS = P::BS;
   constexpr int W = LdsAcc<RT>::W;
-  constexpr int TV = P::TILE_VECS;
   static_assert(P::REALIGN == 0 && P::WIX == 0 && P::DMA == 0 && !P::NOMATH && !P::PERSIST && P::ORD == 0,
                 "the plain ring forms in consecutive order only");
   using AccT = typename LdsAcc<RT>::T;
   const int K = a.K;
   const int R = a.R;
-  const uint32_t tps = static_cast<uint32_t>((a.nvec + TV - 1) / TV);
-  const uint32_t ntiles = tps * static_cast<uint32_t>(a.batch);
-  const uint32_t t = a.t_base + blockIdx.x;
-  if (t >= ntiles) return;  // block-uniform
-  const uint32_t stripe = t / tps, tile = t - stripe * tps;
-  // the stripe's pattern: its tables and its compare mask (all wave-uniform)
-  const uint32_t p = as_const(x.pat)[stripe];
-  a.verify_mask = as_const(x.vmask)[p];
   const uint64_t v0 = static_cast<uint64_t>(tile) * BS + threadIdx.x;
   cptr<const uint8_t*> in = as_const(a.in_tab) + static_cast<size_t>(stripe) * K;
   cptr<uint8_t*> out = as_const(a.out_tab) + static_cast<size_t>(stripe) * R;
@@ -69,7 +62,7 @@ void rs_apply_mixed(ApplyArgs a, MixedArgs x) {
       if (s < K) xr[s] = ld(s);
   }
   {
-    const uint4* src = reinterpret_cast<const uint4*>(a.ltabs + static_cast<size_t>(p) * x.tab_stride);
+    const uint4* src = reinterpret_cast<const uint4*>(a.ltabs + static_cast<size_t>(p) * tab_stride);
     uint4* dst = reinterpret_cast<uint4*>(smem);
     for (int j = threadIdx.x; j < K * 2 * W; j += BS) dst[j] = src[j];
   }
@@ -145,6 +138,48 @@ void rs_apply_mixed(ApplyArgs a, MixedArgs x) {
   if (bad) atomicOr(a.status + static_cast<size_t>(stripe) * a.status_stride, 1);
 }
 
+// An RT instance serves every R <= RT (rows >= R are computed and dropped). One tile of
+// P::TILE_VECS vectors per block; block b works on tile a.t_base + b in consecutive order.
+// (Blocks that work on 2..16 consecutive tiles of a stripe, to pay the table prologue once,
+// measured 6-15 % slower: DESIGN.md §5.8.)
+template <int RT, class P>
+__global__ __launch_bounds__(P::BS) __attribute__((amdgpu_waves_per_eu(P::WPE, lds_max_waves<RT>())))
+void rs_apply_mixed(ApplyArgs a, MixedArgs x) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  constexpr int TV = P::TILE_VECS;
+  const uint32_t tps = static_cast<uint32_t>((a.nvec + TV - 1) / TV);
+  const uint32_t ntiles = tps * static_cast<uint32_t>(a.batch);
+  const uint32_t t = a.t_base + blockIdx.x;
+  if (t >= ntiles) return;  // block-uniform
+  const uint32_t stripe = t / tps, tile = t - stripe * tps;
+  // the stripe's pattern: its tables and its compare mask (all wave-uniform)
+  const uint32_t p = as_const(x.pat)[stripe];
+  a.verify_mask = as_const(x.vmask)[p];
+  mixed_tile<RT, P>(a, smem, stripe, tile, p, x.tab_stride);
+}
+
+// Ragged launches: every stripe its own shard size. The tile map gives the
+// block its stripe with one scalar load; the stripe's first tile, its size and its pattern
+// are three more that depend on it alone, and the verify mask one that depends on the
+// pattern (all wave-uniform). From there the block is a mixed block of a plan whose S is
+// the stripe's. A stripe shorter than 16 bytes is one tile with no vector: its block stages
+// the tables, wave 0 computes the S % 16 tail from them, and every thread leaves.
+template <int RT, class P>
+__global__ __launch_bounds__(P::BS) __attribute__((amdgpu_waves_per_eu(P::WPE, lds_max_waves<RT>())))
+void rs_apply_ragged(ApplyArgs a, RaggedArgs x) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  static_assert(P::TILE_VECS == P::BS, "one vector per thread: the tile map counts 512-vector tiles");
+  const uint32_t t = a.t_base + blockIdx.x;
+  if (t >= x.ntiles) return;  // block-uniform
+  const uint32_t stripe = as_const(x.tile_stripe)[t];
+  const uint32_t tile = t - as_const(x.tile0)[stripe];
+  const uint32_t p = as_const(x.pat)[stripe];
+  a.S = as_const(x.size)[stripe];
+  a.nvec = a.S / 16;
+  a.verify_mask = as_const(x.vmask)[p];
+  mixed_tile<RT, P>(a, smem, stripe, tile, p, x.tab_stride);
+}
+
 // S < 16: one byte position per thread, 16 threads per stripe; the nibble tables are read
 // from the arena in global memory (a launch of batch * S bytes has nothing to amortise an
 // LDS prologue over). An RT instance (8 or 16: the entry width) serves every R <= RT.
@@ -188,14 +223,19 @@ const std::array<MixedFn, 3> kMixed = {&dev::rs_apply_mixed<4, dev::MixedPolicy<
                                        &dev::rs_apply_mixed<16, dev::MixedPolicy<16>>};
 const std::array<MixedFn, 2> kMixedBytes = {&dev::rs_apply_mixed_bytes<8>,
                                             &dev::rs_apply_mixed_bytes<16>};
+using RaggedFn = void (*)(ApplyArgs, RaggedArgs);
+const std::array<RaggedFn, 3> kRagged = {&dev::rs_apply_ragged<4, dev::MixedPolicy<4>>,
+                                         &dev::rs_apply_ragged<8, dev::MixedPolicy<8>>,
+                                         &dev::rs_apply_ragged<16, dev::MixedPolicy<16>>};
 static_assert(dev::MixedPolicy<4>::BS == 512 && dev::MixedPolicy<8>::BS == 512 &&
                   dev::MixedPolicy<16>::BS == 512 && dev::MixedPolicy<4>::TILE_VECS == 512 &&
                   dev::MixedPolicy<8>::TILE_VECS == 512 && dev::MixedPolicy<16>::TILE_VECS == 512,
               "one grid shape for every mixed instance");
 constexpr uint32_t kMixedBlock = 512, kMixedTileVecs = 512;
+static_assert(kRaggedLaunchTileVecs == kMixedTileVecs, "the tile map counts the instances' tiles");
 
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
-// per-device attribute (dispatch.hpp DeviceOnce)
+// per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one)
 DeviceOnce g_mixed_wide_lds;
 
 template <class... Args>
@@ -240,6 +280,41 @@ hipError_t launch_mixed(ApplyArgs a, const MixedArgs& x, hipStream_t stream, Lau
   if (ntiles > 0x7fffffffull) return hipErrorInvalidValue;
   const uint32_t grid = static_cast<uint32_t>(ntiles);
   // long grids in equal consecutive slices, as launch_apply cuts them
+  const uint32_t lim = launch_slice_tiles(a.K + a.R);
+  const uint32_t nsl = grid / 2 > lim ? (grid + lim - 1) / lim : 1;
+  const uint32_t per = (grid + nsl - 1) / nsl;
+  for (uint32_t t0 = 0; t0 < grid; t0 += per) {
+    a.t_base = t0;
+    dispatch(fn, dim3(std::min(per, grid - t0)), dim3(kMixedBlock), lds, stream, ev, t0 == 0,
+             t0 + per >= grid, a, x);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, bool any_tail, hipStream_t stream,
+                         LaunchEvents ev) {
+  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
+      !x.pat || !x.vmask || !x.size || !x.tile0 || !x.tile_stripe || !a.in_tab || !a.out_tab ||
+      !a.status || x.ntiles < static_cast<uint32_t>(a.batch) || x.ntiles > 0x7fffffffu)
+    return hipErrorInvalidValue;
+  a.t_base = 0;
+  a.S = a.nvec = 0;  // per stripe, read by the kernel
+  // the S % 16 tails: wave 0 of each stripe's first tile (rs_apply.hpp tail_lane); stripes
+  // with no tail leave lds_tail at once
+  a.tail_in_vec = any_tail ? 1u : 0u;
+  const size_t lds = dev::lds_bytes(a.K, a.R > 8 ? 16 : 8);
+  const RaggedFn fn = kRagged[a.R > 8 ? 2 : a.R > 4 ? 1 : 0];
+  if (lds > (64u << 10)) {
+    int device = -1;
+    if (hipGetDevice(&device) != hipSuccess) return hipErrorInvalidDevice;
+    g_mixed_wide_lds.run(device, 1, [fn] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+    });
+  }
+  const uint32_t grid = x.ntiles;
+  // long grids in equal consecutive slices, as launch_mixed cuts them; a slice boundary may
+  // fall inside a stripe (the tile map is indexed by the tile's number in the whole grid)
   const uint32_t lim = launch_slice_tiles(a.K + a.R);
   const uint32_t nsl = grid / 2 > lim ? (grid + lim - 1) / lim : 1;
   const uint32_t per = (grid + nsl - 1) / nsl;

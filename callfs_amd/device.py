@@ -140,6 +140,57 @@ class StripeBatch:
             t.random_(0, 256, generator=g)
 
 
+class RaggedBatch:
+    """Stripes of RS(k, m) with their own shard sizes (`sizes[b]` bytes for every shard of
+    stripe b), resident on `device` in one allocation, stripe after stripe and shard after
+    shard (the input of a ragged plan).
+
+    layout "aligned" (default): each shard starts at the next 256-B boundary.
+    layout "packed": shards back to back with no padding, so odd sizes give misaligned
+    addresses and adjacent shards touch."""
+
+    def __init__(self, k: int, m: int, sizes: Sequence[int], device: torch.device,
+                 layout: str = "aligned"):
+        if layout not in ("aligned", "packed"):
+            raise ValueError(f"layout {layout!r}")
+        self.k, self.m, self.n = k, m, k + m
+        self.sizes = [int(s) for s in sizes]
+        if not self.sizes or min(self.sizes) < 1:
+            raise ValueError("sizes: at least one stripe, every shard size >= 1")
+        self.batch = len(self.sizes)
+        self.layout = layout
+        self.device = torch.device(device)
+        self.offsets = []  # [batch][n] byte offset of each shard in buf
+        off = 0
+        for S in self.sizes:
+            row = []
+            for _ in range(self.n):
+                if layout == "aligned":
+                    off = (off + 255) // 256 * 256
+                row.append(off)
+                off += S
+            self.offsets.append(row)
+        self.nbytes = off
+        self.buf = _aligned_empty((off,), 256, self.device)
+
+    def shard(self, b: int, i: int) -> torch.Tensor:
+        o = self.offsets[b][i]
+        return self.buf[o:o + self.sizes[b]]
+
+    def pointers(self) -> list:
+        base = self.buf.data_ptr()
+        return [base + o for row in self.offsets for o in row]
+
+    def fill_random(self, seed: int) -> None:
+        g = torch.Generator(device=self.device)
+        g.manual_seed(seed)
+        self.buf.random_(0, 256, generator=g)
+
+    def gather_stripe(self, b: int) -> torch.Tensor:
+        """An [n][sizes[b]] copy of stripe b's shards."""
+        return torch.stack([self.shard(b, i) for i in range(self.n)])
+
+
 def _mask_rows(present):
     """The rows of a per-stripe presence mask (a batch x n sequence or array), or None
     when `present` is None or a flat sequence of flags."""
@@ -167,6 +218,7 @@ class Plan:
     present parity is re-verified (codec.go:55,59). A flat sequence of k+m flags is one
     mask for the whole batch; a batch x (k+m) sequence or array gives every stripe its own
     mask (a mixed plan, DESIGN.md §5.8: one launch repairs stripes with different erasures).
+    `Plan.ragged` builds a plan over stripes of different shard sizes.
     """
 
     def __init__(self, k: int, m: int, S: int, batch: int, pointers: Sequence[int],
@@ -203,6 +255,41 @@ class Plan:
     def for_batch(cls, sb: StripeBatch, present=None, context=None) -> "Plan":
         dev = sb.device.index if sb.device.index is not None else 0
         return cls(sb.k, sb.m, sb.S, sb.batch, sb.pointers(), present, dev, context)
+
+    @classmethod
+    def ragged(cls, k: int, m: int, sizes: Sequence[int], pointers: Sequence[int],
+               present=None, device: int = 0, context: Optional[N.Context] = None) -> "Plan":
+        """rs_plan_create_ragged: stripe b's shards are sizes[b] bytes; one
+        launch encodes, repairs and verifies stripes of different shard sizes. present: None
+        (every stripe an encode) or batch rows of k+m flags. The plan's S is None and its
+        sizes are kept; when all sizes are equal the library builds the mixed (or uniform)
+        plan of that size."""
+        n, batch = k + m, len(sizes)
+        if len(pointers) != batch * n:
+            raise ValueError("need batch*(k+m) shard pointers")
+        pres = None
+        if present is not None:
+            rows = _mask_rows(present)
+            if rows is None or len(rows) != batch or any(len(r) != n for r in rows):
+                raise ValueError("present: None, or batch rows of k+m flags")
+            pres = (ctypes.c_uint8 * (batch * n))(*[1 if p else 0 for r in rows for p in r])
+        self = cls.__new__(cls)
+        self.ctx = context or N.default_context()
+        self.k, self.m, self.S, self.batch, self.device = k, m, None, batch, device
+        self.sizes = [int(s) for s in sizes]
+        self.handle = None
+        ptrs = (ctypes.c_void_p * max(1, len(pointers)))(*pointers)
+        szs = (ctypes.c_size_t * max(1, batch))(*self.sizes)
+        h = ctypes.c_void_p()
+        N.check(N.lib.rs_plan_create_ragged(self.ctx.handle, device, k, m, batch, szs, pres, ptrs,
+                                            ctypes.byref(h)), "rs_plan_create_ragged")
+        self.handle = h
+        return self
+
+    @classmethod
+    def for_ragged(cls, rb: "RaggedBatch", present=None, context=None) -> "Plan":
+        dev = rb.device.index if rb.device.index is not None else 0
+        return cls.ragged(rb.k, rb.m, rb.sizes, rb.pointers(), present, dev, context)
 
     @property
     def bytes(self) -> int:
@@ -257,7 +344,7 @@ class Plan:
                    166: "realign64-x32", 192: "dma", 194: "dma-g2", 195: "dma-q8",
                    198: "dma-x32", 224: "tridb-g4", 225: "tridb-g8", 256: "bs", 257: "bs-g8",
                    258: "bs-g2", 259: "bs-q8", 260: "bs-q16", 261: "bs-x8", 262: "bs-x32",
-                   512: "mixed"}
+                   512: "mixed", 1024: "ragged"}
 
     def tune(self, reps: int = 5, stream: Optional[torch.cuda.Stream] = None) -> list:
         """rs_plan_tune: time each launch group in every tile order its kernel offers

@@ -273,6 +273,39 @@ int rs_plan_create_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int ba
 int rs_decode_dev_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                         const uint8_t* present, uint8_t* const* shards, void* stream);
 
+/* ---- ragged plans: every stripe its own shard size as well ------
+ * Objects have their own lengths, so a repair, scrub or re-encode batch has as many shard
+ * sizes as objects. sizes holds `batch` shard sizes: every shard of stripe b is sizes[b]
+ * bytes. present holds batch*(k+m) flags as for rs_plan_create_mixed, or NULL: every stripe
+ * is then an encode (data present, parity missing). shards as for rs_plan_create.
+ * Stripe b is computed exactly as a mixed plan of shard size sizes[b] with the mask
+ * present + b*(k+m) would compute it: its missing shards are written from its first k
+ * present shards, its remaining present shards are compared, and the corruption flags are
+ * per stripe. No byte at or beyond sizes[b] of any shard of stripe b is read or written
+ * (shards may touch each other; misaligned shards take unaligned 16-B accesses).
+ * Errors, each of which creates nothing: RS_E_ARG for batch < 1 or a NULL sizes / shards /
+ * out; RS_E_NO_DATA when any sizes[b] is 0; RS_E_TOO_FEW_SHARDS when any stripe has fewer
+ * than k present shards; the profile errors of rs_plan_create_mixed.
+ * When all sizes are equal the call returns exactly what rs_plan_create_mixed returns for
+ * that S (the uniform plan when the masks are equal too; same kernel forms, bit-sliced ones
+ * included). Otherwise the plan is a ragged plan: one launch per launch group over a tile
+ * map of the whole batch, no bit-sliced kernel, no hiprtc compile, no tune-table entry, one
+ * tile order. It works with rs_plan_launch, _launch_timed (which only enqueue: no
+ * allocation, no sync; graph-capturable), _status, _stripe_status, _groups and _destroy as
+ * any plan does. For a ragged plan
+ *   rs_plan_bytes   returns (k+m) * the sum of sizes[b];
+ *   rs_plan_forms   reports RS_ORDER_RAGGED + RS_ORDER_CONSECUTIVE;
+ *   rs_plan_tune    returns RS_OK, times nothing and fills orders with -1;
+ *   rs_plan_set_orders accepts only -1 entries (RS_E_ARG for anything else);
+ *   rs_plan_launch_ceiling / _ceiling_timed return RS_E_ARG.
+ * rs_decode_dev_ragged is the one-shot form (build + launch + status + free; synchronous on
+ * `stream`); it returns RS_E_CORRUPT when any stripe's compared shards mismatch. */
+#define RS_ORDER_RAGGED 1024
+int rs_plan_create_ragged(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                          const uint8_t* present, uint8_t* const* shards, rs_plan** out);
+int rs_decode_dev_ragged(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                         const uint8_t* present, uint8_t* const* shards, void* stream);
+
 /* ---- ShardChecksum on device-resident shards (codec.go:81-84; §8(f) of SURVEY.md) ----
  * SHA-256 of `count` messages already in HBM, one digest per message written to
  * `digests` (device memory, 32*count bytes, FIPS 180-4 byte order — hex-encode it for

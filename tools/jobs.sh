@@ -423,6 +423,15 @@ echo "write ok"
 find "$OUT" -name "*.csv" | head -20
 }
 
+# Ragged plans against a mixed plan at the mean size and against one mixed plan per distinct
+# size (tools/ragged_bench.py): RS(10,4) x 256 stripes of 64 KiB..4 MiB and
+# RS(16,4) x 4,096 stripes of 1..16 KiB. One JSON line per workload on stdout (the lines kept
+# in profiles/r08/ragged/ragged_bench.jsonl). Usage: bash tools/jobs.sh ragged_bench [ragged_bench.py args]
+job_ragged_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+timeout -k 10 400 python3 -u tools/ragged_bench.py "$@" || exit $?
+}
+
 # configs[1]/[2] shape in the layouts upstream produces: bench.py at S = 6,710,887 with the
 # io.ReadAll Split layout (decode into fresh buffers, as Reconstruct allocates them, and in
 # place) and the planar layout; plus the bench shape. Usage: bash tools/jobs.sh readall_bench <tag>
