@@ -414,7 +414,7 @@ std::shared_ptr<Kernel> kernel_for(int K, int R, const uint8_t* coef) {
   std::lock_guard<std::mutex> g(*mu);
   auto it = map->find(key);
   if (it != map->end()) return it->second;
-  // bounded like the coefficient-table cache (rs_capi.cpp TableCache): past kCap entries the
+  // bounded like the coefficient-table cache (rs_context.cpp TableCache): past kCap entries the
   // kernels no table set or compile holds any more are dropped (their modules unloaded)
   constexpr size_t kCap = 1024;
   if (map->size() >= kCap)

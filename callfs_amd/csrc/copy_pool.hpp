@@ -1,4 +1,4 @@
-// Parallel memcpy pool for the host-memory path's pinned staging (rs_capi.cpp).
+// Parallel memcpy pool for the host-memory path's pinned staging (rs_host.cpp).
 // Header-only so tests/native/host_test.cpp can run it under ASan/TSan on the CPU.
 #pragma once
 

@@ -1,7 +1,8 @@
 // Host-memory call placement over the devices of an rs_ctx: which devices a mask
 // selects, on which device a call runs, and how one large object's columns are split
 // over devices. Plain C++ with no HIP dependence, so tests/native/host_test.cpp checks
-// it against mocked device lists on the CPU; rs_capi.cpp is the only product user.
+// it against mocked device lists on the CPU; rs_context.cpp and rs_host.cpp
+// are the product users (DeviceOnce: the kernel files).
 //
 // Every output byte depends only on the same column of the inputs (codec.go:36 ->
 // upstream Encode), so column ranges of one object are independent: the in-process form

@@ -15,6 +15,7 @@
 #include "bitslice.hpp"
 #include "bitslice_rule.hpp"
 #include "dispatch.hpp"
+#include "launch_util.hpp"
 #include "rs_apply.hpp"
 #include "tile_order.hpp"
 #include "tune_table.hpp"
@@ -185,27 +186,9 @@ template <class Launch>
 void launch_sliced(uint32_t grid, int streams, ApplyArgs& a, Launch&& launch) {
   const uint32_t all_rows = a.R >= 32 ? ~0u : (1u << a.R) - 1;
   const bool read_only = (a.verify_mask & all_rows) == all_rows;
-  const uint32_t lim = read_only ? grid : slice_tiles(streams);
-  const uint32_t nsl = grid / 2 > lim ? (grid + lim - 1) / lim : 1;
-  const uint32_t per = (grid + nsl - 1) / nsl;
-  for (uint32_t t0 = 0; t0 < grid; t0 += per) {
-    a.t_base = t0;
-    launch(std::min(per, grid - t0), t0 == 0, t0 + per >= grid);
-  }
-  a.t_base = 0;
+  launch_slices(grid, read_only ? grid : slice_tiles(streams), a, launch);
 }
 
-// One dispatch of kernel fn; with events, the first dispatch of a launch records ev.start
-// at its start and the last records ev.stop at its end (hipExtLaunchKernel).
-template <class... Args>
-void dispatch(void (*fn)(Args...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
-              const LaunchEvents& ev, bool first, bool last, Args... args) {
-  if (ev.start || ev.stop)
-    hipExtLaunchKernelGGL(fn, grid, block, static_cast<uint32_t>(lds), stream,
-                          first ? ev.start : nullptr, last ? ev.stop : nullptr, 0, args...);
-  else
-    hipLaunchKernelGGL(fn, grid, block, lds, stream, args...);
-}
 constexpr int kLdsMinRows = 5;
 constexpr int kLdsMinK = 4;
 constexpr int kPermMaxRows = 4;  // v_perm kernel: k <= 3 and R <= 4 (takes_lds sends the rest to LDS)

@@ -14,6 +14,7 @@
 #include <hip/hip_ext.h>
 
 #include "dispatch.hpp"
+#include "launch_util.hpp"
 #include "rs_apply.hpp"
 
 namespace callfs {
@@ -238,14 +239,25 @@ static_assert(kRaggedLaunchTileVecs == kMixedTileVecs, "the tile map counts the 
 // per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one)
 DeviceOnce g_mixed_wide_lds;
 
-template <class... Args>
-void dispatch(void (*fn)(Args...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
-              const LaunchEvents& ev, bool first, bool last, Args... args) {
-  if (ev.start || ev.stop)
-    hipExtLaunchKernelGGL(fn, grid, block, static_cast<uint32_t>(lds), stream,
-                          first ? ev.start : nullptr, last ? ev.stop : nullptr, 0, args...);
-  else
-    hipLaunchKernelGGL(fn, grid, block, lds, stream, args...);
+// The vector launch both kinds share: the dynamic-LDS opt-in (`once_key`: 0 the mixed
+// instance, 1 the ragged one), then `grid` tiles in equal consecutive slices, as launch_apply
+// cuts them. A slice boundary may fall inside a stripe (tiles are numbered over the whole grid).
+template <class X>
+hipError_t launch_tiles(void (*fn)(ApplyArgs, X), int once_key, uint32_t grid, ApplyArgs& a,
+                        const X& x, hipStream_t stream, const LaunchEvents& ev) {
+  const size_t lds = dev::lds_bytes(a.K, a.R > 8 ? 16 : 8);
+  if (lds > (64u << 10)) {
+    int device = -1;
+    if (hipGetDevice(&device) != hipSuccess) return hipErrorInvalidDevice;
+    g_mixed_wide_lds.run(device, once_key, [fn] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+    });
+  }
+  launch_slices(grid, launch_slice_tiles(a.K + a.R), a, [&](uint32_t blocks, bool first, bool last) {
+    dispatch(fn, dim3(blocks), dim3(kMixedBlock), lds, stream, ev, first, last, a, x);
+  });
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -265,30 +277,11 @@ hipError_t launch_mixed(ApplyArgs a, const MixedArgs& x, hipStream_t stream, Lau
   }
   // the S % 16 tail: wave 0 of each stripe's first tile (rs_apply.hpp tail_lane)
   a.tail_in_vec = a.nvec * 16 < a.S ? 1u : 0u;
-  const size_t lds = dev::lds_bytes(a.K, a.R > 8 ? 16 : 8);
-  const MixedFn fn = kMixed[a.R > 8 ? 2 : a.R > 4 ? 1 : 0];
-  if (lds > (64u << 10)) {
-    int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) return hipErrorInvalidDevice;
-    g_mixed_wide_lds.run(device, 0, [fn] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-    });
-  }
   const uint64_t tps = (a.nvec + kMixedTileVecs - 1) / kMixedTileVecs;
   const uint64_t ntiles = tps * static_cast<uint64_t>(a.batch);
   if (ntiles > 0x7fffffffull) return hipErrorInvalidValue;
-  const uint32_t grid = static_cast<uint32_t>(ntiles);
-  // long grids in equal consecutive slices, as launch_apply cuts them
-  const uint32_t lim = launch_slice_tiles(a.K + a.R);
-  const uint32_t nsl = grid / 2 > lim ? (grid + lim - 1) / lim : 1;
-  const uint32_t per = (grid + nsl - 1) / nsl;
-  for (uint32_t t0 = 0; t0 < grid; t0 += per) {
-    a.t_base = t0;
-    dispatch(fn, dim3(std::min(per, grid - t0)), dim3(kMixedBlock), lds, stream, ev, t0 == 0,
-             t0 + per >= grid, a, x);
-  }
-  return hipGetLastError();
+  return launch_tiles(kMixed[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 0, static_cast<uint32_t>(ntiles), a, x,
+                      stream, ev);
 }
 
 hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, bool any_tail, hipStream_t stream,
@@ -302,28 +295,7 @@ hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, bool any_tail, hipStr
   // the S % 16 tails: wave 0 of each stripe's first tile (rs_apply.hpp tail_lane); stripes
   // with no tail leave lds_tail at once
   a.tail_in_vec = any_tail ? 1u : 0u;
-  const size_t lds = dev::lds_bytes(a.K, a.R > 8 ? 16 : 8);
-  const RaggedFn fn = kRagged[a.R > 8 ? 2 : a.R > 4 ? 1 : 0];
-  if (lds > (64u << 10)) {
-    int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) return hipErrorInvalidDevice;
-    g_mixed_wide_lds.run(device, 1, [fn] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-    });
-  }
-  const uint32_t grid = x.ntiles;
-  // long grids in equal consecutive slices, as launch_mixed cuts them; a slice boundary may
-  // fall inside a stripe (the tile map is indexed by the tile's number in the whole grid)
-  const uint32_t lim = launch_slice_tiles(a.K + a.R);
-  const uint32_t nsl = grid / 2 > lim ? (grid + lim - 1) / lim : 1;
-  const uint32_t per = (grid + nsl - 1) / nsl;
-  for (uint32_t t0 = 0; t0 < grid; t0 += per) {
-    a.t_base = t0;
-    dispatch(fn, dim3(std::min(per, grid - t0)), dim3(kMixedBlock), lds, stream, ev, t0 == 0,
-             t0 + per >= grid, a, x);
-  }
-  return hipGetLastError();
+  return launch_tiles(kRagged[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 1, x.ntiles, a, x, stream, ev);
 }
 
 }  // namespace callfs

@@ -13,6 +13,9 @@
 //     once per (device, R), before the first such launch on each device
 //  9. the tune table (tune_table.hpp): shape keys, lookup and rule fallback, replacement,
 //     persistence through a file, and concurrent recording and lookups
+// 10. the host path's HIP-free parts (host_path.hpp): chunk geometry, the rs_host_alloc pool
+//     and registry (also from eight threads), the 256-byte packer, join spans, index runs,
+//     check_lens' error precedence and the batch grouping
 //  8. the bit-sliced kernels' generator (bitslice_gen.hpp): the bit transpose against its
 //     definition, each coefficient's GF(2) matrix against the field, the XOR network of
 //     random coefficient blocks (zeros included) against a scalar GF multiply, the rule
@@ -32,6 +35,7 @@
 #include "copy_pool.hpp"
 #include "dispatch.hpp"
 #include "gf256.hpp"
+#include "host_path.hpp"
 #include "tile_order.hpp"
 #include "tune_table.hpp"
 
@@ -670,6 +674,169 @@ int main() {
     for (auto& x : ths) x.join();
     CHECK(t.size() > 2);
     std::remove(path);
+  }
+
+  // 10. the host path's HIP-free parts
+  {
+    // geometry. RS(4,2), S = 40,003, 64 KiB chunks: five column chunks of 8,192 on 3 slots
+    ChunkGeometry g = chunk_geometry(40003, 6, 1, 65536, 3);
+    CHECK(g.cw == 8192 && g.spc == 1 && g.cpitch == 8192 && g.spitch == 6 * 8192);
+    CHECK(g.ncol == 5 && g.nblk == 1 && g.nchunks() == 5 && g.nslots == 3 && g.coalesce);
+    CHECK(40003 - (g.ncol - 1) * g.cw == 7235);
+    // 40 stripes of 1,000: shards pitched to 1,024, ten stripes per chunk, four chunks
+    g = chunk_geometry(1000, 6, 40, 65536, 3);
+    CHECK(g.cw == 1000 && g.spc == 10 && g.cpitch == 1024 && g.spitch == 6144);
+    CHECK(g.ncol == 1 && g.nblk == 4 && g.nslots == 3 && g.coalesce);
+    // a shard larger than a chunk whose cb / n is below 4,096: the 4 KiB floor
+    g = chunk_geometry(100000, 20, 1, 65536, 3);
+    CHECK(g.cw == 4096 && g.spc == 1 && g.ncol == 25 && g.nslots == 3);
+    // batch = 1 with S * n equal to the chunk size: one whole-shard chunk, one slot
+    g = chunk_geometry(16384, 4, 1, 65536, 3);
+    CHECK(g.cw == 16384 && g.spc == 1 && g.ncol == 1 && g.nblk == 1 && g.nslots == 1);
+    // fewer chunks than slots; more stripes than a chunk holds in the last block
+    g = chunk_geometry(1000, 6, 15, 65536, 6);
+    CHECK(g.spc == 10 && g.nblk == 2 && g.nslots == 2);
+    // per-run copies once a stripe's staging passes 4 MiB
+    CHECK(!chunk_geometry(1 << 20, 6, 5, 16u << 20, 3).coalesce);
+    CHECK(chunk_geometry(1 << 20, 6, 5, 16u << 20, 3).spc == 2);
+    // a slot's staging (spc * spitch) covers every chunk, and the chunks cover the call
+    bool ok = true;
+    for (size_t S = 1; S <= 5000; ++S)
+      for (int batch : {1, 7, 40}) {
+        const ChunkGeometry q = chunk_geometry(S, 6, batch, 65536, 3);
+        const size_t w = std::min(q.cw, S);
+        ok &= q.cpitch >= w && q.cpitch % kPitchAlign == 0 && q.spitch == q.cpitch * 6;
+        ok &= q.spc >= 1 && q.spc <= batch && q.ncol * q.cw >= S && (q.ncol - 1) * q.cw < S;
+        ok &= q.nblk * q.spc >= static_cast<size_t>(batch) && (q.nblk - 1) * q.spc < static_cast<size_t>(batch);
+        ok &= static_cast<size_t>(q.spc) * q.spitch >= static_cast<size_t>(q.spc - 1) * q.spitch + 5 * q.cpitch + w;
+        ok &= q.spc == 1 || static_cast<size_t>(q.spc) * q.spitch <= 65536;
+        ok &= q.nslots >= 1 && q.nslots <= 3 && static_cast<size_t>(q.nslots) <= q.nchunks();
+      }
+    CHECK(ok);
+
+    // the packer: 256-byte aligned pieces, the total a multiple of 256
+    Packer pk;
+    CHECK(pk.take(1) == 0 && pk.take(256) == 256 && pk.take(0) == 512 && pk.take(257) == 512);
+    CHECK(pk.off == 1024);
+
+    // index runs, join spans
+    const auto runs = index_runs({5, 0, 1, 3, 2, 9});
+    CHECK(runs.size() == 3 && runs[0] == std::make_pair(0, 3) && runs[1] == std::make_pair(5, 5) &&
+          runs[2] == std::make_pair(9, 9));
+    CHECK(index_runs({}).empty());
+    uint8_t obj[1];
+    const Join j{obj, 250, 100, 4};
+    CHECK(join_span(nullptr, 0, 0, 10).first == nullptr);
+    CHECK(join_span(&j, 4, 0, 10).first == nullptr);  // a parity shard
+    CHECK(join_span(&j, 1, 20, 50) == std::make_pair(obj + 120, size_t{50}));
+    CHECK(join_span(&j, 2, 20, 50) == std::make_pair(obj + 220, size_t{30}));  // trimmed at len
+    CHECK(join_span(&j, 2, 50, 50).first == nullptr && join_span(&j, 3, 0, 100).first == nullptr);
+
+    // check_lens: no data before a size mismatch, nil shards only where allowed
+    size_t S = 0;
+    int np = 0;
+    const size_t none[4] = {0, 0, 0, 0}, odd[4] = {0, 8, 9, 8}, holes[4] = {0, 8, 0, 8}, all[4] = {8, 8, 8, 8};
+    CHECK(check_lens(4, none, true, &S, &np) == RS_E_NO_DATA);
+    CHECK(check_lens(4, none, false, &S, &np) == RS_E_NO_DATA);
+    CHECK(check_lens(4, odd, true, &S, &np) == RS_E_SHARD_SIZE);
+    CHECK(check_lens(4, holes, false, &S, &np) == RS_E_SHARD_SIZE);
+    CHECK(check_lens(4, holes, true, &S, &np) == RS_OK && S == 8 && np == 2);
+    CHECK(check_lens(4, all, false, &S, &np) == RS_OK && S == 8 && np == 4);
+
+    // batch groups: one group per (S, presence), stripes in call order
+    BatchGroups bg;
+    const uint8_t pa[3] = {1, 1, 0}, pb[3] = {1, 0, 1};
+    bg.add(100, pa, 3, 0);
+    bg.add(100, pb, 3, 1);
+    bg.add(101, pa, 3, 2);
+    bg.add(100, pa, 3, 3);
+    CHECK(bg.by_key.size() == 3);
+    for (const auto& kv : bg.by_key)
+      if (kv.second.size() == 2) {
+        CHECK(BatchGroups::shard_size(kv.first) == 100 && kv.second[0] == 0 && kv.second[1] == 3);
+        CHECK(std::memcmp(BatchGroups::present(kv.first), pa, 3) == 0);
+      }
+
+    // the registry: ranges by fake addresses (never dereferenced)
+    auto fake = [](uintptr_t a) { return reinterpret_cast<void*>(a); };
+    PinnedRegistry reg;
+    CHECK(reg.empty() && !reg.contains(fake(0x1000), 1));
+    reg.add(fake(0x10000), 0x1000);
+    reg.add(fake(0x11000), 0x1000);  // adjacent
+    CHECK(!reg.empty() && reg.size_of(fake(0x10000)) == 0x1000 && reg.size_of(fake(0x10800)) == 0);
+    CHECK(reg.contains(fake(0x10000), 0x1000));      // the whole range, both edges
+    CHECK(reg.contains(fake(0x10fff), 1) && reg.contains(fake(0x10000), 1));
+    CHECK(!reg.contains(fake(0x10fff), 2));  // across two adjacent ranges
+    CHECK(!reg.contains(fake(0x10800), 0x1000));
+    CHECK(!reg.contains(fake(0x12000), 1));           // just past the end
+    CHECK(!reg.contains(fake(0xffff), 1) && !reg.contains(fake(0xffff), 2));  // below the first
+    CHECK(reg.all().size() == 2 && reg.remove(fake(0x10000)) && !reg.remove(fake(0x10000)));
+    CHECK(!reg.contains(fake(0x10000), 1) && reg.contains(fake(0x11000), 0x1000));
+
+    // the pool: granules, the quarter-waste refusal, the cap
+    constexpr size_t G = HostPool::kGranule;
+    CHECK(HostPool::granule(1) == G && HostPool::granule(G) == G && HostPool::granule(G + 1) == 2 * G);
+    {
+      HostPool pool(64 * G);
+      CHECK(pool.take(4096).p == nullptr);
+      // a 4 KiB request was allocated as one granule: it serves a 1 MiB request
+      CHECK(pool.put(fake(0xA000), HostPool::granule(4096)).empty());
+      CHECK(pool.idle_bytes() == G);
+      const HostPool::Buf b = pool.take(1u << 20);
+      CHECK(b.p == fake(0xA000) && b.cap == G && pool.idle_bytes() == 0);
+      // more than a quarter wasted: refused; exactly a quarter: taken
+      CHECK(pool.put(fake(0xB000), 8 * G).empty());
+      CHECK(pool.take(5 * G).p == nullptr && pool.idle_bytes() == 8 * G);
+      CHECK(pool.take(6 * G).p == fake(0xB000));
+      // the smallest that fits
+      (void)pool.put(fake(0xC000), 8 * G);
+      (void)pool.put(fake(0xD000), 7 * G);
+      CHECK(pool.take(6 * G + 1).p == fake(0xD000) && pool.take(7 * G).p == fake(0xC000));
+      CHECK(pool.drain().empty());
+    }
+    {
+      // over the cap the largest parked buffer goes, not the newest; one larger than the cap
+      // never parks
+      HostPool pool(10 * G);
+      CHECK(pool.put(fake(0x1), 5 * G).empty() && pool.put(fake(0x2), 2 * G).empty());
+      CHECK(pool.put(fake(0x3), 3 * G).empty() && pool.idle_bytes() == 10 * G);  // at the cap
+      const std::vector<void*> drop = pool.put(fake(0x4), 4 * G);  // 14 G parked: the 5 G one leaves
+      CHECK(drop.size() == 1 && drop[0] == fake(0x1) && pool.idle_bytes() == 9 * G);
+      const std::vector<void*> big = pool.put(fake(0x5), 11 * G);
+      CHECK(big.size() == 1 && big[0] == fake(0x5) && pool.idle_bytes() == 9 * G);
+      CHECK(pool.drain().size() == 3 && pool.idle_bytes() == 0);
+      HostPool off(0);  // a cap of 0 parks nothing
+      const std::vector<void*> d0 = off.put(fake(0x6), G);
+      CHECK(d0.size() == 1 && d0[0] == fake(0x6) && off.idle_bytes() == 0 && off.take(1).p == nullptr);
+    }
+    {
+      // eight threads: alloc-like (take or make, add) and free-like (remove, put) cycles on
+      // fake pointers, with lookups of their own and of other threads' ranges
+      PinnedRegistry r;
+      HostPool pool(6 * G);
+      std::atomic<uintptr_t> next{1};
+      std::atomic<int> bad{0};
+      std::vector<std::thread> ths;
+      for (int w = 0; w < 8; ++w)
+        ths.emplace_back([&, w] {
+          for (int i = 0; i < 300; ++i) {
+            const size_t want = static_cast<size_t>(1 + (i + w) % 3) * G;
+            HostPool::Buf b = pool.take(want);
+            if (!b.p) b = {fake(next.fetch_add(1) << 32), HostPool::granule(want)};
+            if (b.cap < want) ++bad;
+            r.add(b.p, b.cap);
+            if (!r.contains(b.p, b.cap) || r.contains(b.p, b.cap + 1)) ++bad;
+            (void)r.contains(fake(uintptr_t{1} << 32), G);
+            (void)r.empty();
+            const size_t cap = r.size_of(b.p);
+            if (cap != b.cap || !r.remove(b.p)) ++bad;
+            (void)pool.put(b.p, cap);
+            if (pool.idle_bytes() > 6 * G) ++bad;
+          }
+        });
+      for (auto& x : ths) x.join();
+      CHECK(bad.load() == 0 && r.empty() && pool.idle_bytes() <= 6 * G);
+    }
   }
 
   std::printf(fails ? "FAILED %d\n" : "host_test ok\n", fails);

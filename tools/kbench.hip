@@ -322,7 +322,7 @@ int main(int argc, char** argv) {
   a.K = k;
   a.R = m;
   a.batch = B;
-  {  // stripe 0's shard addresses, as rs_capi.cpp fill_meta computes it
+  {  // stripe 0's shard addresses, as rs_internal.hpp fill_meta computes it
     std::vector<const void*> s0(in.begin(), in.begin() + k);
     s0.insert(s0.end(), out.begin(), out.begin() + m);
     a.addr_tz = shard_addr_tz(s0.data(), k + m);
