@@ -6,6 +6,8 @@
 #include <vector>
 #include <cstdint>
 
+#include "order_code.hpp"
+
 // 1: also build the measurement-only kernel forms (the 6-bit triple lookups, the 64-vector
 // and double-buffered realigning forms, the no-lookup and aligned-window ceilings) and honour
 // the A/B environment toggles (CALLFS_RS_WIX, _TRIDB, _REALIGN, _TAIL_LAST_TPS). The
@@ -115,35 +117,7 @@ inline int shard_addr_tz(const void* const* p, int count) {
 // offsets (upstream Split layout of a contiguous object) that ran 4.7x the byte kernel
 // (DESIGN.md §5). bytes_only forces the byte kernel over all of [0, S) (kbench A/B).
 // Returns hipSuccess or the launch error.
-// order_candidates / launch_apply code for the realigning kernel of misaligned launches
-// (tile orders are TileOrder values 0..4, which on a misaligned launch select the plain
-// kernel with unaligned accesses)
-// (kOrderRealign + the TileOrder it runs in: consecutive, X8 or X32)
-constexpr int kOrderRealign = 32;
-// (kOrderWix + a TileOrder: the R <= 4 LDS kernel with 6-bit lookups over shard triples,
-// rs_apply.hpp Policy::WIX; aligned launches without Verify rows, K >= 3)
-constexpr int kOrderWix = 64;
-// (kOrderTri + consecutive / G2 / X32 / Q8 / Q16: the triple loop with nibble lookups)
-constexpr int kOrderTri = 96;
-// (kOrderRealignTri + consecutive / X8 / X32: the realigning kernel with its aligned loads
-// issued in triples)
-constexpr int kOrderRealignTri = 128;
-// (kOrderRealign64 + consecutive / X8 / X32: misaligned inputs with 16-B-aligned outputs --
-// upstream Split of an io.ReadAll body, whose parity reedsolomon allocates aligned -- in
-// 64-vector waves: aligned loads realigned in registers, lane 63's neighbour vector from
-// one extra single-lane load, stores unshifted in 1 KiB wave windows; rs_apply.hpp
-// REALIGN 5)
-constexpr int kOrderRealign64 = 160;
-// (kOrderDma + consecutive / G2 / Q8 / X32: aligned R <= 8 launches with their input vectors
-// staged through an LDS-DMA ring, rs_apply.hpp Policy::DMA; A/B build)
-constexpr int kOrderDma = 192;
-// (kOrderTriDbG + 0 / 1: R <= 4, K >= 6 double-buffered triples with the tiles of 4 / 8 stripes
-// interleaved (G4 / G8); A/B build)
-constexpr int kOrderTriDbG = 224;
-// (kOrderBitslice + any TileOrder: the launch group's bit-sliced kernel, ApplyArgs::bs,
-// DESIGN.md §5.7; every launch group gets one: the rule takes it for wide groups and
-// rs_plan_tune times it for every group)
-constexpr int kOrderBitslice = 256;
+// `order` arguments below are order codes (order_code.hpp: the kOrder* bands and their decoder).
 constexpr int kBitsliceMinRows = 1;
 
 // `order` >= 0 (a TileOrder) replaces the measured rule for this launch where the

@@ -465,7 +465,7 @@ int rs_plan_tune(rs_plan* plan, void* stream, int reps, int* orders, int max_gro
     // the bit-sliced orders only when the group's kernel compiles and loads here: a hiprtc
     // that fails on some box leaves the tuner (and the bench) on the nibble-table forms
     const Group& grp = t.groups[gi];
-    const auto bs_order = [](int o) { return o >= kOrderBitslice; };
+    const auto bs_order = [](int o) { return decode_order(o).family == Family::kBitslice; };
     if (std::any_of(cand.begin(), cand.end(), bs_order) &&
         (!grp.bsk || !grp.bsk->function(plan->device, /*wait=*/true)))
       cand.erase(std::remove_if(cand.begin(), cand.end(), bs_order), cand.end());

@@ -36,6 +36,7 @@
 #include "dispatch.hpp"
 #include "gf256.hpp"
 #include "host_path.hpp"
+#include "order_code.hpp"
 #include "tile_order.hpp"
 #include "tune_table.hpp"
 
@@ -837,6 +838,37 @@ int main() {
       for (auto& x : ths) x.join();
       CHECK(bad.load() == 0 && r.empty() && pool.idle_bytes() <= 6 * G);
     }
+  }
+
+  // Order codes (order_code.hpp): every code in [-1, 1100] decodes to its family's band and
+  // member; the valid ones are exactly -1, seven members per family (two for the G4 / G8
+  // triples) and nothing past kOrderBitslice + kTileOrders; encode inverts decode_order.
+  {
+    const int bases[] = {0, kOrderRealign, kOrderWix, kOrderTri, kOrderRealignTri, kOrderRealign64,
+                         kOrderDma, kOrderTriDbG, kOrderBitslice};
+    int valid = 0;
+    for (int code = -1; code <= 1100; ++code) {
+      const Form f = decode_order(code);
+      bool want = code == -1;
+      for (int b = 0; b < 9; ++b)
+        want |= code >= bases[b] && code < bases[b] + (bases[b] == kOrderTriDbG ? 2 : kTileOrders);
+      CHECK(f.valid() == want);
+      valid += f.valid();
+      CHECK(encode(f) == (want ? code : -1));
+      if (code < 0) CHECK(f.family == Family::kRule && !f.has_order());
+      if (code >= 0 && code < kOrderBitslice)
+        CHECK(static_cast<int>(f.family) == 1 + code / 32 && (f.member == code % 32 || f.member == -1));
+      if (code >= kOrderBitslice) CHECK(f.family == Family::kBitslice);
+      if (want && code >= 0) {
+        CHECK(decode_order(encode(f)) == f && f.member == code - bases[static_cast<int>(f.family) - 1]);
+        CHECK(f.family == Family::kTriDbG ? f.order() == TileOrder::kGroup8
+                                           : static_cast<int>(f.order()) == f.member);
+      }
+    }
+    CHECK(valid == 1 + 8 * kTileOrders + 2);
+    CHECK(encode(form_of(Family::kTri, TileOrder::kXcd32)) == kOrderTri + 6);
+    CHECK(!decode_order(512).valid() && !decode_order(1024).valid());  // mixed / ragged plans' forms
+    CHECK(decode_order(-7).family == Family::kRule && encode(Form{Family::kDma, -1}) == -1);
   }
 
   std::printf(fails ? "FAILED %d\n" : "host_test ok\n", fails);
