@@ -11,6 +11,8 @@
 //   launch_record --full I       the whole record of case I
 //   launch_record --unreached    registered kernels the sweep never dispatched
 //   launch_record --time         ns per launch_apply (selection cost; recording off)
+//   launch_record --wide         the kernel each wide-ring launch (R 9..16, consecutive and Q8,
+//                                pinned and by the rule) dispatches with the bit-sliced path off
 //
 // The environment toggles of rs_kernels.hip are read once per process, so the test runs one
 // process per setting.
@@ -259,6 +261,44 @@ int time_selection() {
   return 0;
 }
 
+// The device symbol of the one vector kernel launch_apply dispatches for `a` in order code `o`
+// with the bit-sliced kernels off ("?" when it dispatched none or more than one).
+std::string dispatched(const ApplyArgs& a, int o) {
+  fake::bs_mode = 0;
+  fake::bs_ready = 0;
+  fake::log.clear();
+  tune_table().reset(nullptr);
+  if (launch_apply(a, nullptr, false, o, {}) != hipSuccess) return "?";
+  std::string name;
+  size_t at = 0;
+  while (at < fake::log.size()) {
+    const size_t end = std::min(fake::log.find('\n', at), fake::log.size());
+    const std::string line = fake::log.substr(at, end - at);
+    at = end + 1;
+    if (line.rfind("  attr ", 0) == 0 || line.rfind("  ", 0) != 0) continue;
+    const std::string sym = line.substr(2, line.find(' ', 2) - 2);
+    if (!name.empty() && sym != name) return "?";  // (a sliced grid repeats one symbol)
+    name = sym;
+  }
+  return name.empty() ? "?" : name;
+}
+
+// The wide ring's instances (R 9..16 in consecutive order and in Q8), pinned and by the rule
+// on both sides of its 256-tiles-per-stripe threshold: one line per launch with the symbol.
+int wide_instances() {
+  const struct { const char* name; int code; } kPins[] = {{"consecutive", 0}, {"q8", 3}};
+  for (int R = 9; R <= kMaxRowsPerLaunch; ++R)
+    for (const auto& pin : kPins)
+      std::printf("wide R=%d order=%s %s\n", R, pin.name,
+                  dispatched(shape(11, R, 3 * kTile + 16, 2), pin.code).c_str());
+  for (int R = 9; R <= kMaxRowsPerLaunch; ++R)
+    for (uint64_t tiles : {256, 255})
+      std::printf("rule R=%d tiles=%llu %s\n", R, static_cast<unsigned long long>(tiles),
+                  dispatched(shape(11, R, tiles * kTile, 2), -1).c_str());
+  std::printf("launch_record ok\n");
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -266,6 +306,7 @@ int main(int argc, char** argv) {
   bool unreached = false;
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--time")) return time_selection();
+    if (!std::strcmp(argv[i], "--wide")) return wide_instances();
     if (!std::strcmp(argv[i], "--stride") && i + 1 < argc) stride = std::max(1, std::atoi(argv[++i]));
     if (!std::strcmp(argv[i], "--full") && i + 1 < argc) full = std::atoi(argv[++i]);
     if (!std::strcmp(argv[i], "--unreached")) unreached = true;

@@ -95,6 +95,34 @@ def test_dispatch_matches_record(tmp_path, flavour):
                             % (flavour, section_name(env), w, g, full[-20000:]))
 
 
+def test_wide_ring_launches_reach_sixteen_kernels(tmp_path):
+    """The wide ring of rs_apply_lds has 16 instances (R 9..16 in consecutive order and in Q8),
+    and ring_kernel() falls back silently to the consecutive one where a table entry is null: a
+    byte-exact GPU test cannot tell which instance it ran. With the bit-sliced path off, the 16
+    (R, order) pins must dispatch 16 different registered kernels, and the rule the Q8 one of
+    its R from 256 tiles per stripe and the consecutive one below
+    (tests/test_gpu_nibble_fallback.py runs the same launches on the GPU)."""
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc not available")
+    exe = str(tmp_path / "launch_record_product")
+    build(CSRC, "product", exe, str(tmp_path))
+    pinned, rule = {}, {}
+    for line in run(exe, {}, ["--wide"]):
+        w = line.split()
+        if w[0] == "wide":
+            pinned[int(w[1][2:]), w[2][len("order="):]] = w[3]
+        else:
+            assert w[0] == "rule", line
+            rule[int(w[1][2:]), int(w[2][len("tiles="):])] = w[3]
+    assert sorted(pinned) == [(R, o) for R in range(9, 17) for o in ("consecutive", "q8")]
+    assert all("rs_apply_lds" in s for s in pinned.values()), pinned
+    assert len(set(pinned.values())) == 16, pinned
+    assert sorted(rule) == [(R, t) for R in range(9, 17) for t in (255, 256)]
+    for R in range(9, 17):
+        assert rule[R, 256] == pinned[R, "q8"], (R, rule[R, 256])
+        assert rule[R, 255] == pinned[R, "consecutive"], (R, rule[R, 255])
+
+
 def test_recorder_under_sanitizer(tmp_path):
     """The whole sweep, the codes between and beyond the order families included, with the
     dispatch code and the recorder built under ASan + UBSan (host code with its own main)."""
