@@ -67,6 +67,7 @@ SIGNATURES = {
                                _i64]),
     "rs_host_alloc": (_int, [_vp, _sz, ctypes.POINTER(_vp)]),
     "rs_host_free": (_int, [_vp, _vp]),
+    "rs_host_counters_read": (_int, [_vp, _vp]),
     "rs_encode": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rs_reconstruct": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
     "rs_verify": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
@@ -116,6 +117,12 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 def strerror(code: int) -> str:
     return lib.rs_strerror(code).decode()
+
+
+class HostCounters(ctypes.Structure):
+    """rs_host_counters (include/callfs_rs.h)."""
+    _fields_ = [(name, ctypes.c_uint64)
+                for name in ("calls", "chunks", "launches", "copies", "ragged_calls")]
 
 
 class NativeError(RuntimeError):

@@ -38,22 +38,25 @@ struct MixedGroup {
 
 struct MixedTables {
   int k = 0, m = 0, batch = 0;
+  int rows = 0;  // rows of every pattern: m, or the missing count of build_mixed_tables_missing
   std::vector<MixedPattern> patterns;  // P distinct masks, in order of first appearance
   std::vector<uint32_t> pat;           // [batch]: stripe b's pattern
   std::vector<MixedGroup> groups;
   int P() const { return static_cast<int>(patterns.size()); }
 };
 
-enum class MixedError { kOk, kTooFewShards, kSingular };
+enum class MixedError { kOk, kTooFewShards, kSingular, kRowCount };
 
-// present: batch * (k + m) flags, stripe b's mask at present + b * (k + m); nonzero =
-// present. Fills `t`; on an error `t` is left in an unspecified state.
-inline MixedError build_mixed_tables(int k, int m, int batch, const uint8_t* present,
-                                     MixedTables& t) {
+// The builder behind both forms below. rows == m: every pattern's m rows, missing then
+// compared. rows < m or missing_only: the e = rows missing shards alone (all written); a
+// stripe with another missing count is reported as kRowCount.
+inline MixedError build_mixed_rows(int k, int m, int rows, bool missing_only, int batch,
+                                   const uint8_t* present, MixedTables& t) {
   const int n = k + m;
   t = MixedTables();
   t.k = k;
   t.m = m;
+  t.rows = rows;
   t.batch = batch;
   t.pat.resize(static_cast<size_t>(batch));
   std::map<std::string, uint32_t> seen;
@@ -77,7 +80,11 @@ inline MixedError build_mixed_tables(int k, int m, int batch, const uint8_t* pre
       p.valid = dp.valid;
       p.rows = dp.missing;
       p.missing = static_cast<int>(dp.missing.size());
-      p.rows.insert(p.rows.end(), dp.check.begin(), dp.check.end());
+      if (missing_only) {
+        if (p.missing != rows) return MixedError::kRowCount;
+      } else {
+        p.rows.insert(p.rows.end(), dp.check.begin(), dp.check.end());
+      }
       it = seen.emplace(key, static_cast<uint32_t>(t.patterns.size())).first;
       t.patterns.push_back(std::move(p));
       plans.push_back(std::move(dp));
@@ -85,10 +92,10 @@ inline MixedError build_mixed_tables(int k, int m, int batch, const uint8_t* pre
     t.pat[static_cast<size_t>(b)] = it->second;
   }
   const size_t P = t.patterns.size();
-  for (int g0 = 0; g0 < m; g0 += kMixedRowsPerLaunch) {
+  for (int g0 = 0; g0 < rows; g0 += kMixedRowsPerLaunch) {
     MixedGroup g;
     g.row0 = g0;
-    g.R = std::min(kMixedRowsPerLaunch, m - g0);
+    g.R = std::min(kMixedRowsPerLaunch, rows - g0);
     const size_t per_shard = 32u * static_cast<size_t>(nibble_width(g.R));
     g.tab_stride = static_cast<size_t>(k) * per_shard;
     g.arena.assign(P * g.tab_stride, 0);
@@ -106,6 +113,21 @@ inline MixedError build_mixed_tables(int k, int m, int batch, const uint8_t* pre
     t.groups.push_back(std::move(g));
   }
   return MixedError::kOk;
+}
+
+// present: batch * (k + m) flags, stripe b's mask at present + b * (k + m); nonzero =
+// present. Fills `t`; on an error `t` is left in an unspecified state.
+inline MixedError build_mixed_tables(int k, int m, int batch, const uint8_t* present,
+                                     MixedTables& t) {
+  return build_mixed_rows(k, m, m, false, batch, present, t);
+}
+
+// The form for reconstructs without verification (the host path's ragged batches): every
+// stripe of the batch has exactly e missing shards (1 <= e <= m), a pattern's rows are those
+// alone, all written, and the launch groups are cut over e instead of m.
+inline MixedError build_mixed_tables_missing(int k, int m, int e, int batch,
+                                             const uint8_t* present, MixedTables& t) {
+  return build_mixed_rows(k, m, e, true, batch, present, t);
 }
 
 // True when every stripe of the batch has the same mask (as 0 / nonzero flags).

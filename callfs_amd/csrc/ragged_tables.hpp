@@ -78,6 +78,7 @@ inline RaggedError build_ragged_tables(int k, int m, int batch, const size_t* si
     case MixedError::kOk: break;
     case MixedError::kTooFewShards: return RaggedError::kTooFewShards;
     case MixedError::kSingular: return RaggedError::kSingular;
+    case MixedError::kRowCount: break;  // the missing-rows form only
   }
   return RaggedError::kOk;
 }

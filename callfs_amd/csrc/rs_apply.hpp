@@ -1434,6 +1434,102 @@ __global__ __launch_bounds__(256) void rs_apply_small(SmallArgs a) {
   }
 }
 
+// ---- one-dispatch small ragged batches (rs_kernels.hpp SmallRaggedArgs) ----------------
+// rs_apply_small over items of different widths and patterns (the in-place transport of a
+// heterogeneous host batch, ragged_chunks.hpp). A block reads its item's four table words from
+// the staging buffer (wave-uniform scalar loads: one dependent read before the data loads),
+// then each lane owns one 16-B vector of the item as in small_vector: sixteen loads in flight
+// before any is consumed, v_perm tables read through scalar loads from device memory. An
+// item's input rows lie in the pattern's read order (the k valid shards, then the compared
+// ones), so no shard-index table is needed: input i is row i, a written row rho is output row
+// rho and a compared one input row k + rho - missing. Bytes past the item's width are
+// computed and stored (the pitch is the width rounded up to 16) and masked out of compares.
+template <int RT>
+__device__ __forceinline__ void small_ragged_vector(const SmallRaggedArgs& a, uint32_t item, uint32_t v,
+                                                    uint32_t in16, uint32_t out16, uint32_t w,
+                                                    uint32_t p) {
+  const uint32_t pitch = (w + 15u) & ~15u;
+  const uint8_t* in = a.base + static_cast<size_t>(in16) * 16u;
+  uint8_t* out = const_cast<uint8_t*>(a.base) + static_cast<size_t>(out16) * 16u;
+  const cptr<uint32_t> pt = as_const(a.ptabs) + static_cast<size_t>(p) * a.pstride;
+  const uint32_t vmask = pt[0], missing = pt[1];
+  const cptr<uint32_t> tabs = pt + 4;
+  uint32_t acc[RT][4];
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[r][q] = 0;
+  // 16 loads in flight before any is consumed; loads past K re-read row K-1 (unconditional
+  // loads keep them in flight together; their values are not used)
+  for (int i0 = 0; i0 < a.K; i0 += 16) {
+    uint4 x[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const uint32_t row = i0 + j < a.K ? i0 + j : a.K - 1;
+      x[j] = *(reinterpret_cast<const uint4*>(in + static_cast<size_t>(pitch) * row) + v);
+    }
+    // keep the 16 loads ahead of every use (as in small_vector)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const bool live = i0 + j < a.K;
+      if (!live) x[j] = make_uint4(0, 0, 0, 0);
+      const cptr<uint32_t> t = tabs + static_cast<size_t>(live ? i0 + j : a.K - 1) * RT * 5;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const Sel sel = selectors(word(x[j], q));
+#pragma unroll
+        for (int r = 0; r < RT; ++r) acc[r][q] = fma1(acc[r][q], gf_mul4(sel, t + r * 5));
+      }
+    }
+  }
+  const uint32_t live = w - v * 16u >= 16u ? 16u : w - v * 16u;
+  uint32_t mask[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint32_t b = live > 4u * q ? live - 4u * q : 0u;
+    mask[q] = b >= 4u ? ~0u : (1u << (8u * b)) - 1u;
+  }
+  bool bad = false;
+#pragma unroll
+  for (int r = 0; r < RT; ++r) {
+    const uint32_t rho = static_cast<uint32_t>(a.row0) + r;
+    const uint4 o = make_uint4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+    if ((vmask >> r) & 1u) {  // wave-uniform
+      const uint4 y =
+          *(reinterpret_cast<const uint4*>(in + static_cast<size_t>(pitch) * (a.K + rho - missing)) + v);
+      bad |= (((y.x ^ o.x) & mask[0]) | ((y.y ^ o.y) & mask[1]) | ((y.z ^ o.z) & mask[2]) |
+              ((y.w ^ o.w) & mask[3])) != 0;
+    } else {
+      *(reinterpret_cast<uint4*>(out + static_cast<size_t>(pitch) * rho) + v) = o;
+    }
+  }
+  if (bad) a.status[item] = 1;  // every writer stores the same flag: no atomic
+}
+
+// Grid: x over ceil(widest item's vectors / 256), y over items. A block past its item's last
+// vector only takes part in the completion count (the epilogue of rs_apply_small).
+template <int RT>
+__global__ __launch_bounds__(256) void rs_apply_small_ragged(SmallRaggedArgs a) {
+  const cptr<uint32_t> it = as_const(a.items) + static_cast<size_t>(blockIdx.y) * 4u;
+  const uint32_t in16 = it[0], out16 = it[1], w = it[2], p = it[3];
+  const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+  if (v < (w + 15u) / 16u) small_ragged_vector<RT>(a, blockIdx.y, v, in16, out16, w, p);
+  if (a.done) {  // launch-uniform
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      __threadfence_system();
+      const unsigned total = gridDim.x * gridDim.y;
+      if (atomicAdd(a.counter, 1u) == total - 1u) {
+        atomicExch(a.counter, 0u);
+        __threadfence_system();
+        __hip_atomic_store(a.done, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+  }
+}
+
 // Grid for the vector kernel: one tile per block, or (PERSIST) a fixed grid of
 // `blocks_per_cu` blocks on each of the 256 CUs.
 template <class P>

@@ -289,6 +289,16 @@ int rs_host_free(rs_ctx* ctx, void* p) {
   return rc;
 }
 
+int rs_host_counters_read(const rs_ctx* ctx, rs_host_counters* out) {
+  if (!ctx || !out) return RS_E_ARG;
+  out->calls = ctx->n_calls.load(std::memory_order_relaxed);
+  out->chunks = ctx->n_chunks.load(std::memory_order_relaxed);
+  out->launches = ctx->n_launches.load(std::memory_order_relaxed);
+  out->copies = ctx->n_copies.load(std::memory_order_relaxed);
+  out->ragged_calls = ctx->n_ragged_calls.load(std::memory_order_relaxed);
+  return RS_OK;
+}
+
 int rs_shard_size(int k, int m, int64_t len, int64_t* shard_size) {
   int rc = check_profile(k, m);
   if (rc) return rc;

@@ -201,12 +201,19 @@ struct Slot {
   bool pending = false;  // a chunk's outputs wait in staging
   int b0 = 0, count = 0;  // its stripes
   size_t off = 0, width = 0;  // and columns
+  size_t rag_chunk = 0;       // the ragged chunk in flight (rs_host.cpp run_ragged_chunks)
 };
 
 constexpr int kMaxSlots = 6;
 
 struct Lane {
   Slot slot[kMaxSlots];
+  // Pattern tables of the last ragged run on this lane, keyed by the run's
+  // profile and pattern list: the launch groups' arenas and compare masks for the staged and
+  // direct transports, the v_perm blocks for the in-place one. A stream of batches of one
+  // profile and pattern list (every encode batch) uploads nothing after the first.
+  DevBuf rag_tabs, rag_small_tabs;
+  std::string rag_key, rag_small_key;
 };
 
 struct Device {
@@ -299,6 +306,8 @@ struct rs_ctx {
   callfs::CopyPool pool;
   callfs::PinnedRegistry pinned;
   callfs::HostPool host_pool;
+  // rs_host_counters_read: monotonic, relaxed
+  std::atomic<uint64_t> n_calls{0}, n_chunks{0}, n_launches{0}, n_copies{0}, n_ragged_calls{0};
 
   rs_ctx();
   ~rs_ctx();

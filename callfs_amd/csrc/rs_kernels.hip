@@ -411,6 +411,25 @@ hipError_t launch_small(const SmallArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
+namespace {
+using SmallRaggedFn = void (*)(SmallRaggedArgs);
+template <int... Rs>
+constexpr auto small_ragged_table(std::integer_sequence<int, Rs...>) {
+  return std::array<SmallRaggedFn, sizeof...(Rs)>{&dev::rs_apply_small_ragged<Rs + 1>...};
+}
+const auto kSmallRagged = small_ragged_table(std::make_integer_sequence<int, kMaxRowsPerLaunch>{});
+}  // namespace
+
+hipError_t launch_small_ragged(const SmallRaggedArgs& a, hipStream_t stream) {
+  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.nitems < 1 ||
+      a.nitems > 65535 || a.max_nvec == 0 || a.row0 < 0 || !a.base || !a.items || !a.ptabs ||
+      !a.status || !a.counter)
+    return hipErrorInvalidValue;
+  const unsigned gx = (a.max_nvec + 255u) / 256u;
+  hipLaunchKernelGGL(kSmallRagged[a.R - 1], dim3(gx, static_cast<unsigned>(a.nitems)), dim3(256), 0,
+                     stream, a);
+  return hipGetLastError();
+}
 
 void set_slice_tiles_for_tuning(long long tiles) {
   g_slice_tiles_override.store(tiles, std::memory_order_relaxed);

@@ -102,6 +102,35 @@ struct SmallArgs {
 // Enqueues rs_apply_small for one launch group on `stream`.
 hipError_t launch_small(const SmallArgs& a, hipStream_t stream);
 
+// One-dispatch small ragged batches (rs_apply_small_ragged): a chunk of items of different
+// widths and patterns in host-coherent staging (ragged_chunks.hpp), one launch group per
+// launch. Item j's table entry is four dwords in the staging buffer itself: {offset of its
+// input rows / 16, offset of its output rows / 16, width in bytes, pattern}; rows are pitched
+// at the width rounded up to 16. Input row i is the pattern's i-th read shard (the k valid
+// ones, then the compared ones); row rho of the pattern is output row rho when written and
+// input row K + rho - missing when compared.
+struct SmallRaggedArgs {
+  const uint8_t* base;    // the chunk's staging
+  const uint32_t* items;  // [nitems][4], inside the staging buffer
+  // device memory, cached per lane: pattern p's block of this launch group at
+  // ptabs + p * pstride dwords: {compare mask, missing count, 0, 0}, then [K][R][5] v_perm tables
+  const uint32_t* ptabs;
+  uint32_t pstride;
+  uint32_t max_nvec;  // 16-B vectors of the widest item
+  int K;
+  int R;
+  int row0;  // first pattern row of this launch group
+  int nitems;
+  int* status;  // host-coherent: status[j] = 1 when item j's compared rows mismatch
+  // completion flag and counter as in SmallArgs
+  int* done;
+  unsigned* counter;
+  int seq;
+};
+
+// Enqueues rs_apply_small_ragged for one launch group on `stream`.
+hipError_t launch_small_ragged(const SmallRaggedArgs& a, hipStream_t stream);
+
 // addr_tz for a set of shard addresses: trailing zeros of the OR of their differences
 // from the first (63 for a single address).
 inline int shard_addr_tz(const void* const* p, int count) {

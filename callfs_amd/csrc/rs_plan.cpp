@@ -320,6 +320,7 @@ int rs_plan_create_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int ba
     case MixedError::kOk: break;
     case MixedError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
     case MixedError::kSingular: return RS_E_SINGULAR;
+    case MixedError::kRowCount: return RS_E_ARG;  // the missing-rows form only
   }
   // reads: k valid shards + the compared shards; writes: the missing ones = n per stripe
   plan->bytes = static_cast<uint64_t>(batch) * S * static_cast<uint64_t>(n);

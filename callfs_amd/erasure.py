@@ -353,6 +353,17 @@ def reconstruct_batch(stripes: List[List], k: int, m: int, verify: bool = True,
     return out
 
 
+def host_counters(context: Optional[N.Context] = None) -> dict:
+    """rs_host_counters_read: the context's monotonic counts of host-memory calls that
+    reached a device (`calls`), chunks sent (`chunks`), compute launches (`launches`, one per
+    launch group per chunk), H2D / D2H / memset dispatches (`copies`) and batch calls that took
+    the ragged path (`ragged_calls`)."""
+    ctx = context or N.default_context()
+    c = N.HostCounters()
+    N.check(N.lib.rs_host_counters_read(ctx.handle, ctypes.byref(c)), "rs_host_counters_read")
+    return {name: int(getattr(c, name)) for name, _ in c._fields_}
+
+
 # ---- host-side matrices (no device needed) ------------------------------------------
 
 def encode_matrix(k: int, m: int) -> np.ndarray:

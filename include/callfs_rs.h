@@ -122,10 +122,18 @@ int rs_verify(rs_ctx* ctx, int k, int m, const uint8_t* const* shards, const siz
 
 /* ---- Batched, host memory (many independent stripes per call) ----------------------
  * Not in the reference API: for callers holding many objects at once (repair of every
- * object that lost one shard, bulk re-encode, a server batching small uploads). Stripes
- * are grouped by (S, presence) and each group runs one pipeline in which small stripes
- * are packed many per H2D / launch / D2H, so a batch of 4 KiB objects costs a few round
- * trips instead of one per object.
+ * object that lost one shard, bulk re-encode, a server batching small uploads). A batch
+ * whose stripes all share one shard size and one presence mask runs as one uniform
+ * pipeline in which small stripes are packed many per H2D / launch / D2H. A batch of
+ * different shard sizes or masks runs as one ragged pipeline: the stripes (column parts of
+ * the large ones) are packed into chunks of CALLFS_RS_CHUNK_BYTES whatever their sizes and
+ * masks, and a chunk costs one H2D, one launch per group of 16 rows and one D2H -- or one
+ * dispatch in place on host-coherent staging for batches of at most
+ * CALLFS_RS_SMALL_MAX_BYTES, or launches on the caller's own buffers when all of them
+ * are rs_host_alloc memory -- so the call's cost follows its bytes, not the number of sizes
+ * and masks in it. (Reconstructs with verify == 0 run one such pipeline per missing-shard
+ * count.) CALLFS_RS_RAGGED_BATCH=0 (read once per process) runs one pipeline per
+ * (S, presence) group instead.
  * rs_encode_batch: stripe b has sizes[b]-byte shards, data[b*k + i] / parity[b*m + j]
  *   (= rs_encode per stripe, codec.go:36). sizes[b] == 0 -> status[b] = RS_E_NO_DATA.
  * rs_reconstruct_batch: shards[b*n + i] / lens[b*n + i] with rs_reconstruct's contract
@@ -140,6 +148,25 @@ int rs_encode_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes,
                     const uint8_t* const* data, uint8_t* const* parity, int* status);
 int rs_reconstruct_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
                          size_t* lens, int verify, int* status);
+
+/* ---- counters of the host-memory path -----------------------------------------------
+ * Monotonic per-context counts (relaxed atomics; what an operator graphs, and what shows
+ * that a batch cost one round trip):
+ *   calls         host-memory entry-point calls that reached a device
+ *   chunks        chunks sent
+ *   launches      compute launches, one per launch group per chunk (slices of one group
+ *                 count once)
+ *   copies        H2D / D2H / memset dispatches enqueued for host-memory calls (table
+ *                 uploads included)
+ *   ragged_calls  batch calls that took the ragged path */
+typedef struct rs_host_counters {
+  uint64_t calls;
+  uint64_t chunks;
+  uint64_t launches;
+  uint64_t copies;
+  uint64_t ragged_calls;
+} rs_host_counters;
+int rs_host_counters_read(const rs_ctx* ctx, rs_host_counters* out);
 
 /* ---- device-resident plans (batched stripes, graph-capturable launches) -------------
  * A plan fixes (k, m, S, batch, presence mask) and the device pointers of every
