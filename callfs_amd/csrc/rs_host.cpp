@@ -10,6 +10,7 @@
 #include <chrono>
 #include <thread>
 
+#include "codec_batch.hpp"
 #include "ragged_chunks.hpp"
 #include "rs_internal.hpp"
 
@@ -87,8 +88,8 @@ bool spin_until(const int* flag, int want, int us) {
 // One host-memory call over `batch` stripes that share one table set and one shard size
 // S. in(b, i) / out(b, i) give host buffers by stripe and shard index. stripe_status
 // (nullable, `batch` ints) receives 1 for stripes whose verify rows mismatched. `join`
-// (single-stripe decodes; host_path.hpp) is written while the columns pass through the
-// copy pool; col0 is this call's first column in the whole object (a column part of a
+// (nullable, one Join per stripe; host_path.hpp) is written while the columns pass through
+// the copy pool; col0 is this call's first column in the whole object (a column part of a
 // split object).
 template <class InF, class OutF>
 struct HostCall {
@@ -107,6 +108,7 @@ struct HostCall {
   const std::vector<int>& outs() const { return tp->missing; }  // the shards written
   int n() const { return tp->k + tp->m; }
   bool verify() const { return !tp->check.empty(); }
+  const Join* join_of(int b) const { return join ? join + b : nullptr; }
   // marks the stripes from b0 whose status word is set; true when any is
   bool scan_status(const int* st, int b0, int count) const {
     bool corrupt = false;
@@ -151,7 +153,8 @@ bool direct_ok(const HostCall<InF, OutF>& c) {
     for (int i : c.ins) direct = direct && pinned.contains(c.in(b, i), c.S);
     for (int i : c.outs()) direct = direct && pinned.contains(c.out(b, i), c.S);
   }
-  if (direct && c.join) direct = pinned.contains(c.join->out, c.join->len);
+  for (int b = 0; direct && c.join && b < c.batch; ++b)
+    direct = c.join[b].len == 0 || pinned.contains(c.join[b].out, c.join[b].len);
   return direct;
 }
 
@@ -184,12 +187,13 @@ int run_direct(const HostCall<InF, OutF>& c, Slot& sl) {
   // reconstructed ones once they have landed
   auto join_segs = [&](bool present) {
     std::vector<CopyPool::Seg> js_segs;
-    for (int i = 0; c.join && i < t.k; ++i) {
-      if (static_cast<bool>(is_out[i]) == present) continue;
-      const auto js = join_span(c.join, i, c.col0, c.S);
-      if (js.first)
-        js_segs.push_back({js.first, present ? c.in(0, i) : c.out(0, i), js.second});
-    }
+    for (int b = 0; c.join && b < batch; ++b)
+      for (int i = 0; i < t.k; ++i) {
+        if (static_cast<bool>(is_out[i]) == present) continue;
+        const auto js = join_span(c.join_of(b), i, c.col0, c.S);
+        if (js.first)
+          js_segs.push_back({js.first, present ? c.in(b, i) : c.out(b, i), js.second});
+      }
     c.ctx->pool.run(js_segs);
   };
   join_segs(true);
@@ -232,7 +236,7 @@ int run_chunks(const HostCall<InF, OutF>& c, Lane& L, const ChunkGeometry& g, Tr
     uint8_t* h = tr.staging(sl);
     for (int b = 0; b < sl.count; ++b)
       for (int i : c.outs()) {
-        const auto tee = join_span(c.join, i, c.col0 + sl.off, sl.width);
+        const auto tee = join_span(c.join_of(sl.b0 + b), i, c.col0 + sl.off, sl.width);
         segs.push_back({c.out(sl.b0 + b, i) + sl.off, h + g.spitch * b + g.cpitch * i, sl.width,
                         tee.first, tee.second});
       }
@@ -251,7 +255,7 @@ int run_chunks(const HostCall<InF, OutF>& c, Lane& L, const ChunkGeometry& g, Tr
     uint8_t* h = tr.staging(sl);
     for (int b = 0; b < cnt; ++b)
       for (int i : c.ins) {
-        const auto tee = join_span(c.join, i, c.col0 + off, w);
+        const auto tee = join_span(c.join_of(b0 + b), i, c.col0 + off, w);
         segs.push_back({h + g.spitch * b + g.cpitch * i, c.in(b0 + b, i) + off, w, tee.first,
                         tee.second});
       }
@@ -469,7 +473,6 @@ template <class InF, class OutF>
 int run_host_impl(rs_ctx* ctx, Lane& L, int device, const std::shared_ptr<const Tables>& tp,
                   size_t S, int batch, InF host_in, OutF host_out, int* stripe_status,
                   const Join* join, size_t col0) {
-  if (batch != 1) join = nullptr;  // only single-object decodes join
   HIPCHK(hipSetDevice(device));
   HostCall<InF, OutF> c{ctx, tp, S, batch, host_in, host_out, stripe_status, join, col0, tp->valid};
   c.ins.insert(c.ins.end(), tp->check.begin(), tp->check.end());
@@ -596,6 +599,8 @@ struct RaggedRun {
   MixedTables mt;
   RaggedShape sh;
   std::vector<int> ids;
+  const Join* joins;  // nullable: one per runnable stripe of the call (codec-level batches)
+  const Join* join_of(int id) const { return joins ? joins + id : nullptr; }
   const MixedPattern& pattern(int s) const { return mt.patterns[mt.pat[static_cast<size_t>(s)]]; }
   void count(size_t chunks, size_t copies) const {
     ctx->n_chunks.fetch_add(chunks, std::memory_order_relaxed);
@@ -830,9 +835,13 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
       const int id = r.ids[static_cast<size_t>(it.stripe)];
       if (st[j]) flags[id] = 1;
       const MixedPattern& pt = r.pattern(it.stripe);
-      for (int row = 0; row < pt.missing; ++row)
-        segs.push_back({out(id, pt.rows[static_cast<size_t>(row)]) + it.off,
-                        h + C.items[j].out_off + C.items[j].pitch * static_cast<size_t>(row), it.w});
+      for (int row = 0; row < pt.missing; ++row) {
+        const int i = pt.rows[static_cast<size_t>(row)];
+        const auto tee = join_span(r.join_of(id), i, it.off, it.w);
+        segs.push_back({out(id, i) + it.off,
+                        h + C.items[j].out_off + C.items[j].pitch * static_cast<size_t>(row), it.w,
+                        tee.first, tee.second});
+      }
     }
     sl.pending = false;
     return RS_OK;
@@ -863,8 +872,11 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
       const RaggedItem& it = items[C.first + j];
       const int id = r.ids[static_cast<size_t>(it.stripe)];
       const MixedPattern& pt = r.pattern(it.stripe);
-      for (size_t i = 0; i < k; ++i)
-        segs.push_back({h + C.items[j].in_off + C.items[j].pitch * i, in(id, pt.valid[i]) + it.off, it.w});
+      for (size_t i = 0; i < k; ++i) {
+        const auto tee = join_span(r.join_of(id), pt.valid[i], it.off, it.w);
+        segs.push_back({h + C.items[j].in_off + C.items[j].pitch * i, in(id, pt.valid[i]) + it.off, it.w,
+                        tee.first, tee.second});
+      }
       for (size_t row = static_cast<size_t>(pt.missing); row < pt.rows.size(); ++row)
         segs.push_back({row_at(h, j, static_cast<int>(row)), in(id, pt.rows[row]) + it.off, it.w});
     }
@@ -883,7 +895,9 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
 
 // Direct: every buffer of the run lies in rs_host_alloc memory. One metadata upload (the
 // pointer tables name the caller's buffers), launch_ragged per launch group, the status
-// words back, then a sync. No staging copies and no chunking.
+// words back, then a sync. No staging copies and no chunking; a codec-level batch's tees and
+// joins are copy-pool work on the caller's bytes (present shards while the kernels run,
+// rebuilt ones once they have landed), as in run_direct.
 template <class InF, class OutF>
 int run_ragged_direct(const RaggedRun& r, Lane& L, InF& in, OutF& out, int* flags) {
   std::vector<RaggedItem> items;
@@ -923,7 +937,30 @@ int run_ragged_direct(const RaggedRun& r, Lane& L, InF& in, OutF& out, int* flag
                           sl.stream));
   HIPCHK(hipEventRecord(sl.done, sl.stream));
   r.count(1, compares ? 2 : 1);
+  auto join_segs = [&](bool present) {
+    std::vector<CopyPool::Seg> js_segs;
+    for (size_t j = 0; r.joins && j < C.count; ++j) {
+      const int id = r.ids[j];
+      const MixedPattern& pt = r.pattern(static_cast<int>(j));
+      const size_t S = r.sh.size[j];
+      if (present) {
+        for (int i : pt.valid) {
+          const auto js = join_span(r.join_of(id), i, 0, S);
+          if (js.first) js_segs.push_back({js.first, in(id, i), js.second});
+        }
+      } else {
+        for (int row = 0; row < pt.missing; ++row) {
+          const int i = pt.rows[static_cast<size_t>(row)];
+          const auto js = join_span(r.join_of(id), i, 0, S);
+          if (js.first) js_segs.push_back({js.first, out(id, i), js.second});
+        }
+      }
+    }
+    r.ctx->pool.run(js_segs);
+  };
+  join_segs(true);
   HIPCHK(hipEventSynchronize(sl.done));
+  join_segs(false);
   if (compares) {
     const int* st = static_cast<const int*>(sl.hstat.p);
     for (size_t j = 0; j < C.count; ++j)
@@ -940,7 +977,7 @@ int run_ragged_direct(const RaggedRun& r, Lane& L, InF& in, OutF& out, int* flag
 template <class InF, class OutF>
 int run_ragged_impl(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_missing,
                     const std::vector<size_t>& S, const std::vector<uint8_t>& present, InF& in,
-                    OutF& out, int* flags) {
+                    OutF& out, int* flags, const Join* joins) {
   HIPCHK(hipSetDevice(device));
   const int n = k + m, stripes = static_cast<int>(S.size());
   const size_t nn = static_cast<size_t>(n);
@@ -959,10 +996,12 @@ int run_ragged_impl(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_miss
       }
       direct = ctx->pinned.contains(written ? out(j, i) : in(j, i), S[static_cast<size_t>(j)]);
     }
+  for (int j = 0; direct && joins && j < stripes; ++j)
+    direct = joins[j].len == 0 || ctx->pinned.contains(joins[j].out, joins[j].len);
   for (const RaggedClass& cls : ragged_classes(n, stripes, present.data(), by_missing)) {
     const int rows = by_missing ? cls.e : m;
     for (const auto& seg : ragged_segments(k, n, rows, cls.stripes, present.data(), kRaggedArenaBudget)) {
-      RaggedRun r{ctx, k, m, {}, {}, {}};
+      RaggedRun r{ctx, k, m, {}, {}, {}, joins};
       r.ids.assign(cls.stripes.begin() + static_cast<ptrdiff_t>(seg.first),
                    cls.stripes.begin() + static_cast<ptrdiff_t>(seg.second));
       std::vector<uint8_t> pres(r.ids.size() * nn);
@@ -1016,7 +1055,8 @@ int run_ragged_impl(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_miss
 
 template <class InF, class OutF>
 int run_ragged(rs_ctx* ctx, int k, int m, bool by_missing, const std::vector<size_t>& S,
-               const std::vector<uint8_t>& present, InF in, OutF out, int* flags) {
+               const std::vector<uint8_t>& present, InF in, OutF out, int* flags,
+               const Join* joins = nullptr) {
   if (ctx->devs.empty()) return RS_E_HIP;
   ctx->n_calls.fetch_add(1, std::memory_order_relaxed);
   ctx->n_ragged_calls.fetch_add(1, std::memory_order_relaxed);
@@ -1024,7 +1064,7 @@ int run_ragged(rs_ctx* ctx, int k, int m, bool by_missing, const std::vector<siz
   Device* dev = ctx->devs[device_slot(ctx->rr.fetch_add(1), 0, ctx->devs.size())].get();
   LaneGuard lg{ctx, dev, ctx->acquire(dev)};
   if (!lg.lane) return RS_E_HIP;
-  const int rc = run_ragged_impl(ctx, *lg.lane, dev->id, k, m, by_missing, S, present, in, out, flags);
+  const int rc = run_ragged_impl(ctx, *lg.lane, dev->id, k, m, by_missing, S, present, in, out, flags, joins);
   if (rc != RS_OK) {
     // never hand a lane with work in flight to the next caller
     for (Slot& sl : lg.lane->slot) {
@@ -1075,6 +1115,54 @@ int reconstruct_host(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* 
 int first_error(const int* status, int batch) {
   for (int b = 0; b < batch; ++b)
     if (status[b]) return status[b];
+  return RS_OK;
+}
+
+// The runnable objects of a codec-level batch, routed as rs_encode_batch /
+// rs_reconstruct_batch route their stripes: one (S, mask) group runs the uniform pipeline,
+// two or more run one ragged pipeline (CALLFS_RS_RAGGED_BATCH=0: one pipeline per group).
+// S, present (n flags each), joins and flags are indexed by object; in(b, i) / out(b, i)
+// give object b's shard i. verify: the tables compare the present shards beyond the first k.
+template <class InF, class OutF>
+int run_codec_batch(rs_ctx* ctx, int k, int m, bool verify, const BatchGroups& groups,
+                    const std::vector<size_t>& S, const std::vector<uint8_t>& present,
+                    const std::vector<Join>& joins, InF in, OutF out, std::vector<int>& flags) {
+  const size_t n = static_cast<size_t>(k + m);
+  int rc;
+  if (groups.by_key.size() >= 2 && ragged_batch()) {
+    std::vector<int> ids;
+    for (auto& kv : groups.by_key) ids.insert(ids.end(), kv.second.begin(), kv.second.end());
+    std::sort(ids.begin(), ids.end());
+    std::vector<size_t> Sj(ids.size());
+    std::vector<uint8_t> pres(ids.size() * n);
+    std::vector<Join> jj(ids.size());
+    for (size_t j = 0; j < ids.size(); ++j) {
+      const size_t b = static_cast<size_t>(ids[j]);
+      Sj[j] = S[b];
+      std::memcpy(&pres[j * n], &present[b * n], n);
+      jj[j] = joins[b];
+    }
+    std::vector<int> fj(ids.size(), 0);
+    rc = run_ragged(ctx, k, m, false, Sj, pres, [&](int j, int i) { return in(ids[j], i); },
+                    [&](int j, int i) { return out(ids[j], i); }, fj.data(), jj.data());
+    for (size_t j = 0; j < ids.size(); ++j) flags[static_cast<size_t>(ids[j])] = fj[j];
+    return rc;
+  }
+  bool first = true;
+  for (auto& kv : groups.by_key) {
+    const std::vector<int>& ids = kv.second;
+    auto t = ctx->cache.get(k, m, BatchGroups::present(kv.first), verify);
+    if (!t) return RS_E_SINGULAR;
+    std::vector<Join> jj;
+    for (int b : ids) jj.push_back(joins[static_cast<size_t>(b)]);
+    std::vector<int> fj(ids.size(), 0);
+    rc = run_host(ctx, t, BatchGroups::shard_size(kv.first), static_cast<int>(ids.size()),
+                  [&](int b, int i) { return in(ids[b], i); },
+                  [&](int b, int i) { return out(ids[b], i); }, fj.data(), jj.data(), first);
+    first = false;
+    if (rc != RS_OK && rc != RS_E_CORRUPT) return rc;
+    for (size_t j = 0; j < ids.size(); ++j) flags[static_cast<size_t>(ids[j])] = fj[j];
+  }
   return RS_OK;
 }
 
@@ -1320,6 +1408,101 @@ int rs_reconstruct_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* s
     for (int b : ids)
       for (int i : t->missing) lens[static_cast<size_t>(b) * n + i] = S;
   }
+  return first_error(status, batch);
+}
+
+// ---- exported: codec-level batches (objects in, objects out) ----------------------------
+
+int rs_codec_encode_batch(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* data,
+                          const size_t* lens, uint8_t* const* shards_out, const size_t* out_caps,
+                          size_t* shard_sizes, int* status) {
+  DeviceGuard dg;
+  // per object codec.go:31 Split and :36 Encode; the profile (:22-26) is the call's
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 ||
+      (batch && (!data || !lens || !shards_out || !out_caps || !shard_sizes || !status)))
+    return RS_E_ARG;
+  const int n = k + m;
+  const size_t B = static_cast<size_t>(batch);
+  std::vector<uint8_t> present(B * n, 0);
+  std::vector<SplitPlan> plan(B);
+  std::vector<size_t> S(B, 0);
+  std::vector<Join> tees(B, Join{nullptr, 0, 0, k});
+  BatchGroups groups;
+  for (size_t b = 0; b < B; ++b) {
+    if (lens[b] == 0) {
+      status[b] = RS_E_SHORT_DATA;  // upstream Split
+      continue;
+    }
+    plan[b] = split_plan(k, lens[b]);
+    if (!data[b] || !shards_out[b] || out_caps[b] / static_cast<size_t>(n) < plan[b].S) {
+      status[b] = RS_E_ARG;
+      continue;
+    }
+    status[b] = RS_OK;
+    shard_sizes[b] = S[b] = plan[b].S;
+    split_prepare(plan[b], n, data[b], shards_out[b]);
+    tees[b] = split_tee(plan[b], shards_out[b]);
+    for (int i = 0; i < k; ++i) present[b * n + i] = 1;
+    groups.add(S[b], &present[b * n], n, static_cast<int>(b));
+  }
+  std::vector<int> flags(B, 0);
+  rc = run_codec_batch(ctx, k, m, false, groups, S, present, tees,
+                       [&](int b, int i) { return split_row(plan[b], data[b], shards_out[b], i); },
+                       [&](int b, int i) { return shards_out[b] + S[b] * static_cast<size_t>(i); },
+                       flags);
+  if (rc) return rc;
+  return first_error(status, batch);
+}
+
+int rs_codec_decode_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
+                          size_t* lens, uint8_t* const* out, const int64_t* original_sizes,
+                          int* status) {
+  DeviceGuard dg;
+  // per object codec.go:55 Reconstruct, :59-65 Verify, :67-77 join / trim
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!shards || !lens || !out || !original_sizes || !status)))
+    return RS_E_ARG;
+  const int n = k + m;
+  const size_t B = static_cast<size_t>(batch);
+  std::vector<uint8_t> present(B * n, 0);
+  std::vector<size_t> S(B, 0);
+  std::vector<Join> joins(B, Join{nullptr, 0, 0, k});
+  BatchGroups groups;
+  for (size_t b = 0; b < B; ++b) {
+    uint8_t* const* sh = shards + b * n;
+    const size_t* ln = lens + b * n;
+    int np = 0;
+    if ((status[b] = check_lens(n, ln, true, &S[b], &np))) continue;
+    if (np < k) {
+      status[b] = RS_E_TOO_FEW_SHARDS;
+      continue;
+    }
+    bool ok = original_sizes[b] >= 0 && (original_sizes[b] == 0 || out[b]);
+    for (int i = 0; i < n; ++i) ok &= sh[i] != nullptr;
+    if (!ok) {
+      status[b] = RS_E_ARG;
+      continue;
+    }
+    for (int i = 0; i < n; ++i) present[b * n + i] = ln[i] != 0;
+    joins[b] = decode_join(k, S[b], out[b], static_cast<size_t>(original_sizes[b]));
+    groups.add(S[b], &present[b * n], n, static_cast<int>(b));
+  }
+  std::vector<int> flags(B, 0);
+  auto shard = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
+  rc = run_codec_batch(ctx, k, m, true, groups, S, present, joins, shard, shard, flags);
+  if (rc) return rc;
+  for (auto& kv : groups.by_key)
+    for (int b : kv.second) {
+      for (int i = 0; i < n; ++i)
+        if (!present[static_cast<size_t>(b) * n + i]) lens[static_cast<size_t>(b) * n + i] = S[b];
+      if (flags[b])
+        status[b] = RS_E_CORRUPT;
+      else if (static_cast<uint64_t>(S[b]) * k < static_cast<uint64_t>(original_sizes[b]))
+        status[b] = RS_E_INSUFFICIENT;
+    }
   return first_error(status, batch);
 }
 

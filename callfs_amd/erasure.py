@@ -7,6 +7,7 @@ Same names, argument meaning and error behaviour as the reference:
     NewCodec()                                      Codec()                                                  codec.go:15-17
     (*Codec).Encode(data, profile)                  Codec.encode(data, profile) -> list of n shards          codec.go:21-41
     (*Codec).Decode(shards, profile, originalSize)  Codec.decode(shards, profile, original_size) -> bytes    codec.go:45-78
+    (no counterpart: many objects per call)         Codec.encode_many / Codec.decode_many                    DESIGN.md §7.6
     ShardChecksum(data)                             shard_checksum(data)                                     codec.go:81-84
     ErrInsufficientShards/ErrShardCorrupted/...     exception classes of the same names                      errors.go:7-10
 
@@ -100,6 +101,19 @@ def _wrapped(rc: int, prefix: str) -> Exception:
     if cls is None:
         return N.NativeError(rc, prefix)
     return cls(f"{prefix}: {cls.text}")
+
+
+def _decode_error(rc: int) -> Exception:
+    """What Codec.decode raises for a nonzero code of rs_codec_decode (codec.go:45-78)."""
+    if rc == N.RS_E_CORRUPT:
+        return ErrShardCorrupted()
+    if rc == N.RS_E_INSUFFICIENT:
+        return ErrInsufficientShards()
+    if rc == N.RS_E_INVALID_PROFILE:
+        return ErrInvalidProfile()
+    if rc in (N.RS_E_TOO_FEW_SHARDS, N.RS_E_SHARD_SIZE, N.RS_E_NO_DATA, N.RS_E_SINGULAR):
+        return _wrapped(rc, "erasure: reconstruction failed")
+    return N.NativeError(rc, "erasure: decode")
 
 
 # ---- profile -----------------------------------------------------------------------
@@ -220,15 +234,106 @@ class Codec:
                     shards[i] = bufs[i]
         if rc == N.RS_OK:
             return out
-        if rc == N.RS_E_CORRUPT:
-            raise ErrShardCorrupted()
-        if rc == N.RS_E_INSUFFICIENT:
-            raise ErrInsufficientShards()
-        if rc == N.RS_E_INVALID_PROFILE:
+        raise _decode_error(rc)
+
+    def encode_many(self, datas: Sequence, profile: ErasureProfile
+                    ) -> Tuple[List[Optional[List[memoryview]]], List[Optional[Exception]]]:
+        """Codec.encode for many objects of one profile in one native call
+        (rs_codec_encode_batch: one pipeline over all of them, Split done on the way into its
+        staging). Returns (shards_per_object, errors): errors[b] is None and
+        shards_per_object[b] the n shards of object b (views into one fresh n*S buffer), or
+        errors[b] is an instance of the class and message encode() would have raised for that
+        object and shards_per_object[b] is None. Profile errors raise."""
+        k, m = profile.data_shards, profile.parity_shards
+        if k < 1 or m < 1:
             raise ErrInvalidProfile()
-        if rc in (N.RS_E_TOO_FEW_SHARDS, N.RS_E_SHARD_SIZE, N.RS_E_NO_DATA, N.RS_E_SINGULAR):
-            raise _wrapped(rc, "erasure: reconstruction failed")
-        raise N.NativeError(rc, "erasure: decode")
+        if k + m > 256:
+            raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create encoder")
+        n, B = k + m, len(datas)
+        srcs = [memoryview(d).cast("B") for d in datas]
+        outs = [bytearray(n * ((len(s) + k - 1) // k)) for s in srcs]
+        lens = (ctypes.c_size_t * max(B, 1))(*[len(s) for s in srcs])
+        caps = (ctypes.c_size_t * max(B, 1))(*[len(o) for o in outs])
+        sizes = (ctypes.c_size_t * max(B, 1))()
+        status = (ctypes.c_int * max(B, 1))()
+        rc = N.lib.rs_codec_encode_batch(self.context.handle, k, m, B, _shard_ptrs(srcs or [None]),
+                                         lens, _shard_ptrs(outs or [None]), caps, sizes, status)
+        st = list(status)[:B]
+        if rc != N.RS_OK and rc not in st:
+            raise N.NativeError(rc, "rs_codec_encode_batch")  # call-level
+        shards, errors = [], []
+        for b in range(B):
+            if st[b] == N.RS_OK:
+                S, mv = sizes[b], memoryview(outs[b])
+                shards.append([mv[i * S:(i + 1) * S] for i in range(n)])
+                errors.append(None)
+                continue
+            shards.append(None)
+            errors.append(_wrapped(st[b], "erasure: failed to split data"
+                                   if st[b] == N.RS_E_SHORT_DATA else "erasure: failed to encode parity"))
+        return shards, errors
+
+    def decode_many(self, shards_per_object: Sequence[List], profile: ErasureProfile,
+                    original_sizes: Sequence[int]
+                    ) -> Tuple[List[Optional[bytearray]], List[Optional[Exception]]]:
+        """Codec.decode for many objects of one profile in one native call
+        (rs_codec_decode_batch: Reconstruct, Verify and the join / trim of every object in one
+        pipeline). Returns (objects, errors): errors[b] is None and objects[b] the
+        original_sizes[b] bytes of object b, or errors[b] is an instance of the class and
+        message decode() would have raised for that object and objects[b] is None. Each shard
+        list is mutated as decode() mutates it. Profile errors raise."""
+        k, m = profile.data_shards, profile.parity_shards
+        if k < 1 or m < 1:
+            raise ErrInvalidProfile()
+        n = k + m
+        if n > 256:
+            raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create decoder")
+        if len(original_sizes) != len(shards_per_object):
+            raise ValueError("one original size per object")
+        B = len(shards_per_object)
+        errors: List[Optional[Exception]] = [None] * B
+        run = []  # the objects handed to the native call
+        for b, shards in enumerate(shards_per_object):
+            if len(shards) != n:
+                errors[b] = ErrTooFewShards(f"erasure: reconstruction failed: {ErrTooFewShards.text}")
+            elif int(original_sizes[b]) < 0:
+                errors[b] = N.NativeError(N.RS_E_ARG, "erasure: decode")
+            else:
+                run.append(b)
+        R = len(run)
+        lens = (ctypes.c_size_t * max(R * n, 1))()
+        flat, bufs, outs = [], [], []
+        for j, b in enumerate(run):
+            shards = shards_per_object[b]
+            ln = [0 if s is None else len(s) for s in shards]
+            S = next((x for x in ln if x), 0)
+            cp = list(shards)
+            for i in range(n):
+                lens[j * n + i] = ln[i]
+                if ln[i] == 0 and S:
+                    cp[i] = bytearray(S)  # upstream Reconstruct allocates missing shards
+            bufs.append(cp)
+            flat += cp
+            outs.append(bytearray(int(original_sizes[b])))
+        sizes = (ctypes.c_int64 * max(R, 1))(*[int(original_sizes[b]) for b in run])
+        status = (ctypes.c_int * max(R, 1))()
+        rc = N.lib.rs_codec_decode_batch(self.context.handle, k, m, R, _shard_ptrs(flat or [None]),
+                                         lens, _shard_ptrs(outs or [None]), sizes, status)
+        st = list(status)[:R]
+        if rc != N.RS_OK and rc not in st:
+            raise N.NativeError(rc, "rs_codec_decode_batch")  # call-level
+        objects: List[Optional[bytearray]] = [None] * B
+        for j, b in enumerate(run):
+            shards = shards_per_object[b]
+            if st[j] in (N.RS_OK, N.RS_E_CORRUPT, N.RS_E_INSUFFICIENT):
+                for i in range(n):
+                    if shards[i] is None or len(shards[i]) == 0:
+                        shards[i] = bufs[j][i]
+            if st[j] == N.RS_OK:
+                objects[b] = outs[j]
+            else:
+                errors[b] = _decode_error(st[j])
+        return objects, errors
 
 
 # ---- reedsolomon.Encoder-level helpers over host shards -----------------------------

@@ -2,6 +2,8 @@
 
 package erasure
 
+import "fmt"
+
 // Builds without the GPU codec (the default CGO_ENABLED=0 release builds,
 // Dockerfile:20-22, builds.sh:8-20) keep the reference codec: after codec.go.diff its
 // methods are named cpuEncode / cpuDecode, and these two forward to them, so the binary
@@ -15,6 +17,32 @@ func (c *Codec) Encode(data []byte, profile ErasureProfile) ([][]byte, error) {
 // Decode reconstructs the original data from shards (nil entries are missing).
 func (c *Codec) Decode(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, error) {
 	return c.cpuDecode(shards, profile, originalSize)
+}
+
+// EncodeBatch is Encode per object on builds without the GPU codec (the GPU build runs the
+// whole batch as one call, codec_rocm.go).
+func (c *Codec) EncodeBatch(objs [][]byte, profile ErasureProfile) ([][][]byte, []error) {
+	out := make([][][]byte, len(objs))
+	errs := make([]error, len(objs))
+	for b, d := range objs {
+		out[b], errs[b] = c.cpuEncode(d, profile)
+	}
+	return out, errs
+}
+
+// DecodeBatch is Decode per object on builds without the GPU codec. sizes holds one
+// original size per object.
+func (c *Codec) DecodeBatch(shards [][][]byte, profile ErasureProfile, sizes []int64) ([][]byte, []error) {
+	out := make([][]byte, len(shards))
+	errs := make([]error, len(shards))
+	for b := range shards {
+		if len(sizes) != len(shards) {
+			errs[b] = fmt.Errorf("erasure: %d sizes for %d objects", len(sizes), len(shards))
+			continue
+		}
+		out[b], errs[b] = c.cpuDecode(shards[b], profile, sizes[b])
+	}
+	return out, errs
 }
 
 // The pinned-buffer helpers of the GPU build (codec_rocm.go) exist here too, so callers

@@ -436,6 +436,205 @@ func (c *Codec) RepairBatch(objs [][][]byte, profile ErasureProfile) []error {
 	return errs
 }
 
+// EncodeBatch is Encode for many objects of one profile in one call
+// (rs_codec_encode_batch: one pipeline over all of them, Split done on the way into its
+// staging; DESIGN.md §7.6), e.g. a server batching small uploads. out[b] holds object b's
+// n shards and errs[b] what Encode would report for it. An object whose capacity holds all
+// n shards (a BodyBuffer) is split in place as Encode splits it; any other object gets one
+// fresh buffer of n*S bytes that holds all its shards, so unlike upstream Split no shard
+// aliases objs[b]. The batch goes to the GPU whatever the objects' sizes (gpuMinBytes is
+// the single-object threshold). Not in the reference API: an addition for bulk callers.
+func (c *Codec) EncodeBatch(objs [][]byte, profile ErasureProfile) ([][][]byte, []error) {
+	k, m := profile.DataShards, profile.ParityShards
+	out := make([][][]byte, len(objs))
+	errs := make([]error, len(objs))
+	if k < 1 || m < 1 {
+		for b := range errs {
+			errs[b] = ErrInvalidProfile
+		}
+		return out, errs
+	}
+	if len(objs) == 0 {
+		return out, errs
+	}
+	n := k + m
+	if n > 256 || device() == nil {
+		for b, d := range objs {
+			out[b], errs[b] = c.cpuEncode(d, profile)
+		}
+		return out, errs
+	}
+	B := len(objs)
+	data, dst := newCArray(B), newCArray(B)
+	defer data.free()
+	defer dst.free()
+	lens := make([]C.size_t, B) // Go memory without Go pointers: may be passed
+	caps := make([]C.size_t, B)
+	sizes := make([]C.size_t, B)
+	status := make([]C.int, B)
+	bufs := make([][]byte, B)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for b, d := range objs {
+		lens[b] = C.size_t(len(d))
+		if len(d) == 0 {
+			continue // reports RS_E_SHORT_DATA, as upstream Split does
+		}
+		S := (len(d) + k - 1) / k
+		if cap(d) >= n*S {
+			bufs[b] = d[:n*S] // in place: the pad and the parity land in the spare capacity
+		} else {
+			bufs[b] = make([]byte, n*S)
+		}
+		caps[b] = C.size_t(n * S)
+		pin.Pin(&d[0])
+		pin.Pin(&bufs[b][0])
+		data.set(b, unsafe.Pointer(&d[0]))
+		dst.set(b, unsafe.Pointer(&bufs[b][0]))
+	}
+	rc := C.rs_codec_encode_batch(gpuCtx, C.int(k), C.int(m), C.int(B), data.at(0), &lens[0],
+		dst.at(0), &caps[0], &sizes[0], &status[0])
+	if rc != C.RS_OK && !hasStatus(status, rc) { // a call-level error: no status was written
+		for b := range errs {
+			errs[b] = fmt.Errorf("erasure: failed to encode parity: %w", upstreamErr(rc))
+		}
+		return out, errs
+	}
+	for b := range objs {
+		switch st := status[b]; st {
+		case C.RS_OK:
+			S := int(sizes[b])
+			out[b] = make([][]byte, n)
+			for i := range out[b] {
+				out[b][i] = bufs[b][i*S : (i+1)*S : (i+1)*S]
+			}
+		case C.RS_E_SHORT_DATA:
+			errs[b] = fmt.Errorf("erasure: failed to split data: %w", upstreamErr(st))
+		default:
+			errs[b] = fmt.Errorf("erasure: failed to encode parity: %w", upstreamErr(st))
+		}
+	}
+	return out, errs
+}
+
+// hasStatus: a batch call returns the first nonzero per-object status, so a return value no
+// object reports is a call-level error.
+func hasStatus(status []C.int, rc C.int) bool {
+	for _, st := range status {
+		if st == rc {
+			return true
+		}
+	}
+	return false
+}
+
+// DecodeBatch is Decode for many objects of one profile in one call
+// (rs_codec_decode_batch: Reconstruct, Verify and the join / trim of every object in one
+// pipeline). shards[b] is object b's n shards (nil or empty = missing), sizes[b] its
+// original size; out[b] is the object and errs[b] what Decode would report for it. Like
+// Decode, an object's missing entries are filled once its Reconstruct has run
+// (errs[b] nil, ErrShardCorrupted or ErrInsufficientShards) and left alone otherwise. Not in
+// the reference API: an addition for bulk callers.
+func (c *Codec) DecodeBatch(shards [][][]byte, profile ErasureProfile, sizes []int64) ([][]byte, []error) {
+	k, m := profile.DataShards, profile.ParityShards
+	out := make([][]byte, len(shards))
+	errs := make([]error, len(shards))
+	if k < 1 || m < 1 || len(sizes) != len(shards) {
+		for b := range errs {
+			errs[b] = ErrInvalidProfile
+			if k >= 1 && m >= 1 {
+				errs[b] = fmt.Errorf("erasure: %d sizes for %d objects", len(sizes), len(shards))
+			}
+		}
+		return out, errs
+	}
+	if len(shards) == 0 {
+		return out, errs
+	}
+	n := k + m
+	if n > 256 || device() == nil {
+		for b := range shards {
+			out[b], errs[b] = c.cpuDecode(shards[b], profile, sizes[b])
+		}
+		return out, errs
+	}
+	B := len(shards)
+	bufs := make([][][]byte, B)
+	ptrs, outs := newCArray(B*n), newCArray(B)
+	defer ptrs.free()
+	defer outs.free()
+	lens := make([]C.size_t, B*n) // Go memory without Go pointers: may be passed
+	osz := make([]C.int64_t, B)
+	status := make([]C.int, B)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for b, sh := range shards {
+		if len(sh) != n {
+			errs[b] = fmt.Errorf("erasure: reconstruction failed: %w", reedsolomon.ErrTooFewShards)
+			continue // all lens 0 and no pointers: the object reports RS_E_NO_DATA, ignored
+		}
+		S := 0
+		for _, s := range sh {
+			if len(s) > 0 {
+				S = len(s)
+				break
+			}
+		}
+		bufs[b] = make([][]byte, n)
+		copy(bufs[b], sh)
+		for i, s := range bufs[b] {
+			lens[b*n+i] = C.size_t(len(s))
+			if len(s) == 0 && S > 0 {
+				if cap(s) >= S {
+					s = s[:S]
+				} else {
+					s = make([]byte, S)
+				}
+				bufs[b][i] = s
+			}
+			if len(s) > 0 {
+				pin.Pin(&s[0])
+				ptrs.set(b*n+i, unsafe.Pointer(&s[0]))
+			}
+		}
+		osz[b] = C.int64_t(sizes[b])
+		if sizes[b] > 0 {
+			out[b] = make([]byte, sizes[b])
+			pin.Pin(&out[b][0])
+			outs.set(b, unsafe.Pointer(&out[b][0]))
+		}
+	}
+	rc := C.rs_codec_decode_batch(gpuCtx, C.int(k), C.int(m), C.int(B), ptrs.at(0), &lens[0],
+		outs.at(0), &osz[0], &status[0])
+	callLevel := rc != C.RS_OK && !hasStatus(status, rc) // no status was written
+	for b, sh := range shards {
+		if errs[b] != nil {
+			out[b] = nil
+			continue
+		}
+		st := status[b]
+		if callLevel {
+			st = rc
+		}
+		switch st {
+		case C.RS_OK, C.RS_E_CORRUPT, C.RS_E_INSUFFICIENT:
+			// Reconstruct ran: upstream has filled the nil entries by now (codec.go:55)
+			for i := range sh {
+				if len(sh[i]) == 0 {
+					sh[i] = bufs[b][i]
+				}
+			}
+		}
+		if st != C.RS_OK {
+			out[b] = nil
+		} else if out[b] == nil {
+			out[b] = []byte{} // an empty object, as Decode's buf[:0]
+		}
+		errs[b] = decodeErr(st)
+	}
+	return out, errs
+}
+
 // cpuRepair is RepairBatch's per-object CPU form: upstream Reconstruct + Verify.
 func cpuRepair(shards [][]byte, k, m int) error {
 	enc, err := reedsolomon.New(k, m)

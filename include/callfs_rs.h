@@ -149,6 +149,49 @@ int rs_encode_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes,
 int rs_reconstruct_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
                          size_t* lens, int verify, int* status);
 
+/* ---- Codec-level batches, host memory (many objects per call) -------------------------
+ * Not in the reference API: Codec.Encode / Codec.Decode (codec.go:21-78) for many objects
+ * of one profile at once, for a server batching small uploads or downloads. Objects go in
+ * and come out: Split (codec.go:31) happens on the way into the pipeline's staging and the
+ * join / trim (codec.go:67-77) on the way out of it, so no object is copied a second time,
+ * and every object gets the status the single-object call would return for it. The
+ * runnable objects run as the stripes of rs_encode_batch / rs_reconstruct_batch do: one
+ * uniform pipeline when they share one shard size and one presence mask, else one ragged
+ * pipeline (staged, one dispatch in place for at most CALLFS_RS_SMALL_MAX_BYTES, or launches
+ * on the caller's buffers when every buffer of every runnable object -- data, shards_out,
+ * shards and out -- is rs_host_alloc memory); CALLFS_RS_RAGGED_BATCH=0 runs one pipeline
+ * per (S, presence) group.
+ * rs_codec_encode_batch: object b is handled as rs_codec_encode(ctx, k, m, data[b],
+ *   lens[b], shards_out[b], out_caps[b], &shard_sizes[b]) handles it: n = k+m shards of
+ *   S_b = ceil(lens[b]/k) bytes back to back in shards_out[b], bytes [lens[b], k*S_b) zero.
+ *   status[b]: RS_OK; RS_E_SHORT_DATA for lens[b] == 0; RS_E_ARG for a NULL data[b] or
+ *   shards_out[b] or out_caps[b] < n*S_b (shard_sizes[b] is written for RS_OK alone).
+ *   shards_out[b] == data[b] (the object split in place) is allowed, and buffers of ONE
+ *   object that overlap partly are handled as rs_codec_encode handles them; buffers of
+ *   different objects must not overlap. No byte at or beyond shards_out[b] + n*S_b is
+ *   written.
+ * rs_codec_decode_batch: object b has shards[b*n + i] / lens[b*n + i] with
+ *   rs_codec_decode's contract (0 = missing; missing shards are rebuilt into their buffers
+ *   and their lens set to S when status[b] is RS_OK, RS_E_CORRUPT or RS_E_INSUFFICIENT, as
+ *   upstream Reconstruct has run by then); out[b] receives original_sizes[b] bytes. An
+ *   object with every shard present is still verified and joined. status[b], in this
+ *   order: RS_E_NO_DATA / RS_E_SHARD_SIZE (shard count / size checks), RS_E_TOO_FEW_SHARDS,
+ *   RS_E_ARG (a NULL shard buffer, a negative size, a NULL out[b] with a positive size),
+ *   RS_E_CORRUPT (Verify fails, for that object alone), RS_E_INSUFFICIENT
+ *   (k*S < original_sizes[b]). out[b] is unspecified unless status[b] is RS_OK and is never
+ *   written at or beyond original_sizes[b].
+ * Both: the profile errors (RS_E_INVALID_PROFILE, RS_E_UNSUPPORTED), a NULL array and
+ * batch < 0 (RS_E_ARG) are call-level, checked first, and leave status[] unspecified, as do
+ * RS_E_HIP / RS_E_NOMEM; batch == 0 returns RS_OK. Otherwise the call returns RS_OK or the
+ * first nonzero status in object order. */
+int rs_codec_encode_batch(rs_ctx* ctx, int k, int m, int batch,
+                          const uint8_t* const* data, const size_t* lens,
+                          uint8_t* const* shards_out, const size_t* out_caps,
+                          size_t* shard_sizes, int* status);
+int rs_codec_decode_batch(rs_ctx* ctx, int k, int m, int batch,
+                          uint8_t* const* shards, size_t* lens,
+                          uint8_t* const* out, const int64_t* original_sizes, int* status);
+
 /* ---- counters of the host-memory path -----------------------------------------------
  * Monotonic per-context counts (relaxed atomics; what an operator graphs, and what shows
  * that a batch cost one round trip):

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Times rs_encode_batch / rs_reconstruct_batch over heterogeneous host batches.
+"""Times rs_encode_batch / rs_reconstruct_batch over heterogeneous host batches
+and, with --codec, the codec-level batch calls against the routes they replace.
 
 Seeded, single-threaded workloads, each as an encode and as a reconstruct (one random lost
 shard per stripe, verify on), with pageable and with rs_host_alloc (pinned) buffers:
@@ -21,6 +22,15 @@ one call.
   python tools/host_batch_bench.py --lib parent=/tmp/parent/libcallfs_rs.so \\
       --lib new=callfs_amd/libcallfs_rs.so --lib new2=/tmp/copy_of_new.so --rounds 5
 
+`--codec` instead times the codec-level batch calls on the same workloads
+taken as objects: object length = k x the workload's shard size minus a seeded pad in [0, k),
+as an encode (objects in, n shards per object out, separate buffers) and as a decode with one
+seeded lost shard per object (shards in, objects out). A library that has
+rs_codec_encode_batch / rs_codec_decode_batch is timed through them (route "batch"); one that
+does not -- the parent commit's -- does the same job the two ways it can: route "a", a loop of
+rs_codec_encode / rs_codec_decode per object, and route "b", CPU Split + rs_encode_batch and
+rs_reconstruct_batch + CPU join (one copy per object each way, the cheapest a caller can do).
+
 `--crossover` instead times W3-like batches scaled from 64 KiB to 8 MiB of staging on one
 library; run it once with CALLFS_RS_SMALL_MAX_BYTES=0 (staged) and once with a large value (in
 place) to find where the two transports cross.
@@ -38,7 +48,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(os.path.dirname(HERE), "callfs_amd", "libcallfs_rs.so")
 
-_vp, _sz, _int = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+_vp, _sz, _int, _i64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64
 
 
 class Counters(ctypes.Structure):
@@ -58,6 +68,16 @@ class Lib:
             f = getattr(self.so, fn)
             f.argtypes = args
             f.restype = None if fn == "rs_shutdown" else _int
+        self.so.rs_codec_encode.argtypes = [_vp, _int, _int, _vp, _sz, _vp, _sz, ctypes.POINTER(_sz)]
+        self.so.rs_codec_decode.argtypes = [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _vp, _i64]
+        self.has_codec_batch = hasattr(self.so, "rs_codec_encode_batch")
+        if self.has_codec_batch:
+            self.so.rs_codec_encode_batch.argtypes = [
+                _vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp),
+                ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_int)]
+            self.so.rs_codec_decode_batch.argtypes = [
+                _vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp),
+                ctypes.POINTER(_i64), ctypes.POINTER(_int)]
         self.ctx = _vp()
         rc = self.so.rs_init(ctypes.byref(self.ctx), 1)  # one device
         if rc:
@@ -214,6 +234,167 @@ def run_workload(name, libs, rounds, out, seed):
             lib.free(base)
 
 
+class CodecBatch:
+    """One flat buffer: every object's bytes, then every object's n shards back to back (the
+    layout rs_codec_encode writes), then every joined object; regions and objects 64-B aligned."""
+
+    def __init__(self, k, m, shard_sizes, base, arr, seed):
+        rng = np.random.default_rng(seed + 7)
+        self.k, self.m, self.n, self.arr, self.base = k, m, k + m, arr, base
+        n, B = k + m, len(shard_sizes)
+        self.B, self.S = B, shard_sizes
+        self.L = [k * S - int(rng.integers(0, k)) if k * S > k else k * S for S in shard_sizes]
+        al = lambda x: (x + 63) // 64 * 64  # noqa: E731
+        self.d_off, self.s_off, self.o_off = [], [], []
+        at = 0
+        for L in self.L:
+            self.d_off.append(at)
+            at += al(L)
+        for S in shard_sizes:
+            self.s_off.append(at)
+            at += al(n * S)
+        for L in self.L:
+            self.o_off.append(at)
+            at += al(L)
+        self.total = at
+        self.lost = rng.integers(0, n, B)
+        self.data = (_vp * B)(*[base + o for o in self.d_off])
+        self.dst = (_vp * B)(*[base + o for o in self.s_off])
+        self.out = (_vp * B)(*[base + o for o in self.o_off])
+        self.clens = (_sz * B)(*self.L)
+        self.caps = (_sz * B)(*[n * S for S in shard_sizes])
+        self.csizes = (_sz * B)(*shard_sizes)
+        self.ss = (_sz * B)()
+        self.orig = (_i64 * B)(*self.L)
+        self.status = (_int * B)()
+        self.shards = (_vp * (B * n))(*[base + self.s_off[b] + i * shard_sizes[b] for b in range(B) for i in range(n)])
+        self.dptr = (_vp * (B * k))(*[base + self.s_off[b] + i * shard_sizes[b] for b in range(B) for i in range(k)])
+        self.pptr = (_vp * (B * m))(*[base + self.s_off[b] + (k + j) * shard_sizes[b] for b in range(B) for j in range(m)])
+        self.lens = (_sz * (B * n))()
+        self.lens0 = (_sz * (B * n))(*[0 if i == self.lost[b] else shard_sizes[b] for b in range(B) for i in range(n)])
+        # per-object views of lens and shard pointers for the single-object decode
+        psz, ssz = ctypes.sizeof(_vp), ctypes.sizeof(_sz)
+        self.sh_b = [ctypes.cast(ctypes.addressof(self.shards) + b * n * psz, ctypes.POINTER(_vp)) for b in range(B)]
+        self.ln_b = [ctypes.cast(ctypes.addressof(self.lens) + b * n * ssz, ctypes.POINTER(_sz)) for b in range(B)]
+        self.one = _sz()
+
+    @staticmethod
+    def nbytes(k, m, shard_sizes):
+        return sum(2 * (k * S + 64) + (k + m) * S + 64 for S in shard_sizes)
+
+    def prepare(self, leg):
+        if leg == "dec":
+            ctypes.memmove(self.lens, self.lens0, ctypes.sizeof(self.lens))
+
+    def run(self, lib, route, leg):
+        so, ctx, k, m, B, a = lib.so, lib.ctx, self.k, self.m, self.B, self.arr
+        if route == "batch":
+            if leg == "enc":
+                return so.rs_codec_encode_batch(ctx, k, m, B, self.data, self.clens, self.dst, self.caps, self.ss,
+                                                self.status)
+            return so.rs_codec_decode_batch(ctx, k, m, B, self.shards, self.lens, self.out, self.orig, self.status)
+        if route == "a":
+            rc = 0
+            if leg == "enc":
+                for b in range(B):
+                    rc |= so.rs_codec_encode(ctx, k, m, self.data[b], self.L[b], self.dst[b], self.caps[b],
+                                             ctypes.byref(self.one))
+            else:
+                for b in range(B):
+                    rc |= so.rs_codec_decode(ctx, k, m, self.sh_b[b], self.ln_b[b], self.out[b], self.L[b])
+            return rc
+        if leg == "enc":  # route b: upstream Split on the CPU (copy the body, zero the pad), then the shard batch
+            for L, S, d, s in zip(self.L, self.S, self.d_off, self.s_off):
+                a[s:s + L] = a[d:d + L]
+                a[s + L:s + k * S] = 0
+            return so.rs_encode_batch(ctx, k, m, B, self.csizes, self.dptr, self.pptr, self.status)
+        rc = so.rs_reconstruct_batch(ctx, k, m, B, self.shards, self.lens, 1, self.status)
+        for L, s, o in zip(self.L, self.s_off, self.o_off):  # join + trim: the data shards lie end to end
+            a[o:o + L] = a[s:s + L]
+        return rc
+
+    def joined_ok(self):
+        return all(np.array_equal(self.arr[o:o + L], self.arr[d:d + L])
+                   for L, d, o in zip(self.L, self.d_off, self.o_off))
+
+
+def time_codec(batch, lib, route, leg, reps):
+    all_dt = []
+    for _ in range(reps):
+        batch.prepare(leg)
+        t0 = time.perf_counter()
+        rc = batch.run(lib, route, leg)
+        dt = time.perf_counter() - t0
+        if rc:
+            raise RuntimeError(f"{lib.name} {route} {leg}: rc={rc}")
+        all_dt.append(dt)
+    return min(all_dt) if reps <= 3 else statistics.median(all_dt)
+
+
+def run_codec_workload(name, libs, rounds, out, seed):
+    rng = np.random.default_rng(seed)
+    k, m, sizes = workload(name, rng)
+    total = CodecBatch.nbytes(k, m, sizes)
+    reps = 200 if total < (16 << 20) else 2
+    runs = [(lib, r) for lib in libs for r in (("batch",) if lib.has_codec_batch else ("a", "b"))]
+    for mem in ("pageable", "pinned"):
+        batches, frees = {}, []
+        for lib in libs:
+            if mem == "pageable" and batches:
+                batches[lib.name] = next(iter(batches.values()))
+                continue
+            if mem == "pageable":
+                arr = np.empty(total + 64, np.uint8)
+                base = (arr.ctypes.data + 63) // 64 * 64
+                arr = arr[base - arr.ctypes.data:][:total]
+            else:
+                try:
+                    base, arr = lib.pinned(total)
+                except RuntimeError as e:  # e.g. a locked-memory limit: say so, go on
+                    out.write(json.dumps({"workload": name, "memory": mem, "skipped": str(e)}) + "\n")
+                    print(f"{name} pinned skipped: {e}", flush=True)
+                    for lb, bs in frees:
+                        lb.free(bs)
+                    return
+                frees.append((lib, base))
+            b = CodecBatch(k, m, sizes, base, arr, seed)
+            fill_random(arr[:b.s_off[0]], np.random.default_rng(seed + 1))
+            batches[lib.name] = b
+        for leg in ("enc", "dec"):
+            times = {(lib.name, r): [] for lib, r in runs}
+            counters = {}
+            for lib, r in runs:  # warm-up: allocations, tables; the encode also makes the shards valid
+                b = batches[lib.name]
+                b.prepare("enc")
+                b.run(lib, r, "enc")
+                time_codec(b, lib, r, leg, 1)
+                c0 = lib.counters()
+                time_codec(b, lib, r, leg, 1)
+                c1 = lib.counters()
+                counters[lib.name, r] = c0 and {key: c1[key] - c0[key] for key in c0}
+                if leg == "dec" and not b.joined_ok():
+                    raise RuntimeError(f"{name} {mem} {lib.name} {r}: joined objects differ from the inputs")
+            for _ in range(rounds):
+                for lib, r in runs:
+                    times[lib.name, r].append(time_codec(batches[lib.name], lib, r, leg, reps))
+            obj_bytes = sum(batches[libs[0].name].L)
+            for lib, r in runs:
+                t = times[lib.name, r]
+                line = {"workload": name, "k": k, "m": m, "objects": len(sizes), "object_bytes": obj_bytes,
+                        "leg": "codec_" + leg, "memory": mem, "lib": lib.name, "route": r, "reps_per_round": reps,
+                        "seconds": [round(x, 7) for x in t], "median_s": statistics.median(t),
+                        "us_per_call": round(statistics.median(t) * 1e6, 1),
+                        "gib_per_s": round(obj_bytes / statistics.median(t) / 2**30, 2),
+                        "counters_per_call": counters[lib.name, r]}
+                out.write(json.dumps(line) + "\n")
+                out.flush()
+                print(json.dumps({key: line[key] for key in ("workload", "leg", "memory", "lib", "route",
+                                                             "us_per_call", "gib_per_s", "counters_per_call")}),
+                      flush=True)
+        for lib, base in frees:
+            lib.free(base)
+
+
 def run_crossover(lib, rounds, out, seed):
     """W3-like batches scaled to 64 KiB .. 8 MiB of total staging, pageable."""
     for target in (64 << 10, 128 << 10, 256 << 10, 512 << 10, 1 << 20, 2 << 20, 4 << 20, 8 << 20):
@@ -252,6 +433,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0x5EED)
     ap.add_argument("--out", default="host_batch.jsonl")
     ap.add_argument("--crossover", action="store_true")
+    ap.add_argument("--codec", action="store_true", help="the codec-level batch calls (objects in / out)")
     a = ap.parse_args()
     specs = a.lib or [f"current={DEFAULT_LIB}"]
     libs = [Lib(*s.split("=", 1)) for s in specs]
@@ -261,7 +443,7 @@ def main():
             run_crossover(libs[0], a.rounds, out, a.seed)
         else:
             for w in a.workloads.split(","):
-                run_workload(w, libs, a.rounds, out, a.seed)
+                (run_codec_workload if a.codec else run_workload)(w, libs, a.rounds, out, a.seed)
     return 0
 
 

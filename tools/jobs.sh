@@ -432,6 +432,25 @@ cd "$(dirname "$JOBS")/.." || exit $?
 timeout -k 10 400 python3 -u tools/ragged_bench.py "$@" || exit $?
 }
 
+# The codec-level batch calls against the routes they replace (tools/host_batch_bench.py --codec,
+# DESIGN.md §7.6): workloads W0-W3 as objects, encode and decode, pageable and pinned buffers.
+# PARENT_LIB: the parent commit's libcallfs_rs.so (timed as a loop of single-object calls and as
+# CPU Split / join around the shard-level batch calls); the current build is loaded twice, the
+# second time from a copy, for the spread. Output: <out dir>/codec_batch.jsonl (the lines kept
+# in profiles/r12/codec_batch/).
+# Usage: PARENT_LIB=<path> bash tools/jobs.sh codec_batch_bench <out dir> [workloads, e.g. W2,W3]
+job_codec_batch_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+O=${1:-codec_batch_out}; mkdir -p "$O" || exit $?
+[ -f "$PARENT_LIB" ] || { echo "PARENT_LIB must name the parent commit's libcallfs_rs.so" >&2; exit 2; }
+cp callfs_amd/libcallfs_rs.so $O/libcallfs_rs_copy.so || exit $?
+timeout -k 10 1100 python3 -u tools/host_batch_bench.py --codec --rounds 5 --workloads "${2:-W0,W1,W2,W3}" \
+  --lib parent="$PARENT_LIB" --lib new=callfs_amd/libcallfs_rs.so --lib new2=$O/libcallfs_rs_copy.so \
+  --out $O/codec_batch.jsonl > $O/codec_batch.log 2>&1; rc=$?
+rm -f $O/libcallfs_rs_copy.so
+tail -40 $O/codec_batch.log; exit $rc
+}
+
 # configs[1]/[2] shape in the layouts upstream produces: bench.py at S = 6,710,887 with the
 # io.ReadAll Split layout (decode into fresh buffers, as Reconstruct allocates them, and in
 # place) and the planar layout; plus the bench shape. Usage: bash tools/jobs.sh readall_bench <tag>
