@@ -28,7 +28,9 @@ LIB_AB = os.path.join(os.path.dirname(HERE), "build", "ab", "libcallfs_rs_ab.so"
 RESOURCES = os.path.join(HERE, "kernel_resources.json")
 SOURCES = ["rs_kernels.hip", "rs_mixed.hip", "sha256.hip", "rs_context.cpp", "rs_host.cpp", "rs_plan.cpp",
            "bitslice.cpp"]
-HEADERS = ["bitslice.hpp", "bitslice_gen.hpp", "bitslice_rule.hpp", "tune_table.hpp", "rs_kernels.hpp", "order_code.hpp", "rs_apply.hpp", "tile_order.hpp", "gf256.hpp", "mixed_tables.hpp", "ragged_tables.hpp", "ragged_chunks.hpp", "copy_pool.hpp", "dispatch.hpp", "host_path.hpp", "launch_util.hpp", "rs_internal.hpp", "sha256.hpp", os.path.join("..", "..", "include", "callfs_rs.h")]
+# every header in csrc/ (a new one cannot be forgotten) and the C ABI's
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [
+    os.path.join("..", "..", "include", "callfs_rs.h")]
 ARCH = os.environ.get("CALLFS_OFFLOAD_ARCH", "gfx950")
 
 

@@ -1,9 +1,10 @@
 // The HIP-free parts of the host-memory path and of the plans' buffer layout: the registry
 // and pool of rs_host_alloc buffers, the chunk geometry of the pipeline, the join / tee
-// targets, the argument checks and the stripe grouping of the batch calls, and the 256-byte
-// packer of device buffers. Plain C++ with no HIP dependence, so tests/native/host_test.cpp
-// checks it on the CPU under ASan+UBSan and TSan; rs_context.cpp, rs_host.cpp and
-// rs_plan.cpp are the product users.
+// targets, the argument checks and the admission of a reconstruct stripe, the stripe grouping
+// and the routing of the batch calls, and the 256-byte packer of device buffers. Plain C++
+// with no HIP dependence, so tests/native/host_test.cpp checks it on the CPU under ASan+UBSan
+// and TSan; rs_context.cpp, rs_host.cpp (with its host_*.hpp) and rs_plan.cpp are the product
+// users.
 #pragma once
 
 #include <algorithm>
@@ -211,7 +212,6 @@ struct Join {
   size_t len;
   size_t S;  // full shard size (a column part's offset is added per part)
   int k;
-  bool done = false;  // set when the pipeline wrote every join byte
 };
 
 // Tee target for shard i's columns [col, col+w) or {nullptr, 0}.
@@ -241,13 +241,44 @@ inline int check_lens(int n, const size_t* lens, bool nilok, size_t* S, int* npr
   return RS_OK;
 }
 
+// Whether one stripe of a reconstruct (n shards, k of them data) is to run. In upstream's
+// order: check_lens' status, RS_E_TOO_FEW_SHARDS below k present shards, nothing to do (run
+// false, status RS_OK) when every shard is present and skip_complete (a reconstruct without
+// verify), RS_E_ARG for a NULL shard. Only a stripe to run has its n flags written to `present`.
+struct StripeAdmission {
+  int status = RS_OK;  // the stripe's own when it does not run
+  bool run = false;
+  size_t S = 0;
+};
+inline StripeAdmission admit_stripe(int n, int k, const uint8_t* const* shards, const size_t* lens,
+                                    bool skip_complete, uint8_t* present) {
+  StripeAdmission a;
+  int np = 0;
+  if ((a.status = check_lens(n, lens, true, &a.S, &np))) return a;
+  if (np < k) {
+    a.status = RS_E_TOO_FEW_SHARDS;
+    return a;
+  }
+  if (np == n && skip_complete) return a;
+  for (int i = 0; i < n; ++i)
+    if (!shards[i]) {
+      a.status = RS_E_ARG;
+      return a;
+    }
+  for (int i = 0; i < n; ++i) present[i] = lens[i] != 0;
+  a.run = true;
+  return a;
+}
+
 // Stripes grouped by (S, presence): each group shares one table set and one pipeline.
 struct BatchGroups {
   std::map<std::string, std::vector<int>> by_key;
+  std::vector<int> stripes;  // every stripe added, in the order of the calls
   void add(size_t S, const uint8_t* present, int n, int b) {
     std::string key(reinterpret_cast<const char*>(&S), sizeof S);
     key.append(reinterpret_cast<const char*>(present), n);
     by_key[key].push_back(b);
+    stripes.push_back(b);
   }
   static size_t shard_size(const std::string& key) {
     size_t S;
@@ -258,5 +289,27 @@ struct BatchGroups {
     return reinterpret_cast<const uint8_t*>(key.data() + sizeof(size_t));
   }
 };
+
+// How a batch call's runnable stripes reach the GPU. Two or more groups, with the ragged
+// pipeline allowed: one ragged run over `ids`, every runnable stripe in ascending call order.
+// Otherwise one uniform pipeline per entry of `groups`, in by_key's order (none when the call
+// has nothing to run).
+struct BatchRoute {
+  bool ragged = false;
+  std::vector<int> ids;
+  std::vector<const std::pair<const std::string, std::vector<int>>*> groups;
+};
+inline BatchRoute batch_route(const BatchGroups& g, bool ragged_allowed) {
+  BatchRoute r;
+  r.ragged = g.by_key.size() >= 2 && ragged_allowed;
+  if (r.ragged) {
+    // the callers add their stripes in ascending order: then this is a copy, not a sort
+    r.ids = g.stripes;
+    if (!std::is_sorted(r.ids.begin(), r.ids.end())) std::sort(r.ids.begin(), r.ids.end());
+  } else {
+    for (const auto& kv : g.by_key) r.groups.push_back(&kv);
+  }
+  return r;
+}
 
 }  // namespace callfs

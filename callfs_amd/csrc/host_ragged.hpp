@@ -1,0 +1,472 @@
+// The ragged pipeline of the host-memory path: a batch call whose runnable
+// stripes differ in shard size or erasure pattern runs as one pipeline over items
+// (ragged_chunks.hpp) instead of one uniform pipeline per (S, mask) group. It owns the runs of
+// a call (RaggedRun), their pattern tables on a lane, the staged, in-place and direct
+// transports, the chunk loop over a lane's slots (run_ragged_chunks) and run_ragged, which
+// picks the device and the lane. Included by rs_host.cpp only.
+#pragma once
+
+#include "host_common.hpp"
+#include "ragged_chunks.hpp"
+
+namespace callfs {
+namespace {
+
+// One ragged run: consecutive stripes of one class (ragged_classes) and segment
+// (ragged_segments) with their pattern tables. Stripe s of the run is stripe ids[s] of the
+// call's runnable list.
+struct RaggedRun {
+  rs_ctx* ctx;
+  int k, m;
+  MixedTables mt;
+  RaggedShape sh;
+  std::vector<int> ids;
+  const Join* joins;  // nullable: one per runnable stripe of the call (codec-level batches)
+  const Join* join_of(int id) const { return joins ? joins + id : nullptr; }
+  const MixedPattern& pattern(int s) const { return mt.patterns[mt.pat[static_cast<size_t>(s)]]; }
+  void count(size_t chunks, size_t copies) const {
+    ctx->n_chunks.fetch_add(chunks, std::memory_order_relaxed);
+    ctx->n_launches.fetch_add(chunks * mt.groups.size(), std::memory_order_relaxed);
+    ctx->n_copies.fetch_add(copies, std::memory_order_relaxed);
+  }
+};
+
+// What a lane's table cache is keyed by: the profile, the rows per pattern and the patterns.
+std::string ragged_key(const RaggedRun& r) {
+  std::string key = std::to_string(r.k) + "," + std::to_string(r.m) + "," + std::to_string(r.mt.rows) + ":";
+  for (const MixedPattern& p : r.mt.patterns) key.append(reinterpret_cast<const char*>(p.mask.data()), p.mask.size());
+  return key;
+}
+
+// The run's nibble-table arenas and compare masks in the lane's device buffer, per launch
+// group [vmask][arena]; uploaded when the lane last held another run's.
+struct RaggedDevTables {
+  std::vector<size_t> vmask_off, arena_off;
+};
+int upload_ragged_tables(const RaggedRun& r, Lane& L, RaggedDevTables& dt) {
+  Packer pk;
+  for (const MixedGroup& g : r.mt.groups) {
+    dt.vmask_off.push_back(pk.take(sizeof(uint32_t) * g.vmask.size()));
+    dt.arena_off.push_back(pk.take(g.arena.size()));
+  }
+  std::string key = ragged_key(r);
+  if (L.rag_tabs.p && L.rag_key == key) return RS_OK;
+  L.rag_key.clear();
+  if (const int rc = L.rag_tabs.ensure(pk.off)) return rc;
+  std::vector<uint8_t> h(pk.off, 0);
+  for (size_t gi = 0; gi < r.mt.groups.size(); ++gi) {
+    const MixedGroup& g = r.mt.groups[gi];
+    std::memcpy(h.data() + dt.vmask_off[gi], g.vmask.data(), sizeof(uint32_t) * g.vmask.size());
+    std::memcpy(h.data() + dt.arena_off[gi], g.arena.data(), g.arena.size());
+  }
+  HIPCHK(hipMemcpy(L.rag_tabs.p, h.data(), h.size(), hipMemcpyHostToDevice));
+  r.ctx->n_copies.fetch_add(1, std::memory_order_relaxed);
+  L.rag_key = std::move(key);
+  return RS_OK;
+}
+
+// launch_ragged of every launch group over the chunk laid out by C at `base` (device-visible).
+hipError_t launch_ragged_chunk(const RaggedRun& r, const ChunkLayout& C, uint8_t* base,
+                               const uint8_t* tabs, const RaggedDevTables& dt, hipStream_t s) {
+  for (size_t gi = 0; gi < r.mt.groups.size(); ++gi) {
+    const MixedGroup& g = r.mt.groups[gi];
+    ApplyArgs a{};
+    a.in_tab = reinterpret_cast<const uint8_t* const*>(base + C.in_tab_off);
+    a.out_tab = reinterpret_cast<uint8_t* const*>(base + C.out_tab_off[gi]);
+    a.ltabs = tabs + dt.arena_off[gi];
+    a.status = reinterpret_cast<int*>(base + C.status_off);
+    a.status_stride = 1;
+    a.K = r.k;
+    a.R = g.R;
+    a.batch = static_cast<int>(C.count);
+    RaggedArgs x{};
+    x.pat = reinterpret_cast<const uint32_t*>(base + C.pat_off);
+    x.vmask = reinterpret_cast<const uint32_t*>(tabs + dt.vmask_off[gi]);
+    x.size = reinterpret_cast<const uint64_t*>(base + C.size_off);
+    x.tile0 = reinterpret_cast<const uint32_t*>(base + C.tile0_off);
+    x.tile_stripe = reinterpret_cast<const uint32_t*>(base + C.tile_stripe_off);
+    x.tab_stride = static_cast<uint32_t>(g.tab_stride);
+    x.ntiles = C.ntiles;
+    const hipError_t e = launch_ragged(a, x, C.any_tail, s);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// Staged: one H2D of the chunk's input region (through the zeroed status words that open the
+// output region), launch_ragged per launch group on the slot's device mirror, one D2H of the
+// output region, then the slot's event.
+struct RaggedStaged {
+  const RaggedRun& r;
+  Lane& L;
+  RaggedDevTables dt;
+  int prepare_run() { return upload_ragged_tables(r, L, dt); }
+  int prepare(Slot& sl, size_t bytes) {
+    if (const int rc = sl.dev.ensure(bytes)) return rc;
+    return sl.host.ensure(bytes);
+  }
+  uint8_t* staging(Slot& sl) const { return static_cast<uint8_t*>(sl.host.p); }
+  uint8_t* base(Slot& sl) const { return static_cast<uint8_t*>(sl.dev.p); }
+  int send(Slot& sl, const ChunkLayout& C) const {
+    uint8_t* h = staging(sl);
+    uint8_t* d = base(sl);
+    const size_t head = C.status_off + sizeof(int) * C.count;
+    HIPCHK(hipMemcpyAsync(d, h, head, hipMemcpyHostToDevice, sl.stream));
+    HIPCHK(launch_ragged_chunk(r, C, d, static_cast<const uint8_t*>(L.rag_tabs.p), dt, sl.stream));
+    HIPCHK(hipMemcpyAsync(h + C.status_off, d + C.status_off, C.out_end - C.status_off,
+                          hipMemcpyDeviceToHost, sl.stream));
+    HIPCHK(hipEventRecord(sl.done, sl.stream));
+    r.count(1, 2);
+    return RS_OK;
+  }
+  int wait(Slot& sl) const {
+    HIPCHK(hipEventSynchronize(sl.done));
+    return RS_OK;
+  }
+};
+
+// In place: rs_apply_small_ragged on host-coherent staging, one dispatch per launch group;
+// the host spins on the completion flag the last group releases (host_common.hpp). The
+// pattern blocks ({compare mask, missing count}, v_perm tables; rs_kernels.hpp
+// SmallRaggedArgs) live in the lane's device buffer, keyed like the arenas.
+struct RaggedInplace {
+  const RaggedRun& r;
+  Lane& L;
+  std::vector<size_t> tab_off;   // per launch group, bytes
+  std::vector<uint32_t> pstride;  // per launch group, dwords
+  size_t done_off = 0;
+
+  int prepare_run() {
+    const size_t P = r.mt.patterns.size();
+    Packer pk;
+    for (const MixedGroup& g : r.mt.groups) {
+      pstride.push_back(4u + static_cast<uint32_t>(r.k) * g.R * kTabWords);
+      tab_off.push_back(pk.take(sizeof(uint32_t) * pstride.back() * P));
+    }
+    std::string key = ragged_key(r);
+    if (L.rag_small_tabs.p && L.rag_small_key == key) return RS_OK;
+    L.rag_small_key.clear();
+    if (const int rc = L.rag_small_tabs.ensure(pk.off)) return rc;
+    std::vector<uint8_t> h(pk.off, 0);
+    for (size_t gi = 0; gi < r.mt.groups.size(); ++gi) {
+      const MixedGroup& g = r.mt.groups[gi];
+      const size_t W = static_cast<size_t>(nibble_width(g.R));
+      for (size_t p = 0; p < P; ++p) {
+        auto* blk = reinterpret_cast<uint32_t*>(h.data() + tab_off[gi]) + p * pstride[gi];
+        blk[0] = g.vmask[p];
+        blk[1] = static_cast<uint32_t>(r.mt.patterns[p].missing);
+        for (int i = 0; i < r.k; ++i)
+          for (int row = 0; row < g.R; ++row) {
+            // the coefficient is entry 1 of the low nibble table: c * 1
+            const uint8_t c = g.arena[p * g.tab_stride + static_cast<size_t>(i) * 32u * W + W + row];
+            perm_tables(c, blk + 4 + (static_cast<size_t>(i) * g.R + row) * kTabWords);
+          }
+      }
+    }
+    HIPCHK(hipMemcpy(L.rag_small_tabs.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    r.ctx->n_copies.fetch_add(1, std::memory_order_relaxed);
+    L.rag_small_key = std::move(key);
+    return RS_OK;
+  }
+  int prepare(Slot& sl, size_t bytes) {
+    done_off = round_up(bytes, 256);
+    return done_flag_ensure(sl, done_off);
+  }
+  uint8_t* staging(Slot& sl) const { return static_cast<uint8_t*>(sl.small.p); }
+  uint8_t* base(Slot& sl) const { return staging(sl); }
+  int send(Slot& sl, const ChunkLayout& C) const {
+    uint8_t* b = staging(sl);
+    int* done = done_flag_arm(sl, done_off);
+    uint32_t max_nvec = 1;
+    for (const ItemLayout& it : C.items) max_nvec = std::max(max_nvec, static_cast<uint32_t>(it.pitch / 16));
+    for (size_t gi = 0; gi < r.mt.groups.size(); ++gi) {
+      const MixedGroup& g = r.mt.groups[gi];
+      SmallRaggedArgs A{};
+      A.base = b;
+      A.items = reinterpret_cast<const uint32_t*>(b + C.item_tab_off);
+      A.ptabs = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(L.rag_small_tabs.p) + tab_off[gi]);
+      A.pstride = pstride[gi];
+      A.max_nvec = max_nvec;
+      A.K = r.k;
+      A.R = g.R;
+      A.row0 = g.row0;
+      A.nitems = static_cast<int>(C.count);
+      A.status = reinterpret_cast<int*>(b + C.status_off);
+      A.done = gi + 1 == r.mt.groups.size() ? done : nullptr;
+      A.counter = static_cast<unsigned*>(sl.small_counter.p);
+      A.seq = sl.small_seq;
+      HIPCHK(launch_small_ragged(A, sl.stream));
+    }
+    r.count(1, 0);
+    return RS_OK;
+  }
+  int wait(Slot& sl) const { return done_flag_wait(sl, done_off); }
+  // what the kernel's 32-bit item table can address
+  static bool fits(const ChunkLayout& C) {
+    if (C.out_end >= (1ull << 35) || C.count > kRaggedMaxItems) return false;
+    for (const ItemLayout& it : C.items)
+      if (it.pitch > 0xFFFFFFF0u) return false;
+    return true;
+  }
+};
+
+// The chunk loop of a ragged run, in the style of run_chunks: chunks rotate through the
+// lane's slots; per chunk the metadata is written and the input rows are copied into the
+// slot's staging, the transport sends it, and the output rows of the chunk the slot held
+// before are copied out first. in / out take a stripe of the call's runnable
+// list and a shard index; flags (per runnable stripe) receive 1 where a compared row
+// mismatched.
+template <class Transport, class InF, class OutF>
+int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>& items,
+                      const std::vector<ChunkLayout>& chunks, Transport& tr, InF& in, OutF& out,
+                      int* flags) {
+  int rc;
+  if ((rc = tr.prepare_run())) return rc;
+  size_t bytes = 0;
+  for (const ChunkLayout& C : chunks) bytes = std::max(bytes, C.out_end);
+  const size_t nchunks = chunks.size();
+  const size_t nslots = std::min<size_t>(nchunks, static_cast<size_t>(pipeline_slots()));
+  for (size_t si = 0; si < nslots; ++si) {
+    if ((rc = tr.prepare(L.slot[si], bytes))) return rc;
+    L.slot[si].pending = false;
+  }
+  const size_t k = static_cast<size_t>(r.k);
+  std::vector<CopyPool::Seg> segs;
+  auto drain = [&](Slot& sl) -> int {
+    if (!sl.pending) return RS_OK;
+    const int wrc = tr.wait(sl);
+    if (wrc) return wrc;
+    const ChunkLayout& C = chunks[sl.rag_chunk];
+    uint8_t* h = tr.staging(sl);
+    const int* st = reinterpret_cast<const int*>(h + C.status_off);
+    for (size_t j = 0; j < C.count; ++j) {
+      const RaggedItem& it = items[C.first + j];
+      const int id = r.ids[static_cast<size_t>(it.stripe)];
+      if (st[j]) flags[id] = 1;
+      const MixedPattern& pt = r.pattern(it.stripe);
+      for (int row = 0; row < pt.missing; ++row) {
+        const int i = pt.rows[static_cast<size_t>(row)];
+        const auto tee = join_span(r.join_of(id), i, it.off, it.w);
+        segs.push_back({out(id, i) + it.off,
+                        h + C.items[j].out_off + C.items[j].pitch * static_cast<size_t>(row), it.w,
+                        tee.first, tee.second});
+      }
+    }
+    sl.pending = false;
+    return RS_OK;
+  };
+  for (size_t c = 0; c < nchunks; ++c) {
+    Slot& sl = L.slot[c % nslots];
+    segs.clear();
+    if ((rc = drain(sl))) return rc;
+    // the last chunk's output rows leave before this chunk's layout overwrites them (chunks
+    // of one run are laid out differently: its inputs may lie where those outputs were)
+    if (!segs.empty()) r.ctx->pool.run(segs);
+    segs.clear();
+    const ChunkLayout& C = chunks[c];
+    uint8_t* h = tr.staging(sl);
+    uint8_t* b = tr.base(sl);
+    // a row's address by the pattern's row number: written rows in the output part, compared
+    // ones behind the k inputs
+    auto row_at = [&](uint8_t* at, size_t j, int row) {
+      const ItemLayout& il = C.items[j];
+      const int missing = r.pattern(items[C.first + j].stripe).missing;
+      return row < missing ? at + il.out_off + il.pitch * static_cast<size_t>(row)
+                           : at + il.in_off + il.pitch * (k + static_cast<size_t>(row - missing));
+    };
+    fill_chunk_meta(C, r.sh, items, r.mt, r.mt.pat.data(), h,
+                    [&](size_t j, int i) { return b + C.items[j].in_off + C.items[j].pitch * static_cast<size_t>(i); },
+                    [&](size_t j, int row) { return row_at(b, j, row); });
+    for (size_t j = 0; j < C.count; ++j) {
+      const RaggedItem& it = items[C.first + j];
+      const int id = r.ids[static_cast<size_t>(it.stripe)];
+      const MixedPattern& pt = r.pattern(it.stripe);
+      for (size_t i = 0; i < k; ++i) {
+        const auto tee = join_span(r.join_of(id), pt.valid[i], it.off, it.w);
+        segs.push_back({h + C.items[j].in_off + C.items[j].pitch * i, in(id, pt.valid[i]) + it.off, it.w,
+                        tee.first, tee.second});
+      }
+      for (size_t row = static_cast<size_t>(pt.missing); row < pt.rows.size(); ++row)
+        segs.push_back({row_at(h, j, static_cast<int>(row)), in(id, pt.rows[row]) + it.off, it.w});
+    }
+    r.ctx->pool.run(segs);
+    if ((rc = tr.send(sl, C))) return rc;
+    sl.pending = true;
+    sl.rag_chunk = c;
+  }
+  for (size_t c = nchunks - nslots; c < nchunks; ++c) {
+    segs.clear();
+    if ((rc = drain(L.slot[c % nslots]))) return rc;
+    r.ctx->pool.run(segs);
+  }
+  return RS_OK;
+}
+
+// Direct: every buffer of the run lies in rs_host_alloc memory. One metadata upload (the
+// pointer tables name the caller's buffers), launch_ragged per launch group, the status
+// words back, then a sync. No staging copies and no chunking; a codec-level batch's tees and
+// joins are copy-pool work on the caller's bytes (present shards while the kernels run,
+// rebuilt ones once they have landed), as in run_direct.
+template <class InF, class OutF>
+int run_ragged_direct(const RaggedRun& r, Lane& L, InF& in, OutF& out, int* flags) {
+  std::vector<RaggedItem> items;
+  uint64_t ntiles = 0;
+  for (int s = 0; s < r.sh.stripes(); ++s) {
+    items.push_back({s, 0, r.sh.size[static_cast<size_t>(s)]});
+    ntiles += ragged_tiles(items.back().w);
+  }
+  if (ntiles > kRaggedMaxTiles) return RS_E_ARG;
+  const ChunkLayout C = layout_chunk(r.sh, items, 0, items.size(), false);
+  RaggedStaged tabs{r, L, {}};
+  int rc;
+  if ((rc = tabs.prepare_run())) return rc;
+  Slot& sl = L.slot[0];
+  if ((rc = sl.meta.ensure(C.out_end)) || (rc = sl.hmeta.ensure(C.out_end)) ||
+      (rc = sl.hstat.ensure(sizeof(int) * C.count)))
+    return rc;
+  sl.meta_tables = nullptr;  // the uniform staged path refills its tables next time
+  auto* h = static_cast<uint8_t*>(sl.hmeta.p);
+  auto* d = static_cast<uint8_t*>(sl.meta.p);
+  bool compares = false;
+  auto shard = [&](size_t j, int i) -> uint8_t* {
+    const int id = r.ids[j];
+    const MixedPattern& pt = r.pattern(static_cast<int>(j));
+    for (int row = 0; row < pt.missing; ++row)
+      if (pt.rows[static_cast<size_t>(row)] == i) return out(id, i);
+    return const_cast<uint8_t*>(in(id, i));
+  };
+  for (int s = 0; s < r.sh.stripes(); ++s) compares |= r.pattern(s).missing < r.mt.rows;
+  fill_chunk_meta(C, r.sh, items, r.mt, r.mt.pat.data(), h,
+                  [&](size_t j, int i) { return shard(j, r.pattern(static_cast<int>(j)).valid[static_cast<size_t>(i)]); },
+                  [&](size_t j, int row) { return shard(j, r.pattern(static_cast<int>(j)).rows[static_cast<size_t>(row)]); });
+  HIPCHK(hipMemcpyAsync(d, h, C.out_end, hipMemcpyHostToDevice, sl.stream));
+  HIPCHK(launch_ragged_chunk(r, C, d, static_cast<const uint8_t*>(L.rag_tabs.p), tabs.dt, sl.stream));
+  if (compares)
+    HIPCHK(hipMemcpyAsync(sl.hstat.p, d + C.status_off, sizeof(int) * C.count, hipMemcpyDeviceToHost,
+                          sl.stream));
+  HIPCHK(hipEventRecord(sl.done, sl.stream));
+  r.count(1, compares ? 2 : 1);
+  std::vector<CopyPool::Seg> present, rebuilt;
+  for (size_t j = 0; r.joins && j < C.count; ++j) {
+    const int id = r.ids[j];
+    const MixedPattern& pt = r.pattern(static_cast<int>(j));
+    const size_t S = r.sh.size[j];
+    for (int i : pt.valid) {
+      const auto js = join_span(r.join_of(id), i, 0, S);
+      if (js.first) present.push_back({js.first, in(id, i), js.second});
+    }
+    for (int row = 0; row < pt.missing; ++row) {
+      const int i = pt.rows[static_cast<size_t>(row)];
+      const auto js = join_span(r.join_of(id), i, 0, S);
+      if (js.first) rebuilt.push_back({js.first, out(id, i), js.second});
+    }
+  }
+  if ((rc = join_around_launch(r.ctx, sl, present, rebuilt))) return rc;
+  if (compares) {
+    const int* st = static_cast<const int*>(sl.hstat.p);
+    for (size_t j = 0; j < C.count; ++j)
+      if (st[j]) flags[r.ids[j]] = 1;
+  }
+  return RS_OK;
+}
+
+// A heterogeneous batch call on one device and lane. The call's runnable stripes are listed
+// by S[j] and present[j * n ..]; in(j, i) / out(j, i) give runnable stripe j's shard i.
+// by_missing: a reconstruct without verification, whose stripes run in classes by missing
+// count (a pattern's rows are its missing shards alone). flags[j] = 1 where stripe j's
+// compared rows mismatched.
+template <class InF, class OutF>
+int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_missing,
+                       const std::vector<size_t>& S, const std::vector<uint8_t>& present, InF& in,
+                       OutF& out, int* flags, const Join* joins) {
+  HIPCHK(hipSetDevice(device));
+  const int n = k + m, stripes = static_cast<int>(S.size());
+  const size_t nn = static_cast<size_t>(n);
+  // direct: every buffer pinned, and the call at or above the zero-copy threshold
+  unsigned long long total = 0;
+  for (size_t s : S) total += static_cast<unsigned long long>(s) * nn;
+  bool direct = !ctx->pinned.empty() && total >= zero_copy_min(nn);
+  for (int j = 0; direct && j < stripes; ++j)
+    for (int i = 0; direct && i < n; ++i) {
+      const bool written = !present[static_cast<size_t>(j) * nn + i];
+      if (by_missing && !written) {
+        // only the first k present shards are read
+        int before = 0;
+        for (int q = 0; q < i; ++q) before += present[static_cast<size_t>(j) * nn + q] != 0;
+        if (before >= k) continue;
+      }
+      direct = ctx->pinned.contains(written ? out(j, i) : in(j, i), S[static_cast<size_t>(j)]);
+    }
+  for (int j = 0; direct && joins && j < stripes; ++j)
+    direct = joins[j].len == 0 || ctx->pinned.contains(joins[j].out, joins[j].len);
+  for (const RaggedClass& cls : ragged_classes(n, stripes, present.data(), by_missing)) {
+    const int rows = by_missing ? cls.e : m;
+    for (const auto& seg : ragged_segments(k, n, rows, cls.stripes, present.data(), kRaggedArenaBudget)) {
+      RaggedRun r{ctx, k, m, {}, {}, {}, joins};
+      r.ids.assign(cls.stripes.begin() + static_cast<ptrdiff_t>(seg.first),
+                   cls.stripes.begin() + static_cast<ptrdiff_t>(seg.second));
+      std::vector<uint8_t> pres(r.ids.size() * nn);
+      for (size_t s = 0; s < r.ids.size(); ++s)
+        std::memcpy(&pres[s * nn], &present[static_cast<size_t>(r.ids[s]) * nn], nn);
+      const int count = static_cast<int>(r.ids.size());
+      const MixedError me = by_missing ? build_mixed_tables_missing(k, m, rows, count, pres.data(), r.mt)
+                                       : build_mixed_tables(k, m, count, pres.data(), r.mt);
+      if (me == MixedError::kSingular) return RS_E_SINGULAR;
+      if (me != MixedError::kOk) return RS_E_ARG;
+      r.sh.k = k;
+      for (const MixedGroup& g : r.mt.groups) r.sh.group_rows.push_back(g.R);
+      for (int s = 0; s < count; ++s) {
+        const MixedPattern& pt = r.pattern(s);
+        r.sh.size.push_back(S[static_cast<size_t>(r.ids[static_cast<size_t>(s)])]);
+        r.sh.nin.push_back(k + static_cast<int>(pt.rows.size()) - pt.missing);
+        r.sh.nout.push_back(pt.missing);
+      }
+      int rc;
+      if (direct) {
+        if ((rc = run_ragged_direct(r, L, in, out, flags))) return rc;
+        continue;
+      }
+      const std::vector<RaggedItem> items = ragged_items(r.sh, chunk_bytes());
+      // the whole run as one in-place chunk on slot 0
+      if (items.size() <= kRaggedMaxItems && small_max_bytes() > 0) {
+        std::vector<ChunkLayout> one(1, layout_chunk(r.sh, items, 0, items.size()));
+        if (one[0].out_end <= small_max_bytes() && RaggedInplace::fits(one[0])) {
+          RaggedInplace tr{r, L, {}, {}, 0};
+          if ((rc = run_ragged_chunks(r, L, items, one, tr, in, out, flags))) return rc;
+          continue;
+        }
+      }
+      const std::vector<ChunkLayout> chunks = ragged_chunks(r.sh, items, chunk_bytes());
+      bool inplace = inplace_pipeline();
+      for (const ChunkLayout& C : chunks) inplace = inplace && RaggedInplace::fits(C);
+      for (const ChunkLayout& C : chunks)
+        if (C.ntiles > kRaggedMaxTiles) return RS_E_ARG;
+      if (inplace) {
+        RaggedInplace tr{r, L, {}, {}, 0};
+        rc = run_ragged_chunks(r, L, items, chunks, tr, in, out, flags);
+      } else {
+        RaggedStaged tr{r, L, {}};
+        rc = run_ragged_chunks(r, L, items, chunks, tr, in, out, flags);
+      }
+      if (rc) return rc;
+    }
+  }
+  return RS_OK;
+}
+
+template <class InF, class OutF>
+int run_ragged(rs_ctx* ctx, int k, int m, bool by_missing, const std::vector<size_t>& S,
+               const std::vector<uint8_t>& present, InF in, OutF out, int* flags,
+               const Join* joins = nullptr) {
+  if (ctx->devs.empty()) return RS_E_HIP;
+  ctx->n_calls.fetch_add(1, std::memory_order_relaxed);
+  ctx->n_ragged_calls.fetch_add(1, std::memory_order_relaxed);
+  // one device and lane, chosen round-robin like any call (split_ways does not apply)
+  Device* dev = ctx->devs[device_slot(ctx->rr.fetch_add(1), 0, ctx->devs.size())].get();
+  return with_lane(ctx, dev, [&](Lane& L) {
+    return run_ragged_on_lane(ctx, L, dev->id, k, m, by_missing, S, present, in, out, flags, joins);
+  });
+}
+
+}  // namespace
+}  // namespace callfs

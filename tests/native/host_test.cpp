@@ -15,7 +15,8 @@
 //     persistence through a file, and concurrent recording and lookups
 // 10. the host path's HIP-free parts (host_path.hpp): chunk geometry, the rs_host_alloc pool
 //     and registry (also from eight threads), the 256-byte packer, join spans, index runs,
-//     check_lens' error precedence and the batch grouping
+//     check_lens' error precedence, the admission of a reconstruct stripe, the batch
+//     grouping and the batch calls' routing decision
 //  8. the bit-sliced kernels' generator (bitslice_gen.hpp): the bit transpose against its
 //     definition, each coefficient's GF(2) matrix against the field, the XOR network of
 //     random coefficient blocks (zeros included) against a scalar GF multiply, the rule
@@ -757,6 +758,83 @@ int main() {
         CHECK(BatchGroups::shard_size(kv.first) == 100 && kv.second[0] == 0 && kv.second[1] == 3);
         CHECK(std::memcmp(BatchGroups::present(kv.first), pa, 3) == 0);
       }
+
+    // admission of a reconstruct stripe, RS(2,2): every status, the skip, and their order
+    {
+      uint8_t buf[1];
+      const uint8_t* const full[4] = {buf, buf, buf, buf};
+      const uint8_t* const hole[4] = {buf, nullptr, buf, buf};  // a NULL shard pointer
+      const size_t one[4] = {0, 0, 8, 0}, two[4] = {8, 0, 0, 8}, three[4] = {8, 0, 8, 8};
+      uint8_t pres[4];
+      auto admit = [&](const uint8_t* const* sh, const size_t* ln, bool skip_complete) {
+        std::memset(pres, 7, 4);
+        return admit_stripe(4, 2, sh, ln, skip_complete, pres);
+      };
+      auto untouched = [&] { return pres[0] == 7 && pres[1] == 7 && pres[2] == 7 && pres[3] == 7; };
+      StripeAdmission a = admit(full, none, false);
+      CHECK(!a.run && a.status == RS_E_NO_DATA && untouched());
+      a = admit(full, odd, false);
+      CHECK(!a.run && a.status == RS_E_SHARD_SIZE && untouched());
+      a = admit(full, one, false);
+      CHECK(!a.run && a.status == RS_E_TOO_FEW_SHARDS && untouched());
+      // runnable: the shard size and the presence flags
+      a = admit(full, two, true);
+      CHECK(a.run && a.status == RS_OK && a.S == 8);
+      CHECK(pres[0] == 1 && pres[1] == 0 && pres[2] == 0 && pres[3] == 1);
+      // every shard present: nothing to do without verification, a run with it
+      a = admit(full, all, true);
+      CHECK(!a.run && a.status == RS_OK && a.S == 8 && untouched());
+      a = admit(full, all, false);
+      CHECK(a.run && a.status == RS_OK && a.S == 8 && pres[0] && pres[1] && pres[2] && pres[3]);
+      // a NULL shard: RS_E_ARG with enough shards, present or absent by its length
+      a = admit(hole, three, true);
+      CHECK(!a.run && a.status == RS_E_ARG && untouched());
+      a = admit(hole, all, false);
+      CHECK(!a.run && a.status == RS_E_ARG && untouched());
+      // ... but the lengths' errors and too few shards come first, and so does the skip
+      CHECK(admit(hole, none, false).status == RS_E_NO_DATA);
+      CHECK(admit(hole, odd, false).status == RS_E_SHARD_SIZE);
+      CHECK(admit(hole, one, false).status == RS_E_TOO_FEW_SHARDS);
+      a = admit(hole, all, true);
+      CHECK(!a.run && a.status == RS_OK);
+      // a size mismatch outranks too few shards
+      const size_t odd1[4] = {0, 8, 9, 0};
+      CHECK(admit(full, odd1, false).status == RS_E_SHARD_SIZE);
+    }
+
+    // the routing decision: ragged from two groups on, when allowed; the runnable stripes in
+    // ascending order whatever the insertion order; groups in by_key's order
+    {
+      BatchGroups none_run, one_group, two_groups;
+      for (bool allowed : {false, true}) {
+        const BatchRoute r0 = batch_route(none_run, allowed);  // an all-skipped batch
+        CHECK(!r0.ragged && r0.ids.empty() && r0.groups.empty());
+      }
+      one_group.add(100, pa, 3, 4);
+      one_group.add(100, pa, 3, 1);
+      for (bool allowed : {false, true}) {
+        const BatchRoute r1 = batch_route(one_group, allowed);
+        CHECK(!r1.ragged && r1.ids.empty() && r1.groups.size() == 1);
+        CHECK(r1.groups[0] == &*one_group.by_key.begin());
+        CHECK(r1.groups[0]->second == std::vector<int>({4, 1}));
+      }
+      two_groups.add(101, pa, 3, 5);
+      two_groups.add(100, pb, 3, 2);
+      two_groups.add(101, pa, 3, 0);
+      two_groups.add(100, pb, 3, 7);
+      const BatchRoute on = batch_route(two_groups, true);
+      CHECK(on.ragged && on.groups.empty() && on.ids == std::vector<int>({0, 2, 5, 7}));
+      const BatchRoute off = batch_route(two_groups, false);
+      CHECK(!off.ragged && off.ids.empty() && off.groups.size() == 2);
+      auto it = two_groups.by_key.begin();
+      CHECK(off.groups[0] == &*it && off.groups[1] == &*std::next(it));
+      const int g100 = BatchGroups::shard_size(off.groups[0]->first) == 100 ? 0 : 1;
+      CHECK(off.groups[g100]->second == std::vector<int>({2, 7}));  // stripes in call order
+      CHECK(off.groups[1 - g100]->second == std::vector<int>({5, 0}));
+      // three groups (the batch above): still one ragged run over every stripe
+      const BatchRoute r3 = batch_route(bg, true);
+      CHECK(r3.ragged && r3.ids == std::vector<int>({0, 1, 2, 3}));
+    }
 
     // the registry: ranges by fake addresses (never dereferenced)
     auto fake = [](uintptr_t a) { return reinterpret_cast<void*>(a); };

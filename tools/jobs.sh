@@ -633,7 +633,7 @@ timeout -k 10 900 python3 -u tools/ceiling_sweep.py --tune 1 --rounds 2 --only p
 echo ok
 }
 
-# Zero-copy threshold (CALLFS_RS_ZERO_COPY_MIN_BYTES, rs_host.cpp direct_ok) on the current
+# Zero-copy threshold (CALLFS_RS_ZERO_COPY_MIN_BYTES, host_common.hpp zero_copy_min) on the current
 # build: rs_host_alloc buffers through the zero-copy launch (threshold 1 B) against the
 # one-dispatch small path / staged pipeline (threshold 1 GiB), encode + decode, 1 and 8
 # request threads. Output: gpurun_out/<tag>/zc.jsonl. Usage: bash tools/jobs.sh zc_threshold <tag>
