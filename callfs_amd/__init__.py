@@ -23,6 +23,7 @@ from .erasure import (  # noqa: F401
     encode_matrix,
     encode_shards,
     reconstruct,
+    reconstruct_some,
     shard_checksum,
     shard_layout,
     verify,
@@ -32,6 +33,6 @@ __all__ = [
     "Codec", "ErasureProfile", "ErasureError", "ErrInsufficientShards", "ErrInvalidProfile",
     "ErrShardCorrupted", "ErrShardNotFound", "ErrShortData", "ErrTooFewShards",
     "ErrShardNoData", "ErrShardSize", "ErrSingular", "ErrUnsupportedProfile",
-    "decode_rows", "encode_matrix", "encode_shards", "reconstruct", "verify",
+    "decode_rows", "encode_matrix", "encode_shards", "reconstruct", "reconstruct_some", "verify",
     "shard_checksum", "shard_layout",
 ]

@@ -81,6 +81,14 @@ SIGNATURES = {
                                      ctypes.POINTER(_int)]),
     "rs_codec_decode_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
                                      ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_int)]),
+    "rs_reconstruct_some": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _u8p]),
+    "rs_reconstruct_some_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp),
+                                         ctypes.POINTER(_sz), _u8p, _int, ctypes.POINTER(_int)]),
+    "rs_codec_decode_data": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _vp,
+                                    _i64]),
+    "rs_codec_decode_data_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp),
+                                          ctypes.POINTER(_sz), ctypes.POINTER(_vp),
+                                          ctypes.POINTER(_i64), ctypes.POINTER(_int)]),
     "rs_plan_create": (_int, [_vp, _int, _int, _int, _sz, _int, _u8p, ctypes.POINTER(_vp),
                               ctypes.POINTER(_vp)]),
     "rs_plan_launch": (_int, [_vp, _vp]),
@@ -106,6 +114,10 @@ SIGNATURES = {
                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rs_decode_dev_ragged": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
                                     ctypes.POINTER(_vp), _vp]),
+    "rs_plan_create_required": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p, _u8p,
+                                       ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rs_decode_dev_required": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p, _u8p,
+                                      ctypes.POINTER(_vp), _vp]),
     "rs_sha256_plan_create": (_int, [_vp, _int, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64),
                                      _int, ctypes.POINTER(_vp)]),
     "rs_sha256_plan_launch": (_int, [_vp, _vp, _vp]),

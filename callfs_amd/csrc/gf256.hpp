@@ -125,8 +125,13 @@ struct DecodePlan {
   Mat rows;                  // (missing + check) x k; missing rows first
 };
 
-// present: n flags. Returns false when singular (cannot happen for k+m <= 256).
-inline bool decode_plan(int k, int m, const uint8_t* present, DecodePlan& p) {
+// present: n flags. wanted: n flags or null (ReconstructSome's `required`): a missing shard
+// whose flag is clear is left out of `missing` and has no row; flags on present shards are
+// ignored; `check` is the same whatever is wanted. The rows are the matching subset of the
+// all-wanted plan's rows, in the same order. Returns false when singular (cannot happen for
+// k+m <= 256).
+inline bool decode_plan(int k, int m, const uint8_t* present, const uint8_t* wanted,
+                        DecodePlan& p) {
   const int n = k + m;
   Mat E;
   if (!encode_matrix(k, m, E)) return false;
@@ -135,7 +140,7 @@ inline bool decode_plan(int k, int m, const uint8_t* present, DecodePlan& p) {
     if (present[i]) {
       if (static_cast<int>(p.valid.size()) < k) p.valid.push_back(i);
       else p.check.push_back(i);  // always a parity index: data indices come first
-    } else {
+    } else if (!wanted || wanted[i]) {
       p.missing.push_back(i);
     }
   }
@@ -159,6 +164,11 @@ inline bool decode_plan(int k, int m, const uint8_t* present, DecodePlan& p) {
   for (int idx : p.missing) emit(idx);
   for (int idx : p.check) emit(idx);
   return true;
+}
+
+// Every missing shard wanted (Reconstruct).
+inline bool decode_plan(int k, int m, const uint8_t* present, DecodePlan& p) {
+  return decode_plan(k, m, present, nullptr, p);
 }
 
 // v_perm_b32 lookup tables for multiplying 4 packed bytes by coefficient c:

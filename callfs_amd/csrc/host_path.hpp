@@ -270,6 +270,43 @@ inline StripeAdmission admit_stripe(int n, int k, const uint8_t* const* shards, 
   return a;
 }
 
+// A stripe's shards in a call with a wanted set (ReconstructSome): the flags admission writes
+// and the batch calls group, class and build tables by. A call without one writes 0 / 1, which
+// read the same: every missing shard is wanted.
+constexpr uint8_t kShardWanted = 0;    // missing, to be rebuilt
+constexpr uint8_t kShardPresent = 1;
+constexpr uint8_t kShardUnwanted = 2;  // missing, neither written nor read
+
+// admit_stripe with a wanted set. wanted: n flags (nonzero = wanted; flags on present shards
+// count for nothing). In order: check_lens' status, RS_E_TOO_FEW_SHARDS, nothing to do (run
+// false, status RS_OK) when no missing shard is wanted and nothing is compared (!verify),
+// RS_E_ARG for a NULL shard among those the call touches -- the present ones and the wanted
+// missing ones; an unwanted missing shard may be NULL. With verify, a stripe of exactly k
+// present shards that wants nothing has no row either: run false, status RS_OK, and `flags`
+// and S are still written (decode's join copies its data shards). flags: n of kShard*.
+inline StripeAdmission admit_stripe_required(int n, int k, const uint8_t* const* shards,
+                                             const size_t* lens, const uint8_t* wanted, bool verify,
+                                             uint8_t* flags) {
+  StripeAdmission a;
+  int np = 0;
+  if ((a.status = check_lens(n, lens, true, &a.S, &np))) return a;
+  if (np < k) {
+    a.status = RS_E_TOO_FEW_SHARDS;
+    return a;
+  }
+  int w = 0;
+  for (int i = 0; i < n; ++i) w += !lens[i] && wanted[i];
+  if (w == 0 && !verify) return a;
+  for (int i = 0; i < n; ++i)
+    if (!shards[i] && (lens[i] || wanted[i])) {
+      a.status = RS_E_ARG;
+      return a;
+    }
+  for (int i = 0; i < n; ++i) flags[i] = lens[i] ? kShardPresent : wanted[i] ? kShardWanted : kShardUnwanted;
+  a.run = w + (np - k) > 0;
+  return a;
+}
+
 // Stripes grouped by (S, presence): each group shares one table set and one pipeline.
 struct BatchGroups {
   std::map<std::string, std::vector<int>> by_key;

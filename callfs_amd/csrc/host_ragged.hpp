@@ -22,6 +22,7 @@ struct RaggedRun {
   RaggedShape sh;
   std::vector<int> ids;
   const Join* joins;  // nullable: one per runnable stripe of the call (codec-level batches)
+  bool some = false;  // a call with a wanted set: patterns are (mask, wanted) pairs
   const Join* join_of(int id) const { return joins ? joins + id : nullptr; }
   const MixedPattern& pattern(int s) const { return mt.patterns[mt.pat[static_cast<size_t>(s)]]; }
   void count(size_t chunks, size_t copies) const {
@@ -35,6 +36,11 @@ struct RaggedRun {
 std::string ragged_key(const RaggedRun& r) {
   std::string key = std::to_string(r.k) + "," + std::to_string(r.m) + "," + std::to_string(r.mt.rows) + ":";
   for (const MixedPattern& p : r.mt.patterns) key.append(reinterpret_cast<const char*>(p.mask.data()), p.mask.size());
+  if (r.some)  // one mask has as many patterns as wanted sets: their rows tell them apart
+    for (const MixedPattern& p : r.mt.patterns) {
+      key.push_back('|');
+      for (int i : p.rows) key.push_back(static_cast<char>(i));
+    }
   return key;
 }
 
@@ -375,8 +381,11 @@ int run_ragged_direct(const RaggedRun& r, Lane& L, InF& in, OutF& out, int* flag
 // by_missing: a reconstruct without verification, whose stripes run in classes by missing
 // count (a pattern's rows are its missing shards alone). flags[j] = 1 where stripe j's
 // compared rows mismatched.
+// some: a call with a wanted set. `present` then holds kShard* flags
+// (host_path.hpp), an unwanted missing shard is neither read nor written, and the stripes run
+// in classes by row count (ragged_classes_required), compared rows dropped when by_missing.
 template <class InF, class OutF>
-int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_missing,
+int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_missing, bool some,
                        const std::vector<size_t>& S, const std::vector<uint8_t>& present, InF& in,
                        OutF& out, int* flags, const Join* joins) {
   HIPCHK(hipSetDevice(device));
@@ -389,28 +398,49 @@ int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_m
   for (int j = 0; direct && j < stripes; ++j)
     for (int i = 0; direct && i < n; ++i) {
       const bool written = !present[static_cast<size_t>(j) * nn + i];
+      if (some && present[static_cast<size_t>(j) * nn + i] == kShardUnwanted) continue;
       if (by_missing && !written) {
         // only the first k present shards are read
         int before = 0;
-        for (int q = 0; q < i; ++q) before += present[static_cast<size_t>(j) * nn + q] != 0;
+        for (int q = 0; q < i; ++q) before += present[static_cast<size_t>(j) * nn + q] == kShardPresent;
         if (before >= k) continue;
       }
       direct = ctx->pinned.contains(written ? out(j, i) : in(j, i), S[static_cast<size_t>(j)]);
     }
   for (int j = 0; direct && joins && j < stripes; ++j)
     direct = joins[j].len == 0 || ctx->pinned.contains(joins[j].out, joins[j].len);
-  for (const RaggedClass& cls : ragged_classes(n, stripes, present.data(), by_missing)) {
-    const int rows = by_missing ? cls.e : m;
-    for (const auto& seg : ragged_segments(k, n, rows, cls.stripes, present.data(), kRaggedArenaBudget)) {
+  const std::vector<RaggedClass> classes =
+      some ? ragged_classes_required(n, k, stripes, present.data(), !by_missing)
+           : ragged_classes(n, stripes, present.data(), by_missing);
+  for (const RaggedClass& cls : classes) {
+    const int rows = by_missing || some ? cls.e : m;
+    const auto segments =
+        some ? ragged_segments_required(k, n, rows, cls.stripes, present.data(), kRaggedArenaBudget)
+             : ragged_segments(k, n, rows, cls.stripes, present.data(), kRaggedArenaBudget);
+    for (const auto& seg : segments) {
       RaggedRun r{ctx, k, m, {}, {}, {}, joins};
+      r.some = some;
       r.ids.assign(cls.stripes.begin() + static_cast<ptrdiff_t>(seg.first),
                    cls.stripes.begin() + static_cast<ptrdiff_t>(seg.second));
       std::vector<uint8_t> pres(r.ids.size() * nn);
       for (size_t s = 0; s < r.ids.size(); ++s)
         std::memcpy(&pres[s * nn], &present[static_cast<size_t>(r.ids[s]) * nn], nn);
       const int count = static_cast<int>(r.ids.size());
-      const MixedError me = by_missing ? build_mixed_tables_missing(k, m, rows, count, pres.data(), r.mt)
-                                       : build_mixed_tables(k, m, count, pres.data(), r.mt);
+      MixedError me;
+      if (some) {
+        // every pattern of the class has `rows` rows: the tables are what the kernels expect
+        std::vector<uint8_t> want(pres.size());
+        for (size_t q = 0; q < pres.size(); ++q) {
+          want[q] = pres[q] == kShardWanted;
+          pres[q] = pres[q] == kShardPresent;
+        }
+        me = build_mixed_tables_required(k, m, count, pres.data(), want.data(), r.mt, !by_missing);
+        for (const MixedPattern& pt : r.mt.patterns)
+          if (me == MixedError::kOk && static_cast<int>(pt.rows.size()) != rows) me = MixedError::kRowCount;
+      } else {
+        me = by_missing ? build_mixed_tables_missing(k, m, rows, count, pres.data(), r.mt)
+                        : build_mixed_tables(k, m, count, pres.data(), r.mt);
+      }
       if (me == MixedError::kSingular) return RS_E_SINGULAR;
       if (me != MixedError::kOk) return RS_E_ARG;
       r.sh.k = k;
@@ -457,14 +487,14 @@ int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_m
 template <class InF, class OutF>
 int run_ragged(rs_ctx* ctx, int k, int m, bool by_missing, const std::vector<size_t>& S,
                const std::vector<uint8_t>& present, InF in, OutF out, int* flags,
-               const Join* joins = nullptr) {
+               const Join* joins = nullptr, bool some = false) {
   if (ctx->devs.empty()) return RS_E_HIP;
   ctx->n_calls.fetch_add(1, std::memory_order_relaxed);
   ctx->n_ragged_calls.fetch_add(1, std::memory_order_relaxed);
   // one device and lane, chosen round-robin like any call (split_ways does not apply)
   Device* dev = ctx->devs[device_slot(ctx->rr.fetch_add(1), 0, ctx->devs.size())].get();
   return with_lane(ctx, dev, [&](Lane& L) {
-    return run_ragged_on_lane(ctx, L, dev->id, k, m, by_missing, S, present, in, out, flags, joins);
+    return run_ragged_on_lane(ctx, L, dev->id, k, m, by_missing, some, S, present, in, out, flags, joins);
   });
 }
 

@@ -261,6 +261,27 @@ inline std::vector<RaggedClass> ragged_classes(int n, int stripes, const uint8_t
   return out;
 }
 
+// The sibling for calls with a wanted set (flags: stripes * n of kShard*, host_path.hpp): one
+// class per row count r = wanted missing shards + (verify: present shards beyond the first k),
+// in ascending r, so that every pattern of a class has exactly r rows, which is what the
+// ragged kernels rest on; `e` holds r. Stripes with r = 0 are in no class.
+inline std::vector<RaggedClass> ragged_classes_required(int n, int k, int stripes, const uint8_t* flags,
+                                                        bool verify) {
+  std::vector<std::vector<int>> by(static_cast<size_t>(n) + 1);
+  for (int b = 0; b < stripes; ++b) {
+    int w = 0, np = 0;
+    for (int i = 0; i < n; ++i) {
+      w += flags[static_cast<size_t>(b) * n + i] == kShardWanted;
+      np += flags[static_cast<size_t>(b) * n + i] == kShardPresent;
+    }
+    by[static_cast<size_t>(w + (verify && np > k ? np - k : 0))].push_back(b);
+  }
+  std::vector<RaggedClass> out;
+  for (int r = 1; r <= n; ++r)
+    if (!by[r].empty()) out.push_back({r, std::move(by[r])});
+  return out;
+}
+
 // Bytes of one pattern's tables over every launch group of `rows` rows.
 inline size_t pattern_arena_bytes(int k, int rows) {
   size_t bytes = 0;
@@ -283,6 +304,30 @@ inline std::vector<std::pair<size_t, size_t>> ragged_segments(int k, int n, int 
     std::string key(static_cast<size_t>(n), '0');
     for (int i = 0; i < n; ++i)
       if (present[static_cast<size_t>(stripes[j]) * n + i]) key[static_cast<size_t>(i)] = '1';
+    if (!seen.count(key) && seen.size() == max_patterns) {
+      segs.push_back({begin, j});
+      begin = j;
+      seen.clear();
+    }
+    seen.insert(std::move(key));
+  }
+  if (begin < stripes.size()) segs.push_back({begin, stripes.size()});
+  return segs;
+}
+
+// ragged_segments for calls with a wanted set: a pattern is a stripe's whole row of kShard*
+// flags (the mask and the wanted missing shards).
+inline std::vector<std::pair<size_t, size_t>> ragged_segments_required(int k, int n, int rows,
+                                                                       const std::vector<int>& stripes,
+                                                                       const uint8_t* flags, size_t budget) {
+  const size_t per = pattern_arena_bytes(k, rows);
+  const size_t max_patterns = std::max<size_t>(1, budget / std::max<size_t>(per, 1));
+  std::vector<std::pair<size_t, size_t>> segs;
+  std::set<std::string> seen;
+  size_t begin = 0;
+  for (size_t j = 0; j < stripes.size(); ++j) {
+    std::string key(reinterpret_cast<const char*>(flags + static_cast<size_t>(stripes[j]) * n),
+                    static_cast<size_t>(n));
     if (!seen.count(key) && seen.size() == max_patterns) {
       segs.push_back({begin, j});
       begin = j;

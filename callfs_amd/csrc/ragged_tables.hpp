@@ -83,6 +83,76 @@ inline RaggedError build_ragged_tables(int k, int m, int batch, const size_t* si
   return RaggedError::kOk;
 }
 
+// ---- required plans (rs_plan_create_required) ---------------------------
+// Patterns with their own row counts (build_mixed_tables_required) leave some stripes with
+// no row in a launch group, so every group has a tile map of its own over the stripes that
+// have one: tile0 is still indexed by stripe (entries of skipped stripes are never read: no
+// tile names them), tile_stripe lists the group's tiles alone. A group no stripe has a row
+// in has ntiles = 0 and launches nothing.
+struct GroupTileMap {
+  std::vector<uint32_t> tile0;        // [batch + 1]
+  std::vector<uint32_t> tile_stripe;  // [ntiles]
+  uint32_t ntiles = 0;
+  int stripes = 0;        // stripes with a row in the group
+  bool any_tail = false;  // one of them has size % 16 != 0
+};
+
+struct RequiredTables {
+  MixedTables mixed;           // build_mixed_tables_required
+  std::vector<uint64_t> size;  // [batch]
+  std::vector<GroupTileMap> maps;  // one per launch group of `mixed`
+  // sum over the stripes with a row of size * (k + written rows + compared rows)
+  uint64_t bytes = 0;
+};
+
+inline RaggedError build_required_tables(int k, int m, int batch, const size_t* sizes,
+                                         const uint8_t* present, const uint8_t* required,
+                                         RequiredTables& t) {
+  t = RequiredTables();
+  t.size.assign(static_cast<size_t>(batch), 0);
+  for (int b = 0; b < batch; ++b) {
+    if (sizes[b] == 0) return RaggedError::kNoData;
+    t.size[static_cast<size_t>(b)] = sizes[b];
+  }
+  switch (build_mixed_tables_required(k, m, batch, present, required, t.mixed)) {
+    case MixedError::kOk: break;
+    case MixedError::kTooFewShards: return RaggedError::kTooFewShards;
+    case MixedError::kSingular: return RaggedError::kSingular;
+    case MixedError::kRowCount: break;  // the missing-rows form only
+  }
+  for (int b = 0; b < batch; ++b) {
+    const uint64_t r = t.mixed.patterns[t.mixed.pat[static_cast<size_t>(b)]].rows.size();
+    if (r == 0) continue;
+    const uint64_t add = t.size[static_cast<size_t>(b)] * (static_cast<uint64_t>(k) + r);
+    if (add / (static_cast<uint64_t>(k) + r) != t.size[static_cast<size_t>(b)] ||
+        t.bytes + add < t.bytes)
+      return RaggedError::kTooManyTiles;
+    t.bytes += add;
+  }
+  for (const MixedGroup& g : t.mixed.groups) {
+    GroupTileMap gm;
+    gm.tile0.assign(static_cast<size_t>(batch) + 1, 0);
+    uint64_t ntiles = 0;
+    for (int b = 0; b < batch; ++b) {
+      gm.tile0[static_cast<size_t>(b)] = static_cast<uint32_t>(ntiles);
+      if (g.nrows[t.mixed.pat[static_cast<size_t>(b)]] == 0) continue;
+      const uint64_t S = t.size[static_cast<size_t>(b)];
+      ntiles += ragged_tiles(S);
+      if (ntiles > kRaggedMaxTiles) return RaggedError::kTooManyTiles;
+      gm.any_tail |= (S & 15u) != 0;
+      ++gm.stripes;
+    }
+    gm.tile0[static_cast<size_t>(batch)] = static_cast<uint32_t>(ntiles);
+    gm.ntiles = static_cast<uint32_t>(ntiles);
+    gm.tile_stripe.resize(static_cast<size_t>(ntiles));
+    for (int b = 0; b < batch; ++b)
+      for (uint32_t i = gm.tile0[static_cast<size_t>(b)]; i < gm.tile0[static_cast<size_t>(b) + 1]; ++i)
+        gm.tile_stripe[i] = static_cast<uint32_t>(b);
+    t.maps.push_back(std::move(gm));
+  }
+  return RaggedError::kOk;
+}
+
 // True when every stripe of the batch has the same shard size.
 inline bool ragged_sizes_equal(int batch, const size_t* sizes) {
   for (int b = 1; b < batch; ++b)

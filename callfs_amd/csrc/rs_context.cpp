@@ -16,10 +16,11 @@ namespace callfs {
 
 namespace {
 
-// verify=false drops the check rows (plain Reconstruct).
-std::shared_ptr<const Tables> build_tables(int k, int m, const uint8_t* present, bool verify) {
+// verify=false drops the check rows (plain Reconstruct); wanted as for decode_plan.
+std::shared_ptr<const Tables> build_tables(int k, int m, const uint8_t* present, bool verify,
+                                           const uint8_t* wanted) {
   DecodePlan dp;
-  if (!decode_plan(k, m, present, dp)) return nullptr;
+  if (!decode_plan(k, m, present, wanted, dp)) return nullptr;
   auto t = std::make_shared<Tables>();
   t->k = k;
   t->m = m;
@@ -59,19 +60,22 @@ std::shared_ptr<const Tables> build_tables(int k, int m, const uint8_t* present,
 
 }  // namespace
 
-std::shared_ptr<const Tables> TableCache::get(int k, int m, const uint8_t* present, bool verify) {
+std::shared_ptr<const Tables> TableCache::get(int k, int m, const uint8_t* present, bool verify,
+                                              const uint8_t* wanted) {
   std::string key;
   key.reserve(k + m + 8);
   key.append(reinterpret_cast<const char*>(&k), sizeof k);
   key.append(reinterpret_cast<const char*>(&m), sizeof m);
   key.push_back(verify ? 'v' : 'r');
-  for (int i = 0; i < k + m; ++i) key.push_back(present[i] ? '1' : '0');
+  // '0' a missing shard that is rebuilt, 'u' one nobody wants: all wanted = the key of null
+  for (int i = 0; i < k + m; ++i)
+    key.push_back(present[i] ? '1' : (!wanted || wanted[i]) ? '0' : 'u');
   {
     std::lock_guard<std::mutex> g(mu_);
     auto it = map_.find(key);
     if (it != map_.end()) return it->second;
   }
-  auto t = build_tables(k, m, present, verify);
+  auto t = build_tables(k, m, present, verify, wanted);
   if (!t) return nullptr;
   std::lock_guard<std::mutex> g(mu_);
   if (map_.size() >= kCap) map_.clear();

@@ -24,14 +24,21 @@ std::shared_ptr<const Tables> encode_tables(rs_ctx* ctx, int k, int m) {
 
 // Shared by rs_reconstruct / rs_codec_decode. verify=true fuses upstream Verify. `joined`
 // (nullable) asks for decode's join of original_size bytes into `out` on the way through
-// the pipeline and tells whether the pipeline ran and wrote it.
+// the pipeline and tells whether the pipeline ran and wrote it. wanted (nullable, k+m flags):
+// the missing shards to rebuild (rs_reconstruct_some, rs_codec_decode_data); the others are
+// neither written nor read.
 int reconstruct_host(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
                      bool verify, uint8_t* out = nullptr, size_t original_size = 0,
-                     bool* joined = nullptr) {
-  uint8_t present[256];
-  const StripeAdmission a = admit_stripe(k + m, k, shards, lens, !verify, present);
+                     bool* joined = nullptr, const uint8_t* wanted = nullptr) {
+  uint8_t present[256], want[256];
+  const StripeAdmission a = wanted ? admit_stripe_required(k + m, k, shards, lens, wanted, verify, present)
+                                   : admit_stripe(k + m, k, shards, lens, !verify, present);
   if (!a.run) return a.status;
-  auto t = ctx->cache.get(k, m, present, verify);
+  for (int i = 0; wanted && i < k + m; ++i) {
+    want[i] = present[i] != kShardUnwanted;
+    present[i] = present[i] == kShardPresent;
+  }
+  auto t = ctx->cache.get(k, m, present, verify, wanted ? want : nullptr);
   if (!t) return RS_E_SINGULAR;
   if (t->groups.empty()) return RS_OK;
   const Join join = decode_join(k, a.S, out, original_size);
@@ -55,6 +62,9 @@ int first_error(const int* status, int batch) {
 struct BatchMode {
   bool verify;
   bool by_missing;
+  // a call with a wanted set: `present` holds kShard* flags (host_path.hpp), the group key is
+  // the (mask, wanted) pair and a ragged run classes its stripes by row count
+  bool some = false;
 };
 
 // The runnable stripes of a batch call (`groups`) on the route batch_route (host_path.hpp)
@@ -84,14 +94,21 @@ int run_batch(rs_ctx* ctx, int k, int m, BatchMode mode, const BatchGroups& grou
     const int rc = run_ragged(ctx, k, m, mode.by_missing, Sj, pres,
                               [&](int j, int i) { return in(ids[j], i); },
                               [&](int j, int i) { return out(ids[j], i); }, fj.data(),
-                              joins ? jj.data() : nullptr);
+                              joins ? jj.data() : nullptr, mode.some);
     for (size_t j = 0; j < ids.size(); ++j) flags[ids[j]] = fj[j];
     return rc;
   }
   bool first = true;
   for (const auto* kv : route.groups) {
     const std::vector<int>& ids = kv->second;
-    auto t = ctx->cache.get(k, m, BatchGroups::present(kv->first), mode.verify);
+    // the group's flags: 0 / 1 read as a mask whose missing shards are all wanted
+    const uint8_t* key = BatchGroups::present(kv->first);
+    uint8_t pres[256], want[256];
+    for (size_t i = 0; i < n; ++i) {
+      pres[i] = mode.some ? key[i] == kShardPresent : key[i] != 0;
+      want[i] = !mode.some || key[i] != kShardUnwanted;
+    }
+    auto t = ctx->cache.get(k, m, pres, mode.verify, want);
     if (!t) return RS_E_SINGULAR;
     if (t->groups.empty()) continue;
     std::vector<Join> jj;
@@ -111,18 +128,44 @@ int run_batch(rs_ctx* ctx, int k, int m, BatchMode mode, const BatchGroups& grou
 
 // Shared by rs_reconstruct_batch / rs_codec_decode_batch, as reconstruct_host is by the
 // single calls. out and original_sizes (both or neither) ask for decode's join per object.
+// required (nullable, batch * n flags) or data_only (the data shards) name the missing shards
+// to rebuild: the others are neither written nor read, a stripe without a row reaches no
+// device, and decode's join of such a stripe is a plain copy of its data shards.
 int reconstruct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
                            size_t* lens, bool verify, uint8_t* const* out,
-                           const int64_t* original_sizes, int* status) {
+                           const int64_t* original_sizes, int* status,
+                           const uint8_t* required = nullptr, bool data_only = false) {
   const size_t n = static_cast<size_t>(k + m), B = static_cast<size_t>(batch);
+  const bool some = required || data_only;
   std::vector<uint8_t> present(B * n, 0);
   std::vector<size_t> S(B, 0);  // nonzero for the stripes that run
   std::vector<Join> joins(out ? B : 0, Join{nullptr, 0, 0, k});
+  std::vector<uint8_t> data_flags(data_only ? n : 0, 0);
+  for (int i = 0; data_only && i < k; ++i) data_flags[static_cast<size_t>(i)] = 1;
+  std::vector<CopyPool::Seg> copies;  // the joins of stripes without a row
   BatchGroups groups;
   for (size_t b = 0; b < B; ++b) {
     const StripeAdmission a =
-        admit_stripe(k + m, k, shards + b * n, lens + b * n, !verify, &present[b * n]);
+        some ? admit_stripe_required(k + m, k, shards + b * n, lens + b * n,
+                                     data_only ? data_flags.data() : required + b * n, verify,
+                                     &present[b * n])
+             : admit_stripe(k + m, k, shards + b * n, lens + b * n, !verify, &present[b * n]);
     status[b] = a.status;
+    if (!a.run && some && out && a.status == RS_OK) {
+      // admitted, nothing to compute: every data shard is present (data_only)
+      if (original_sizes[b] < 0 || (original_sizes[b] != 0 && !out[b])) {
+        status[b] = RS_E_ARG;
+        continue;
+      }
+      const Join j = decode_join(k, a.S, out[b], static_cast<size_t>(original_sizes[b]));
+      for (int i = 0; i < k; ++i) {
+        const auto js = join_span(&j, i, 0, a.S);
+        if (js.first) copies.push_back({js.first, shards[b * n + static_cast<size_t>(i)], js.second});
+      }
+      if (static_cast<uint64_t>(a.S) * k < static_cast<uint64_t>(original_sizes[b]))
+        status[b] = RS_E_INSUFFICIENT;
+      continue;
+    }
     if (!a.run) continue;
     if (out) {
       // a runnable object's own arguments: the same RS_E_ARG as a NULL shard
@@ -137,8 +180,9 @@ int reconstruct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const*
   }
   std::vector<int> flags(B, 0);
   auto shard = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
-  const int rc = run_batch(ctx, k, m, BatchMode{verify, !verify}, groups, S.data(), present.data(),
-                           out ? joins.data() : nullptr, shard, shard, flags.data());
+  if (!copies.empty()) ctx->pool.run(copies);
+  const int rc = run_batch(ctx, k, m, BatchMode{verify, !verify, some}, groups, S.data(),
+                           present.data(), out ? joins.data() : nullptr, shard, shard, flags.data());
   if (rc) return rc;
   for (size_t b = 0; b < B; ++b) {
     if (!S[b]) continue;
@@ -150,6 +194,36 @@ int reconstruct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const*
       status[b] = RS_E_INSUFFICIENT;
   }
   return first_error(status, batch);
+}
+
+// rs_codec_decode, and with data_only rs_codec_decode_data: upstream ReconstructData in
+// Reconstruct's place, so missing parity stays missing.
+int codec_decode(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens, uint8_t* out,
+                 int64_t original_size, bool data_only) {
+  DeviceGuard dg;
+  // codec.go:46-48 profile, :50 New, :55 Reconstruct, :59-65 Verify, :67-77 join/trim
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shards || !lens || original_size < 0 || (original_size && !out)) return RS_E_ARG;
+  bool joined = false;
+  uint8_t data_flags[256] = {0};
+  for (int i = 0; i < k; ++i) data_flags[i] = 1;
+  rc = reconstruct_host(ctx, k, m, shards, lens, true, out, static_cast<size_t>(original_size),
+                        &joined, data_only ? data_flags : nullptr);
+  if (rc) return rc;
+  const size_t S = lens[0];
+  if (static_cast<uint64_t>(S) * k < static_cast<uint64_t>(original_size))
+    return RS_E_INSUFFICIENT;
+  if (joined) return RS_OK;  // joined on the way through the pipeline
+  size_t left = static_cast<size_t>(original_size);
+  std::vector<CopyPool::Seg> segs;
+  for (int i = 0; i < k && left; ++i) {
+    const size_t c = std::min(S, left);
+    segs.push_back({out + S * i, shards[i], c});
+    left -= c;
+  }
+  ctx->pool.run(segs);
+  return RS_OK;
 }
 
 }  // namespace
@@ -205,6 +279,15 @@ int rs_reconstruct(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* le
   return reconstruct_host(ctx, k, m, shards, lens, false);
 }
 
+int rs_reconstruct_some(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                        const uint8_t* required) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shards || !lens) return RS_E_ARG;
+  return reconstruct_host(ctx, k, m, shards, lens, false, nullptr, 0, nullptr, required);
+}
+
 int rs_verify(rs_ctx* ctx, int k, int m, const uint8_t* const* shards, const size_t* lens,
               int* ok) {
   DeviceGuard dg;
@@ -230,28 +313,12 @@ int rs_verify(rs_ctx* ctx, int k, int m, const uint8_t* const* shards, const siz
 
 int rs_codec_decode(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
                     uint8_t* out, int64_t original_size) {
-  DeviceGuard dg;
-  // codec.go:46-48 profile, :50 New, :55 Reconstruct, :59-65 Verify, :67-77 join/trim
-  int rc = check_profile(k, m);
-  if (rc) return rc;
-  if (!ctx || !shards || !lens || original_size < 0 || (original_size && !out)) return RS_E_ARG;
-  bool joined = false;
-  rc = reconstruct_host(ctx, k, m, shards, lens, true, out, static_cast<size_t>(original_size),
-                        &joined);
-  if (rc) return rc;
-  const size_t S = lens[0];
-  if (static_cast<uint64_t>(S) * k < static_cast<uint64_t>(original_size))
-    return RS_E_INSUFFICIENT;
-  if (joined) return RS_OK;  // joined on the way through the pipeline
-  size_t left = static_cast<size_t>(original_size);
-  std::vector<CopyPool::Seg> segs;
-  for (int i = 0; i < k && left; ++i) {
-    const size_t c = std::min(S, left);
-    segs.push_back({out + S * i, shards[i], c});
-    left -= c;
-  }
-  ctx->pool.run(segs);
-  return RS_OK;
+  return codec_decode(ctx, k, m, shards, lens, out, original_size, false);
+}
+
+int rs_codec_decode_data(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                         uint8_t* out, int64_t original_size) {
+  return codec_decode(ctx, k, m, shards, lens, out, original_size, true);
 }
 
 // ---- exported: batched host-memory calls ------------------------------------------------
@@ -288,6 +355,16 @@ int rs_reconstruct_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* s
   if (rc) return rc;
   if (!ctx || batch < 0 || (batch && (!shards || !lens || !status))) return RS_E_ARG;
   return reconstruct_batch_host(ctx, k, m, batch, shards, lens, verify != 0, nullptr, nullptr, status);
+}
+
+int rs_reconstruct_some_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
+                              size_t* lens, const uint8_t* required, int verify, int* status) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!shards || !lens || !status))) return RS_E_ARG;
+  return reconstruct_batch_host(ctx, k, m, batch, shards, lens, verify != 0, nullptr, nullptr, status,
+                                required);
 }
 
 // ---- exported: codec-level batches (objects in, objects out) ----------------------------
@@ -345,6 +422,18 @@ int rs_codec_decode_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* 
   if (!ctx || batch < 0 || (batch && (!shards || !lens || !out || !original_sizes || !status)))
     return RS_E_ARG;
   return reconstruct_batch_host(ctx, k, m, batch, shards, lens, true, out, original_sizes, status);
+}
+
+int rs_codec_decode_data_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
+                               size_t* lens, uint8_t* const* out, const int64_t* original_sizes,
+                               int* status) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!shards || !lens || !out || !original_sizes || !status)))
+    return RS_E_ARG;
+  return reconstruct_batch_host(ctx, k, m, batch, shards, lens, true, out, original_sizes, status,
+                                nullptr, true);
 }
 
 }  // extern "C"

@@ -85,8 +85,11 @@ struct Tables {
 
 class TableCache {
  public:
-  // verify=false drops the check rows (plain Reconstruct). Null: a singular matrix.
-  std::shared_ptr<const Tables> get(int k, int m, const uint8_t* present, bool verify);
+  // verify=false drops the check rows (plain Reconstruct). wanted (k+m flags, or null: every
+  // missing shard): a missing shard whose flag is clear gets no row (ReconstructSome); a
+  // wanted set that names every missing shard shares the null entry. Null: a singular matrix.
+  std::shared_ptr<const Tables> get(int k, int m, const uint8_t* present, bool verify,
+                                    const uint8_t* wanted = nullptr);
 
  private:
   static constexpr size_t kCap = 4096;

@@ -246,6 +246,24 @@ constexpr uint32_t kRaggedLaunchTileVecs = 512;
 hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, bool any_tail, hipStream_t stream,
                          LaunchEvents ev = {});
 
+// ---- required launches (rs_mixed.hip) ----------------------------------
+// A ragged launch group whose patterns have their own row counts (ReconstructSome: a
+// missing shard nobody wants has no row). r is the launch group's own tile map, over the
+// stripes with a row in the group alone (tile0 still indexed by stripe); nrows[p] in 1..a.R
+// is how many of pattern p's rows the group holds. out_tab is pitched at a.R, and slots at
+// and past a stripe's row count hold nothing the kernel loads.
+struct RaggedSomeArgs {
+  RaggedArgs r;
+  const uint32_t* nrows;  // [P] rows of each pattern in this launch group
+};
+
+// (kOrderRequired + the TileOrder it runs in, always consecutive: rs_plan_forms of a required plan)
+constexpr int kOrderRequired = 2048;
+
+// Enqueues the launch group as launch_ragged does; r.ntiles == 0 enqueues nothing.
+hipError_t launch_ragged_some(ApplyArgs a, const RaggedSomeArgs& x, bool any_tail,
+                              hipStream_t stream, LaunchEvents ev = {});
+
 // Tiles per slice of a sliced launch (launch_apply's rule) for `streams` shard streams.
 uint32_t launch_slice_tiles(int streams);
 

@@ -36,9 +36,12 @@ using MixedPolicy = typename std::conditional<
 // stripe, its tile within the stripe, the stripe's pattern p and (in `a`) the stripe's S,
 // nvec and verify mask. Stages pattern p's tables into LDS, runs the S % 16 tail where
 // a.tail_in_vec places it, then the input ring, lookups, stores and compares.
-template <int RT, class P>
+// SOME (the required plans' kernel): a.R is the stripe's own row count and
+// out_stride the launch group's, the pitch of out_tab; rows at and past a.R have no pointer
+// there and none is loaded.
+template <int RT, class P, bool SOME = false>
 __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t stripe, uint32_t tile,
-                                           uint32_t p, uint32_t tab_stride) {
+                                           uint32_t p, uint32_t tab_stride, uint32_t out_stride = 0) {
   constexpr int BS = P::BS;
   constexpr int W = LdsAcc<RT>::W;
   static_assert(P::REALIGN == 0 && P::WIX == 0 && P::DMA == 0 && !P::NOMATH && !P::PERSIST && P::ORD == 0,
@@ -48,7 +51,7 @@ __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t
   const int R = a.R;
   const uint64_t v0 = static_cast<uint64_t>(tile) * BS + threadIdx.x;
   cptr<const uint8_t*> in = as_const(a.in_tab) + static_cast<size_t>(stripe) * K;
-  cptr<uint8_t*> out = as_const(a.out_tab) + static_cast<size_t>(stripe) * R;
+  cptr<uint8_t*> out = as_const(a.out_tab) + static_cast<size_t>(stripe) * (SOME ? out_stride : R);
   const bool active = v0 < a.nvec;
   auto ld = [&](int i) { return load16<P>(reinterpret_cast<const uint4*>(in[i]) + v0); };
   // The first input vectors go out before the table prologue: the prologue is a global
@@ -181,6 +184,31 @@ void rs_apply_ragged(ApplyArgs a, RaggedArgs x) {
   mixed_tile<RT, P>(a, smem, stripe, tile, p, x.tab_stride);
 }
 
+// Required launches: a ragged launch whose patterns have their own row
+// counts. The tile map is the launch group's own and holds only the stripes with a row in
+// the group; nrows[p] (wave-uniform, one more scalar load beside vmask[p]) is how many of
+// pattern p's rows the group holds, 1..R. out_tab keeps the group's pitch R, and the block
+// stores or compares rows [0, nrows[p]) alone -- in the vector body, the early compare
+// loads and the S % 16 tail alike: the slots past them hold no pointer.
+template <int RT, class P>
+__global__ __launch_bounds__(P::BS) __attribute__((amdgpu_waves_per_eu(P::WPE, lds_max_waves<RT>())))
+void rs_apply_ragged_some(ApplyArgs a, RaggedSomeArgs xs) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  static_assert(P::TILE_VECS == P::BS, "one vector per thread: the tile map counts 512-vector tiles");
+  const RaggedArgs& x = xs.r;
+  const uint32_t t = a.t_base + blockIdx.x;
+  if (t >= x.ntiles) return;  // block-uniform
+  const uint32_t stripe = as_const(x.tile_stripe)[t];
+  const uint32_t tile = t - as_const(x.tile0)[stripe];
+  const uint32_t p = as_const(x.pat)[stripe];
+  a.S = as_const(x.size)[stripe];
+  a.nvec = a.S / 16;
+  a.verify_mask = as_const(x.vmask)[p];
+  const uint32_t stride = static_cast<uint32_t>(a.R);
+  a.R = static_cast<int>(as_const(xs.nrows)[p]);
+  mixed_tile<RT, P, true>(a, smem, stripe, tile, p, x.tab_stride, stride);
+}
+
 // S < 16: one byte position per thread, 16 threads per stripe; the nibble tables are read
 // from the arena in global memory (a launch of batch * S bytes has nothing to amortise an
 // LDS prologue over). An RT instance (8 or 16: the entry width) serves every R <= RT.
@@ -228,6 +256,10 @@ using RaggedFn = void (*)(ApplyArgs, RaggedArgs);
 const std::array<RaggedFn, 3> kRagged = {&dev::rs_apply_ragged<4, dev::MixedPolicy<4>>,
                                          &dev::rs_apply_ragged<8, dev::MixedPolicy<8>>,
                                          &dev::rs_apply_ragged<16, dev::MixedPolicy<16>>};
+using RaggedSomeFn = void (*)(ApplyArgs, RaggedSomeArgs);
+const std::array<RaggedSomeFn, 3> kRaggedSome = {&dev::rs_apply_ragged_some<4, dev::MixedPolicy<4>>,
+                                                 &dev::rs_apply_ragged_some<8, dev::MixedPolicy<8>>,
+                                                 &dev::rs_apply_ragged_some<16, dev::MixedPolicy<16>>};
 static_assert(dev::MixedPolicy<4>::BS == 512 && dev::MixedPolicy<8>::BS == 512 &&
                   dev::MixedPolicy<16>::BS == 512 && dev::MixedPolicy<4>::TILE_VECS == 512 &&
                   dev::MixedPolicy<8>::TILE_VECS == 512 && dev::MixedPolicy<16>::TILE_VECS == 512,
@@ -236,7 +268,7 @@ constexpr uint32_t kMixedBlock = 512, kMixedTileVecs = 512;
 static_assert(kRaggedLaunchTileVecs == kMixedTileVecs, "the tile map counts the instances' tiles");
 
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
-// per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one)
+// per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one, 2 the required one)
 DeviceOnce g_mixed_wide_lds;
 
 // The vector launch both kinds share: the dynamic-LDS opt-in (`once_key`: 0 the mixed
@@ -296,6 +328,20 @@ hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, bool any_tail, hipStr
   // with no tail leave lds_tail at once
   a.tail_in_vec = any_tail ? 1u : 0u;
   return launch_tiles(kRagged[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 1, x.ntiles, a, x, stream, ev);
+}
+
+hipError_t launch_ragged_some(ApplyArgs a, const RaggedSomeArgs& x, bool any_tail,
+                              hipStream_t stream, LaunchEvents ev) {
+  const RaggedArgs& r = x.r;
+  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
+      !r.pat || !r.vmask || !r.size || !r.tile0 || !x.nrows || !a.in_tab || !a.out_tab ||
+      !a.status || r.ntiles > 0x7fffffffu || (r.ntiles && !r.tile_stripe))
+    return hipErrorInvalidValue;
+  if (r.ntiles == 0) return hipSuccess;  // no stripe has a row in this launch group
+  a.t_base = 0;
+  a.S = a.nvec = 0;  // per stripe, read by the kernel
+  a.tail_in_vec = any_tail ? 1u : 0u;
+  return launch_tiles(kRaggedSome[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 2, r.ntiles, a, x, stream, ev);
 }
 
 }  // namespace callfs

@@ -2,7 +2,7 @@
 // repeated, graph-capturable launches over shards in device memory -- uniform plans (one
 // erasure pattern, one shard size: every kernel form and tile order), mixed plans (a
 // pattern per stripe) and ragged plans (a shard size per stripe too,
-// §5.9) -- the tile-order tuner and the one-shot device calls built on them.
+// §5.9) and required plans (only the missing shards a caller wants, §5.10) -- the tile-order tuner and the one-shot device calls built on them.
 #include <cstdio>
 
 #include "mixed_tables.hpp"
@@ -19,6 +19,9 @@ static_assert(kRaggedTileVecs == kRaggedLaunchTileVecs, "the tile map counts the
 // A ragged plan (rs_plan_create_ragged) is a mixed plan with a tile map: `ragged` is set,
 // the plan's S is the largest shard size (never 0) and each stripe's own size sits in the
 // device buffer with tile0 and tile_stripe (ragged_tables.hpp).
+// A required plan (rs_plan_create_required) is a ragged plan whose patterns have their own
+// row counts: `some` is set, every launch group has its own tile map (g_*) and the patterns'
+// row counts inside it (nrows_off).
 struct MixedPlan {
   MixedTables t;
   size_t in_off = 0, pat_off = 0;
@@ -27,6 +30,10 @@ struct MixedPlan {
   bool any_tail = false;  // some stripe's size is no multiple of 16
   uint32_t ntiles = 0;
   size_t size_off = 0, tile0_off = 0, tile_stripe_off = 0;
+  bool some = false;
+  std::vector<size_t> nrows_off, g_tile0_off, g_tile_stripe_off;  // per launch group
+  std::vector<uint32_t> g_ntiles;
+  std::vector<uint8_t> g_any_tail;
 };
 
 struct rs_plan {
@@ -69,7 +76,8 @@ size_t plan_groups(const rs_plan& plan) {
 
 // The arguments of launch group gi. A mixed or ragged plan's per-stripe tables go to *x
 // (the MixedArgs fields, and the tile map of a ragged plan).
-ApplyArgs plan_group_args(const rs_plan& plan, size_t gi, RaggedArgs* x = nullptr) {
+ApplyArgs plan_group_args(const rs_plan& plan, size_t gi, RaggedArgs* x = nullptr,
+                          const uint32_t** nrows = nullptr) {
   auto* d = static_cast<uint8_t*>(plan.dmeta.p);
   if (!plan.mixed)
     return group_args(*plan.tables, plan.layout, gi, plan.batch, d, plan.S, 1, plan.hint);
@@ -95,6 +103,12 @@ ApplyArgs plan_group_args(const rs_plan& plan, size_t gi, RaggedArgs* x = nullpt
       x->tile_stripe = reinterpret_cast<const uint32_t*>(d + mp.tile_stripe_off);
       x->ntiles = mp.ntiles;
     }
+    if (mp.some) {  // the launch group's own tile map
+      x->tile0 = reinterpret_cast<const uint32_t*>(d + mp.g_tile0_off[gi]);
+      x->tile_stripe = reinterpret_cast<const uint32_t*>(d + mp.g_tile_stripe_off[gi]);
+      x->ntiles = mp.g_ntiles[gi];
+      if (nrows) *nrows = reinterpret_cast<const uint32_t*>(d + mp.nrows_off[gi]);
+    }
   }
   return a;
 }
@@ -109,9 +123,13 @@ hipError_t plan_launch(const rs_plan& plan, hipStream_t s, const std::vector<int
   const size_t ng = plan_groups(plan);
   for (size_t gi = 0; gi < ng; ++gi) {
     RaggedArgs r{};
-    const ApplyArgs a = plan_group_args(plan, gi, &r);
+    const uint32_t* nrows = nullptr;
+    const ApplyArgs a = plan_group_args(plan, gi, &r, &nrows);
     const LaunchEvents g = group_events(ev, gi, ng);
-    const hipError_t e = plan.mixed->ragged
+    const hipError_t e = plan.mixed->some
+                             ? launch_ragged_some(a, RaggedSomeArgs{r, nrows},
+                                                  plan.mixed->g_any_tail[gi] != 0, s, g)
+                         : plan.mixed->ragged
                              ? launch_ragged(a, r, plan.mixed->any_tail, s, g)
                              : launch_mixed(a, MixedArgs{r.pat, r.vmask, r.tab_stride}, s, g);
     if (e != hipSuccess) return e;
@@ -133,8 +151,11 @@ std::unique_ptr<rs_plan> new_plan(int device, size_t S, int batch) {
 // Lays out and uploads the device buffer of a mixed plan (plan.mixed->t built, plan.device
 // and plan.batch set): the status words, the shard-pointer tables, pat and per launch group
 // the compare masks and the table arena, each piece 256-B aligned. With `rg` (a ragged plan)
-// also the stripes' sizes, tile0 and tile_stripe.
-int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rg) {
+// also the stripes' sizes, tile0 and tile_stripe. With `rq` (a required plan) the sizes and
+// per launch group its tile map and the patterns' row counts; an out_tab slot at or past a
+// stripe's row count holds null, and a shard no row names is in no table.
+int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rg,
+                 const RequiredTables* rq = nullptr) {
   MixedPlan& mp = *plan.mixed;
   const int k = mp.t.k, n = mp.t.k + mp.t.m, batch = plan.batch;
   Packer pk;
@@ -152,6 +173,17 @@ int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rg) 
     mp.tile0_off = pk.take(sizeof(uint32_t) * rg->tile0.size());
     mp.tile_stripe_off = pk.take(sizeof(uint32_t) * rg->tile_stripe.size());
   }
+  if (rq) {
+    mp.size_off = pk.take(sizeof(uint64_t) * rq->size.size());
+    for (size_t gi = 0; gi < mp.t.groups.size(); ++gi) {
+      const GroupTileMap& gm = rq->maps[gi];
+      mp.nrows_off.push_back(pk.take(sizeof(uint32_t) * P));
+      mp.g_tile0_off.push_back(pk.take(sizeof(uint32_t) * gm.tile0.size()));
+      mp.g_tile_stripe_off.push_back(pk.take(sizeof(uint32_t) * std::max<size_t>(1, gm.tile_stripe.size())));
+      mp.g_ntiles.push_back(gm.ntiles);
+      mp.g_any_tail.push_back(gm.any_tail);
+    }
+  }
   std::vector<uint8_t> h(pk.off, 0);
   auto shard_ptr = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
   auto* in = reinterpret_cast<const uint8_t**>(h.data() + mp.in_off);
@@ -166,7 +198,8 @@ int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rg) 
     for (int b = 0; b < batch; ++b) {
       const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
       for (int r = 0; r < g.R; ++r)
-        o[static_cast<size_t>(b) * g.R + r] = shard_ptr(b, pt.rows[g.row0 + r]);
+        o[static_cast<size_t>(b) * g.R + r] =
+            static_cast<size_t>(g.row0 + r) < pt.rows.size() ? shard_ptr(b, pt.rows[g.row0 + r]) : nullptr;
     }
     std::memcpy(h.data() + mp.vmask_off[gi], g.vmask.data(), sizeof(uint32_t) * P);
     std::memcpy(h.data() + mp.arena_off[gi], g.arena.data(), g.arena.size());
@@ -176,6 +209,17 @@ int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rg) 
     std::memcpy(h.data() + mp.tile0_off, rg->tile0.data(), sizeof(uint32_t) * rg->tile0.size());
     std::memcpy(h.data() + mp.tile_stripe_off, rg->tile_stripe.data(),
                 sizeof(uint32_t) * rg->tile_stripe.size());
+  }
+  if (rq) {
+    std::memcpy(h.data() + mp.size_off, rq->size.data(), sizeof(uint64_t) * rq->size.size());
+    for (size_t gi = 0; gi < mp.t.groups.size(); ++gi) {
+      const GroupTileMap& gm = rq->maps[gi];
+      std::memcpy(h.data() + mp.nrows_off[gi], mp.t.groups[gi].nrows.data(), sizeof(uint32_t) * P);
+      std::memcpy(h.data() + mp.g_tile0_off[gi], gm.tile0.data(), sizeof(uint32_t) * gm.tile0.size());
+      if (!gm.tile_stripe.empty())
+        std::memcpy(h.data() + mp.g_tile_stripe_off[gi], gm.tile_stripe.data(),
+                    sizeof(uint32_t) * gm.tile_stripe.size());
+    }
   }
   if (const int rc = upload(plan.dmeta, plan.device, h.data(), h.size())) return rc;
   // the device copy is all a launch reads: the host arenas can go
@@ -230,6 +274,12 @@ int launch_once(rs_plan* p, void* stream) {
   return rc;
 }
 
+// rs_plan_create's body. wanted (k+m flags, or null: every missing shard): the missing shards
+// that get a row; a plan with no row at all has no launch group.
+int create_uniform(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
+                   const uint8_t* present, const uint8_t* wanted, uint8_t* const* shards,
+                   rs_plan** out);
+
 int one_shot(rs_ctx* ctx, int device, int k, int m, size_t S, int batch, const uint8_t* present,
              uint8_t* const* shards, void* stream) {
   rs_plan* p = nullptr;
@@ -240,12 +290,11 @@ int one_shot(rs_ctx* ctx, int device, int k, int m, size_t S, int batch, const u
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-// ---- constructors ---------------------------------------------------------------------------
-
-int rs_plan_create(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
-                   const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
+int create_uniform(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
+                   const uint8_t* present, const uint8_t* wanted, uint8_t* const* shards,
+                   rs_plan** out) {
   DeviceGuard dg;
   int rc = check_profile(k, m);
   if (rc) return rc;
@@ -261,14 +310,17 @@ int rs_plan_create(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
     np += pres[i];
   }
   if (np < k) return RS_E_TOO_FEW_SHARDS;
-  auto t = ctx->cache.get(k, m, pres, true);
+  auto t = ctx->cache.get(k, m, pres, true, wanted);
   if (!t) return RS_E_SINGULAR;
   auto plan = new_plan(device, S, batch);
   plan->tables = t;
   plan->layout = meta_layout(*t, batch);
   plan->status_off = plan->layout.status_off;
   // reads: k valid shards + compared parity; writes: missing shards.
-  plan->bytes = static_cast<uint64_t>(batch) * S * (t->k + t->check.size() + t->missing.size());
+  // (a plan with no row reads nothing)
+  plan->bytes = t->groups.empty()
+                    ? 0
+                    : static_cast<uint64_t>(batch) * S * (t->k + t->check.size() + t->missing.size());
   std::vector<uint8_t> h(plan->layout.total);
   plan->hint = fill_meta(*t, plan->layout, batch, h.data(), [&](int b, int i) {
     return static_cast<const uint8_t*>(shards[static_cast<size_t>(b) * n + i]);
@@ -292,6 +344,17 @@ int rs_plan_create(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
   }
   *out = plan.release();
   return RS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- constructors ---------------------------------------------------------------------------
+
+int rs_plan_create(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
+                   const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
+  return create_uniform(ctx, device, k, m, S, batch, present, nullptr, shards, out);
 }
 
 int rs_plan_create_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
@@ -377,6 +440,53 @@ int rs_plan_create_ragged(rs_ctx* ctx, int device, int k, int m, int batch, cons
   return RS_OK;
 }
 
+int rs_plan_create_required(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                            const uint8_t* present, const uint8_t* required,
+                            uint8_t* const* shards, rs_plan** out) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !sizes || !shards || !out || batch < 1) return RS_E_ARG;
+  *out = nullptr;
+  const int n = k + m;
+  // nothing to leave out (no masks: every stripe an encode): exactly the ragged plan
+  if (!required || !present || required_all_wanted(n, batch, present, required))
+    return rs_plan_create_ragged(ctx, device, k, m, batch, sizes, present, shards, out);
+  for (int b = 0; b < batch; ++b)
+    if (sizes[b] == 0) return RS_E_NO_DATA;
+  for (int b = 0; b < batch; ++b) {
+    int np = 0;
+    for (int i = 0; i < n; ++i) np += present[static_cast<size_t>(b) * n + i] != 0;
+    if (np < k) return RS_E_TOO_FEW_SHARDS;
+  }
+  // one size, one (mask, wanted) pair: the uniform plan over the wanted rows
+  if (ragged_sizes_equal(batch, sizes) && required_pairs_equal(n, batch, present, required))
+    return create_uniform(ctx, device, k, m, sizes[0], batch, present, required, shards, out);
+  Device* dev = ctx->device(device);
+  if (!dev) return RS_E_ARG;
+  RequiredTables rq;
+  switch (build_required_tables(k, m, batch, sizes, present, required, rq)) {
+    case RaggedError::kOk: break;
+    case RaggedError::kNoData: return RS_E_NO_DATA;
+    case RaggedError::kTooManyTiles: return RS_E_ARG;
+    case RaggedError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
+    case RaggedError::kSingular: return RS_E_SINGULAR;
+  }
+  auto plan = new_plan(device, *std::max_element(sizes, sizes + batch), batch);
+  plan->mixed = std::make_unique<MixedPlan>();
+  plan->fixed_form = kOrderRequired + RS_ORDER_CONSECUTIVE;
+  MixedPlan& mp = *plan->mixed;
+  mp.t = std::move(rq.mixed);
+  mp.ragged = true;
+  mp.some = true;
+  // per stripe with a row: the k shards read, the rows written and the rows compared
+  plan->bytes = rq.bytes;
+  rc = upload_mixed(*plan, shards, nullptr, &rq);
+  if (rc) return rc;
+  *out = plan.release();
+  return RS_OK;
+}
+
 void rs_plan_destroy(rs_plan* plan) {
   DeviceGuard dg;
   delete plan;
@@ -392,7 +502,7 @@ int rs_plan_launch_timed(rs_plan* plan, void* stream, void* start_event, void* s
   DeviceGuard dg;
   if (!plan) return RS_E_ARG;
   HIPCHK(hipSetDevice(plan->device));
-  if (plan->S == 0)  // nothing dispatches: the events still bracket this (empty) launch
+  if (plan->S == 0 || plan_groups(*plan) == 0)  // nothing dispatches: the events still bracket this (empty) launch
     return record_empty(stream, start_event, stop_event);
   LaunchEvents ev;
   ev.start = static_cast<hipEvent_t>(start_event);
@@ -624,6 +734,16 @@ int rs_decode_dev_ragged(rs_ctx* ctx, int device, int k, int m, int batch, const
                          const uint8_t* present, uint8_t* const* shards, void* stream) {
   rs_plan* p = nullptr;
   const int rc = rs_plan_create_ragged(ctx, device, k, m, batch, sizes, present, shards, &p);
+  if (rc) return rc;
+  return launch_once(p, stream);
+}
+
+int rs_decode_dev_required(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                           const uint8_t* present, const uint8_t* required,
+                           uint8_t* const* shards, void* stream) {
+  rs_plan* p = nullptr;
+  const int rc = rs_plan_create_required(ctx, device, k, m, batch, sizes, present, required,
+                                         shards, &p);
   if (rc) return rc;
   return launch_once(p, stream);
 }

@@ -258,12 +258,16 @@ class Plan:
 
     @classmethod
     def ragged(cls, k: int, m: int, sizes: Sequence[int], pointers: Sequence[int],
-               present=None, device: int = 0, context: Optional[N.Context] = None) -> "Plan":
+               present=None, device: int = 0, context: Optional[N.Context] = None,
+               required=None) -> "Plan":
         """rs_plan_create_ragged: stripe b's shards are sizes[b] bytes; one
         launch encodes, repairs and verifies stripes of different shard sizes. present: None
         (every stripe an encode) or batch rows of k+m flags. The plan's S is None and its
         sizes are kept; when all sizes are equal the library builds the mixed (or uniform)
-        plan of that size."""
+        plan of that size.
+        required: None, or batch rows of k+m flags beside present's
+        (rs_plan_create_required): a missing shard whose flag is clear is
+        neither rebuilt nor touched (its pointer may be 0)."""
         n, batch = k + m, len(sizes)
         if len(pointers) != batch * n:
             raise ValueError("need batch*(k+m) shard pointers")
@@ -273,6 +277,12 @@ class Plan:
             if rows is None or len(rows) != batch or any(len(r) != n for r in rows):
                 raise ValueError("present: None, or batch rows of k+m flags")
             pres = (ctypes.c_uint8 * (batch * n))(*[1 if p else 0 for r in rows for p in r])
+        req = None
+        if required is not None:
+            rows = _mask_rows(required)
+            if rows is None or len(rows) != batch or any(len(r) != n for r in rows):
+                raise ValueError("required: None, or batch rows of k+m flags")
+            req = (ctypes.c_uint8 * (batch * n))(*[1 if p else 0 for r in rows for p in r])
         self = cls.__new__(cls)
         self.ctx = context or N.default_context()
         self.k, self.m, self.S, self.batch, self.device = k, m, None, batch, device
@@ -281,15 +291,20 @@ class Plan:
         ptrs = (ctypes.c_void_p * max(1, len(pointers)))(*pointers)
         szs = (ctypes.c_size_t * max(1, batch))(*self.sizes)
         h = ctypes.c_void_p()
-        N.check(N.lib.rs_plan_create_ragged(self.ctx.handle, device, k, m, batch, szs, pres, ptrs,
-                                            ctypes.byref(h)), "rs_plan_create_ragged")
+        if req is not None:
+            N.check(N.lib.rs_plan_create_required(self.ctx.handle, device, k, m, batch, szs, pres,
+                                                  req, ptrs, ctypes.byref(h)),
+                    "rs_plan_create_required")
+        else:
+            N.check(N.lib.rs_plan_create_ragged(self.ctx.handle, device, k, m, batch, szs, pres,
+                                                ptrs, ctypes.byref(h)), "rs_plan_create_ragged")
         self.handle = h
         return self
 
     @classmethod
-    def for_ragged(cls, rb: "RaggedBatch", present=None, context=None) -> "Plan":
+    def for_ragged(cls, rb: "RaggedBatch", present=None, context=None, required=None) -> "Plan":
         dev = rb.device.index if rb.device.index is not None else 0
-        return cls.ragged(rb.k, rb.m, rb.sizes, rb.pointers(), present, dev, context)
+        return cls.ragged(rb.k, rb.m, rb.sizes, rb.pointers(), present, dev, context, required)
 
     @property
     def bytes(self) -> int:
@@ -344,7 +359,7 @@ class Plan:
                    166: "realign64-x32", 192: "dma", 194: "dma-g2", 195: "dma-q8",
                    198: "dma-x32", 224: "tridb-g4", 225: "tridb-g8", 256: "bs", 257: "bs-g8",
                    258: "bs-g2", 259: "bs-q8", 260: "bs-q16", 261: "bs-x8", 262: "bs-x32",
-                   512: "mixed", 1024: "ragged"}
+                   512: "mixed", 1024: "ragged", 2048: "required"}
 
     def tune(self, reps: int = 5, stream: Optional[torch.cuda.Stream] = None) -> list:
         """rs_plan_tune: time each launch group in every tile order its kernel offers

@@ -200,10 +200,13 @@ class Codec:
             raise _wrapped(rc, "erasure: failed to encode parity")
         return shards
 
-    def decode(self, shards: List, profile: ErasureProfile, original_size: int) -> bytearray:
+    def decode(self, shards: List, profile: ErasureProfile, original_size: int,
+               data_only: bool = False) -> bytearray:
         """codec.go:45-78. `None` or empty entries are missing shards; they are
         reconstructed in place (the list is mutated, as Go mutates its [][]byte).
-        Returns a fresh buffer of original_size bytes (Go: buf[:originalSize])."""
+        Returns a fresh buffer of original_size bytes (Go: buf[:originalSize]).
+        data_only: rs_codec_decode_data (upstream ReconstructData in Reconstruct's place):
+        the same bytes and errors, but missing parity shards are not rebuilt and stay None."""
         k, m = profile.data_shards, profile.parity_shards
         if k < 1 or m < 1:
             raise ErrInvalidProfile()
@@ -218,19 +221,20 @@ class Codec:
         S = next((lens[i] for i in range(n) if lens[i]), 0)
         bufs = list(shards)
         for i in range(n):
-            if lens[i] == 0 and S:
+            if lens[i] == 0 and S and (i < k or not data_only):
                 bufs[i] = bytearray(S)  # upstream Reconstruct allocates missing shards
         ptrs = (ctypes.c_void_p * n)(*[_addr(b) if b is not None and len(b) else 0
                                       for b in bufs])
         out = bytearray(max(int(original_size), 0))
-        rc = N.lib.rs_codec_decode(self.context.handle, k, m, ptrs, lens,
-                                   _addr(out) if out else None, int(original_size))
+        fn = N.lib.rs_codec_decode_data if data_only else N.lib.rs_codec_decode
+        rc = fn(self.context.handle, k, m, ptrs, lens, _addr(out) if out else None,
+                int(original_size))
         # upstream Reconstruct (codec.go:55) has filled the nil entries before Verify
         # (:59) and the join-length check (:73) can fail, so ErrShardCorrupted and
         # ErrInsufficientShards leave them filled too (as the Go shim does)
         if rc in (N.RS_OK, N.RS_E_CORRUPT, N.RS_E_INSUFFICIENT):
             for i in range(n):
-                if shards[i] is None or len(shards[i]) == 0:
+                if (shards[i] is None or len(shards[i]) == 0) and lens[i]:
                     shards[i] = bufs[i]
         if rc == N.RS_OK:
             return out
@@ -274,14 +278,15 @@ class Codec:
         return shards, errors
 
     def decode_many(self, shards_per_object: Sequence[List], profile: ErasureProfile,
-                    original_sizes: Sequence[int]
+                    original_sizes: Sequence[int], data_only: bool = False
                     ) -> Tuple[List[Optional[bytearray]], List[Optional[Exception]]]:
         """Codec.decode for many objects of one profile in one native call
         (rs_codec_decode_batch: Reconstruct, Verify and the join / trim of every object in one
         pipeline). Returns (objects, errors): errors[b] is None and objects[b] the
         original_sizes[b] bytes of object b, or errors[b] is an instance of the class and
         message decode() would have raised for that object and objects[b] is None. Each shard
-        list is mutated as decode() mutates it. Profile errors raise."""
+        list is mutated as decode() mutates it. Profile errors raise.
+        data_only: rs_codec_decode_data_batch, as decode(data_only=True) per object."""
         k, m = profile.data_shards, profile.parity_shards
         if k < 1 or m < 1:
             raise ErrInvalidProfile()
@@ -310,15 +315,16 @@ class Codec:
             cp = list(shards)
             for i in range(n):
                 lens[j * n + i] = ln[i]
-                if ln[i] == 0 and S:
+                if ln[i] == 0 and S and (i < k or not data_only):
                     cp[i] = bytearray(S)  # upstream Reconstruct allocates missing shards
             bufs.append(cp)
             flat += cp
             outs.append(bytearray(int(original_sizes[b])))
         sizes = (ctypes.c_int64 * max(R, 1))(*[int(original_sizes[b]) for b in run])
         status = (ctypes.c_int * max(R, 1))()
-        rc = N.lib.rs_codec_decode_batch(self.context.handle, k, m, R, _shard_ptrs(flat or [None]),
-                                         lens, _shard_ptrs(outs or [None]), sizes, status)
+        fn = N.lib.rs_codec_decode_data_batch if data_only else N.lib.rs_codec_decode_batch
+        rc = fn(self.context.handle, k, m, R, _shard_ptrs(flat or [None]), lens,
+                _shard_ptrs(outs or [None]), sizes, status)
         st = list(status)[:R]
         if rc != N.RS_OK and rc not in st:
             raise N.NativeError(rc, "rs_codec_decode_batch")  # call-level
@@ -327,7 +333,7 @@ class Codec:
             shards = shards_per_object[b]
             if st[j] in (N.RS_OK, N.RS_E_CORRUPT, N.RS_E_INSUFFICIENT):
                 for i in range(n):
-                    if shards[i] is None or len(shards[i]) == 0:
+                    if (shards[i] is None or len(shards[i]) == 0) and lens[j * n + i]:
                         shards[i] = bufs[j][i]
             if st[j] == N.RS_OK:
                 objects[b] = outs[j]
@@ -376,6 +382,28 @@ def reconstruct(shards: List, k: int, m: int, context: Optional[N.Context] = Non
             shards[i] = bufs[i]
 
 
+def reconstruct_some(shards: List, k: int, m: int, required: Sequence[bool],
+                     context: Optional[N.Context] = None) -> None:
+    """upstream enc.ReconstructSome(shards, required): only the missing entries whose flag in
+    `required` (k+m flags) is set are rebuilt and replaced; the others stay missing."""
+    ctx = context or N.default_context()
+    n = k + m
+    if len(shards) != n:
+        raise ErrTooFewShards()
+    if len(required) != n:
+        raise ValueError("required needs k+m flags")
+    lens = (ctypes.c_size_t * n)(*[0 if s is None else len(s) for s in shards])
+    S = next((lens[i] for i in range(n) if lens[i]), 0)
+    bufs = [bytearray(S) if (lens[i] == 0 and S and required[i]) else shards[i] for i in range(n)]
+    req = (ctypes.c_uint8 * n)(*[1 if r else 0 for r in required])
+    rc = N.lib.rs_reconstruct_some(ctx.handle, k, m, _shard_ptrs(bufs), lens, req)
+    if rc != N.RS_OK:
+        raise _wrapped(rc, "reconstruct")
+    for i in range(n):
+        if (shards[i] is None or len(shards[i]) == 0) and lens[i]:
+            shards[i] = bufs[i]
+
+
 def verify(shards: List, k: int, m: int, context: Optional[N.Context] = None) -> bool:
     """upstream enc.Verify(shards) (codec.go:59)."""
     ctx = context or N.default_context()
@@ -419,16 +447,20 @@ def encode_batch(stripes: Sequence[Sequence], k: int, m: int,
 
 
 def reconstruct_batch(stripes: List[List], k: int, m: int, verify: bool = True,
-                      context: Optional[N.Context] = None) -> List[int]:
+                      context: Optional[N.Context] = None, required=None) -> List[int]:
     """rs_reconstruct_batch: stripes[b] is an n-list of shards (None / empty = missing),
     reconstructed in place like reconstruct(); with verify the present parity beyond the
     first k is re-checked per stripe. Returns status[b] (RS_OK, RS_E_CORRUPT,
-    RS_E_TOO_FEW_SHARDS, RS_E_SHARD_SIZE, RS_E_NO_DATA, ...)."""
+    RS_E_TOO_FEW_SHARDS, RS_E_SHARD_SIZE, RS_E_NO_DATA, ...).
+    required: None, or per stripe k+m flags (rs_reconstruct_some_batch): only the missing
+    entries whose flag is set are rebuilt and replaced."""
     ctx = context or N.default_context()
     n = k + m
     B = len(stripes)
     if any(len(st) != n for st in stripes):
         raise ErrTooFewShards()
+    if required is not None and (len(required) != B or any(len(r) != n for r in required)):
+        raise ValueError("required: None, or one row of k+m flags per stripe")
     # missing entries get fresh buffers in a per-stripe copy (upstream Reconstruct
     # allocates them); the caller's lists change only for stripes that succeeded
     flat, lens, bufs = [], (ctypes.c_size_t * max(B * n, 1))(), []
@@ -438,13 +470,18 @@ def reconstruct_batch(stripes: List[List], k: int, m: int, verify: bool = True,
         cp = list(st)
         for i in range(n):
             lens[b * n + i] = ln[i]
-            if ln[i] == 0 and S:
+            if ln[i] == 0 and S and (required is None or required[b][i]):
                 cp[i] = bytearray(S)
         bufs.append(cp)
         flat += cp
     status = (ctypes.c_int * max(B, 1))()
-    rc = N.lib.rs_reconstruct_batch(ctx.handle, k, m, B, _shard_ptrs(flat or [None]), lens,
-                                    int(verify), status)
+    if required is None:
+        rc = N.lib.rs_reconstruct_batch(ctx.handle, k, m, B, _shard_ptrs(flat or [None]), lens,
+                                        int(verify), status)
+    else:
+        req = (ctypes.c_uint8 * max(B * n, 1))(*[1 if f else 0 for r in required for f in r])
+        rc = N.lib.rs_reconstruct_some_batch(ctx.handle, k, m, B, _shard_ptrs(flat or [None]), lens,
+                                             req, int(verify), status)
     if rc < 0 and rc not in (N.RS_E_CORRUPT, N.RS_E_TOO_FEW_SHARDS, N.RS_E_SHARD_SIZE,
                              N.RS_E_NO_DATA):
         if not (rc == N.RS_E_ARG and any(s == N.RS_E_ARG for s in list(status)[:B])):
@@ -453,7 +490,7 @@ def reconstruct_batch(stripes: List[List], k: int, m: int, verify: bool = True,
     for b, st in enumerate(stripes):
         if out[b] in (N.RS_OK, N.RS_E_CORRUPT):
             for i in range(n):
-                if st[i] is None or len(st[i]) == 0:
+                if (st[i] is None or len(st[i]) == 0) and lens[b * n + i]:
                     st[i] = bufs[b][i]
     return out
 

@@ -45,6 +45,41 @@ func (c *Codec) DecodeBatch(shards [][][]byte, profile ErasureProfile, sizes []i
 	return out, errs
 }
 
+// DecodeData is Decode with upstream ReconstructData in Reconstruct's place: missing data
+// shards are rebuilt and joined, missing parity shards stay nil (the GPU build runs
+// rs_codec_decode_data, codec_rocm.go).
+func (c *Codec) DecodeData(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, error) {
+	return cpuDecodeData(shards, profile, originalSize)
+}
+
+// DecodeDataBatch is DecodeData per object on builds without the GPU codec.
+func (c *Codec) DecodeDataBatch(shards [][][]byte, profile ErasureProfile, sizes []int64) ([][]byte, []error) {
+	out := make([][]byte, len(shards))
+	errs := make([]error, len(shards))
+	for b := range shards {
+		if len(sizes) != len(shards) {
+			errs[b] = fmt.Errorf("erasure: %d sizes for %d objects", len(sizes), len(shards))
+			continue
+		}
+		out[b], errs[b] = cpuDecodeData(shards[b], profile, sizes[b])
+	}
+	return out, errs
+}
+
+// RepairSome is upstream ReconstructSome per object on builds without the GPU codec:
+// want[b] (nil: every missing shard) names the entries of objs[b] to rebuild.
+func (c *Codec) RepairSome(objs [][][]byte, want [][]bool, profile ErasureProfile) []error {
+	errs := make([]error, len(objs))
+	for b, shards := range objs {
+		var w []bool
+		if want != nil {
+			w = want[b]
+		}
+		errs[b] = cpuRepairSome(shards, w, profile.DataShards, profile.ParityShards)
+	}
+	return errs
+}
+
 // The pinned-buffer helpers of the GPU build (codec_rocm.go) exist here too, so callers
 // compile on every build: there is no device, so HostBuffer and BodyBuffer return nil
 // (read into heap buffers as before), FreeHostBuffer ignores its argument and DecodePinned

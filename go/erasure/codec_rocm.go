@@ -239,7 +239,17 @@ func split(data []byte, k, m int) [][]byte {
 // ErrTooFewShards / ErrShardSize / ErrShardNoData leaves the caller's slice exactly as
 // it was (codec_test.go:65-88).
 func (c *Codec) Decode(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, error) {
-	return c.decode(shards, profile, originalSize, false)
+	return c.decode(shards, profile, originalSize, false, false)
+}
+
+// DecodeData is Decode for callers that keep the joined object alone (RetrieveFile,
+// manager.go:250-320): rs_codec_decode_data, upstream ReconstructData in Reconstruct's
+// place. Missing data shards are rebuilt, filled and joined; missing parity shards stay nil
+// and get no buffer; the present shards beyond the first k are verified as in Decode, and
+// the errors are Decode's. An object whose k data shards are all present and that has
+// nothing to verify costs a copy and no GPU work. Not in the reference API.
+func (c *Codec) DecodeData(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, error) {
+	return c.decode(shards, profile, originalSize, false, true)
 }
 
 // DecodePinned is Decode for shards fetched into HostBuffers (manager.go:473,530 reading
@@ -253,16 +263,19 @@ func (c *Codec) Decode(shards [][]byte, profile ErasureProfile, originalSize int
 // Decode (heap buffers, FreeHostBuffer ignores them).
 // Not in the reference API: an addition for servers that read into pinned buffers.
 func (c *Codec) DecodePinned(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, error) {
-	return c.decode(shards, profile, originalSize, true)
+	return c.decode(shards, profile, originalSize, true, false)
 }
 
-func (c *Codec) decode(shards [][]byte, profile ErasureProfile, originalSize int64, pinned bool) ([]byte, error) {
+func (c *Codec) decode(shards [][]byte, profile ErasureProfile, originalSize int64, pinned, dataOnly bool) ([]byte, error) {
 	k, m := profile.DataShards, profile.ParityShards
 	if k < 1 || m < 1 {
 		return nil, ErrInvalidProfile
 	}
 	n := k + m
 	if n > 256 || originalSize < int64(gpuMinBytes) || device() == nil {
+		if dataOnly {
+			return cpuDecodeData(shards, profile, originalSize)
+		}
 		return c.cpuDecode(shards, profile, originalSize)
 	}
 	alloc := func(size int) []byte { return make([]byte, size) }
@@ -299,7 +312,7 @@ func (c *Codec) decode(shards [][]byte, profile ErasureProfile, originalSize int
 	defer pin.Unpin()
 	for i := range bufs {
 		*lensAt(i) = C.size_t(len(bufs[i]))
-		if len(bufs[i]) == 0 && S > 0 {
+		if len(bufs[i]) == 0 && S > 0 && (i < k || !dataOnly) {
 			if cap(bufs[i]) >= S {
 				bufs[i] = bufs[i][:S]
 			} else {
@@ -317,13 +330,19 @@ func (c *Codec) decode(shards [][]byte, profile ErasureProfile, originalSize int
 		pin.Pin(&buf[0])
 		out = (*C.uint8_t)(unsafe.Pointer(&buf[0]))
 	}
-	rc := C.rs_codec_decode(gpuCtx, C.int(k), C.int(m), ptrs.at(0), lens, out, C.int64_t(originalSize))
+	var rc C.int
+	if dataOnly {
+		rc = C.rs_codec_decode_data(gpuCtx, C.int(k), C.int(m), ptrs.at(0), lens, out, C.int64_t(originalSize))
+	} else {
+		rc = C.rs_codec_decode(gpuCtx, C.int(k), C.int(m), ptrs.at(0), lens, out, C.int64_t(originalSize))
+	}
 	handed := map[*byte]bool{}
 	switch rc {
 	case C.RS_OK, C.RS_E_CORRUPT, C.RS_E_INSUFFICIENT:
-		// Reconstruct ran: upstream has filled the nil entries by now (codec.go:55)
+		// Reconstruct ran: upstream has filled the nil entries by now (codec.go:55); with
+		// dataOnly the rebuilt ones are those whose length the call set
 		for i := range shards {
-			if len(shards[i]) == 0 {
+			if len(shards[i]) == 0 && *lensAt(i) != 0 {
 				shards[i] = bufs[i]
 				handed[unsafe.SliceData(bufs[i])] = true
 			}
@@ -350,8 +369,21 @@ func (c *Codec) decode(shards [][]byte, profile ErasureProfile, originalSize int
 // (Verify of the present parity beyond the first k included). Not in the reference
 // API: an addition for bulk callers, no existing caller changes.
 func (c *Codec) RepairBatch(objs [][][]byte, profile ErasureProfile) []error {
+	return c.RepairSome(objs, nil, profile)
+}
+
+// RepairSome is RepairBatch for callers that want some shards back, not all (upstream
+// ReconstructSome; rs_reconstruct_some_batch): a repair job after a dead instance fetches k
+// shards per object and wants the one shard index that instance held. want[b] has n flags
+// naming the entries of objs[b] to rebuild; want == nil or want[b] == nil means every missing
+// entry. Entries that are missing and not wanted stay nil: no buffer, no write. Verify of the
+// present shards beyond the first k and the errors are RepairBatch's. Not in the reference API.
+func (c *Codec) RepairSome(objs [][][]byte, want [][]bool, profile ErasureProfile) []error {
 	k, m := profile.DataShards, profile.ParityShards
 	errs := make([]error, len(objs))
+	wanted := func(b, i int) bool {
+		return want == nil || b >= len(want) || want[b] == nil || (i < len(want[b]) && want[b][i])
+	}
 	if k < 1 || m < 1 {
 		for b := range errs {
 			errs[b] = ErrInvalidProfile
@@ -364,7 +396,11 @@ func (c *Codec) RepairBatch(objs [][][]byte, profile ErasureProfile) []error {
 	}
 	if n > 256 || device() == nil {
 		for b, shards := range objs {
-			errs[b] = cpuRepair(shards, k, m)
+			if want == nil || b >= len(want) || want[b] == nil {
+				errs[b] = cpuRepair(shards, k, m)
+			} else {
+				errs[b] = cpuRepairSome(shards, want[b], k, m)
+			}
 		}
 		return errs
 	}
@@ -372,6 +408,7 @@ func (c *Codec) RepairBatch(objs [][][]byte, profile ErasureProfile) []error {
 	ptrs := newCArray(len(objs) * n)
 	defer ptrs.free()
 	lens := make([]C.size_t, len(objs)*n) // Go memory without Go pointers: may be passed
+	req := make([]C.uint8_t, len(objs)*n)
 	status := make([]C.int, len(objs))
 	var pin runtime.Pinner
 	defer pin.Unpin()
@@ -391,7 +428,10 @@ func (c *Codec) RepairBatch(objs [][][]byte, profile ErasureProfile) []error {
 		copy(bufs[b], shards)
 		for i, s := range bufs[b] {
 			lens[b*n+i] = C.size_t(len(s))
-			if len(s) == 0 && S > 0 {
+			if wanted(b, i) {
+				req[b*n+i] = 1
+			}
+			if len(s) == 0 && S > 0 && wanted(b, i) {
 				s = make([]byte, S)
 				bufs[b][i] = s
 			}
@@ -401,8 +441,8 @@ func (c *Codec) RepairBatch(objs [][][]byte, profile ErasureProfile) []error {
 			}
 		}
 	}
-	rc := C.rs_reconstruct_batch(gpuCtx, C.int(k), C.int(m), C.int(len(objs)), ptrs.at(0),
-		&lens[0], 1, &status[0])
+	rc := C.rs_reconstruct_some_batch(gpuCtx, C.int(k), C.int(m), C.int(len(objs)), ptrs.at(0),
+		&lens[0], &req[0], 1, &status[0])
 	stripeArg := false // RS_E_ARG is per-stripe only when some stripe reports it
 	for _, st := range status {
 		stripeArg = stripeArg || st == C.RS_E_ARG
@@ -426,7 +466,7 @@ func (c *Codec) RepairBatch(objs [][][]byte, profile ErasureProfile) []error {
 		st := status[b]
 		if st == C.RS_OK || st == C.RS_E_CORRUPT {
 			for i := range shards {
-				if len(shards[i]) == 0 {
+				if len(shards[i]) == 0 && lens[b*n+i] != 0 {
 					shards[i] = bufs[b][i]
 				}
 			}
@@ -536,6 +576,18 @@ func hasStatus(status []C.int, rc C.int) bool {
 // (errs[b] nil, ErrShardCorrupted or ErrInsufficientShards) and left alone otherwise. Not in
 // the reference API: an addition for bulk callers.
 func (c *Codec) DecodeBatch(shards [][][]byte, profile ErasureProfile, sizes []int64) ([][]byte, []error) {
+	return c.decodeBatch(shards, profile, sizes, false)
+}
+
+// DecodeDataBatch is DecodeData for many objects of one profile in one call
+// (rs_codec_decode_data_batch): DecodeBatch that rebuilds and fills missing data shards
+// alone. Objects that need no row at all are joined by a copy, and a batch of such objects
+// reaches no device. Not in the reference API.
+func (c *Codec) DecodeDataBatch(shards [][][]byte, profile ErasureProfile, sizes []int64) ([][]byte, []error) {
+	return c.decodeBatch(shards, profile, sizes, true)
+}
+
+func (c *Codec) decodeBatch(shards [][][]byte, profile ErasureProfile, sizes []int64, dataOnly bool) ([][]byte, []error) {
 	k, m := profile.DataShards, profile.ParityShards
 	out := make([][]byte, len(shards))
 	errs := make([]error, len(shards))
@@ -554,7 +606,11 @@ func (c *Codec) DecodeBatch(shards [][][]byte, profile ErasureProfile, sizes []i
 	n := k + m
 	if n > 256 || device() == nil {
 		for b := range shards {
-			out[b], errs[b] = c.cpuDecode(shards[b], profile, sizes[b])
+			if dataOnly {
+				out[b], errs[b] = cpuDecodeData(shards[b], profile, sizes[b])
+			} else {
+				out[b], errs[b] = c.cpuDecode(shards[b], profile, sizes[b])
+			}
 		}
 		return out, errs
 	}
@@ -584,7 +640,7 @@ func (c *Codec) DecodeBatch(shards [][][]byte, profile ErasureProfile, sizes []i
 		copy(bufs[b], sh)
 		for i, s := range bufs[b] {
 			lens[b*n+i] = C.size_t(len(s))
-			if len(s) == 0 && S > 0 {
+			if len(s) == 0 && S > 0 && (i < k || !dataOnly) {
 				if cap(s) >= S {
 					s = s[:S]
 				} else {
@@ -604,8 +660,14 @@ func (c *Codec) DecodeBatch(shards [][][]byte, profile ErasureProfile, sizes []i
 			outs.set(b, unsafe.Pointer(&out[b][0]))
 		}
 	}
-	rc := C.rs_codec_decode_batch(gpuCtx, C.int(k), C.int(m), C.int(B), ptrs.at(0), &lens[0],
-		outs.at(0), &osz[0], &status[0])
+	var rc C.int
+	if dataOnly {
+		rc = C.rs_codec_decode_data_batch(gpuCtx, C.int(k), C.int(m), C.int(B), ptrs.at(0), &lens[0],
+			outs.at(0), &osz[0], &status[0])
+	} else {
+		rc = C.rs_codec_decode_batch(gpuCtx, C.int(k), C.int(m), C.int(B), ptrs.at(0), &lens[0],
+			outs.at(0), &osz[0], &status[0])
+	}
 	callLevel := rc != C.RS_OK && !hasStatus(status, rc) // no status was written
 	for b, sh := range shards {
 		if errs[b] != nil {
@@ -620,7 +682,7 @@ func (c *Codec) DecodeBatch(shards [][][]byte, profile ErasureProfile, sizes []i
 		case C.RS_OK, C.RS_E_CORRUPT, C.RS_E_INSUFFICIENT:
 			// Reconstruct ran: upstream has filled the nil entries by now (codec.go:55)
 			for i := range sh {
-				if len(sh[i]) == 0 {
+				if len(sh[i]) == 0 && lens[b*n+i] != 0 {
 					sh[i] = bufs[b][i]
 				}
 			}

@@ -192,6 +192,35 @@ int rs_codec_decode_batch(rs_ctx* ctx, int k, int m, int batch,
                           uint8_t* const* shards, size_t* lens,
                           uint8_t* const* out, const int64_t* original_sizes, int* status);
 
+/* ---- Only the shards a caller asks for --------------------------
+ * Upstream ReconstructSome(shards, required) and ReconstructData for host memory. A download
+ * keeps the joined data alone and a repair wants the one shard its node lost: these calls
+ * rebuild nothing else. required holds k+m flags per stripe (batch*(k+m) for the batch call;
+ * nonzero = wanted), or NULL: every missing shard is wanted, and the call is then exactly
+ * rs_reconstruct / rs_reconstruct_batch (same work, same rs_host_counters).
+ *   - A missing shard whose flag is set is rebuilt, bit-exact with rs_reconstruct, and its
+ *     lens entry becomes S.
+ *   - A missing shard whose flag is clear is neither written nor read: its pointer may be
+ *     NULL and its lens entry stays 0.
+ *   - Flags on present shards are ignored. With verify != 0 the present shards beyond the
+ *     first k are compared as in rs_reconstruct_batch (RS_E_CORRUPT per stripe).
+ * Contract and status values are rs_reconstruct's / rs_reconstruct_batch's. A stripe that
+ * wants nothing (and, with verify, has nothing to compare) is RS_OK without device work; a
+ * call of such stripes alone reaches no device and moves no counter.
+ * rs_codec_decode_data / rs_codec_decode_data_batch are rs_codec_decode / _batch with the
+ * data shards wanted (ReconstructData in Reconstruct's place): `out`, the joins, trims,
+ * error precedence and RS_E_CORRUPT from the compared shards are the same, missing parity
+ * shards stay missing (lens 0) and their buffers may be NULL. */
+int rs_reconstruct_some(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                        const uint8_t* required);
+int rs_reconstruct_some_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
+                              size_t* lens, const uint8_t* required, int verify, int* status);
+int rs_codec_decode_data(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                         uint8_t* out, int64_t original_size);
+int rs_codec_decode_data_batch(rs_ctx* ctx, int k, int m, int batch,
+                               uint8_t* const* shards, size_t* lens,
+                               uint8_t* const* out, const int64_t* original_sizes, int* status);
+
 /* ---- counters of the host-memory path -----------------------------------------------
  * Monotonic per-context counts (relaxed atomics; what an operator graphs, and what shows
  * that a batch cost one round trip):
@@ -375,6 +404,44 @@ int rs_plan_create_ragged(rs_ctx* ctx, int device, int k, int m, int batch, cons
                           const uint8_t* present, uint8_t* const* shards, rs_plan** out);
 int rs_decode_dev_ragged(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
                          const uint8_t* present, uint8_t* const* shards, void* stream);
+
+/* ---- required plans: only the missing shards a caller wants ------
+ * Upstream ReconstructSome(shards, required) / ReconstructData for device-resident batches:
+ * a download needs its data shards alone, a repair the one shard its node lost. sizes,
+ * present and shards as for rs_plan_create_ragged; required holds batch*(k+m) flags beside
+ * present's (nonzero = wanted), or NULL: every missing shard is wanted.
+ *   - A missing shard whose flag is set is rebuilt, bit-exact with rs_plan_create_ragged.
+ *   - A missing shard whose flag is clear is neither written nor read: its pointer is never
+ *     passed to a kernel and may be NULL.
+ *   - Flags on present shards are ignored; present shards beyond the first k are compared
+ *     as in every plan, and the corruption flags are per stripe.
+ * Errors are those of rs_plan_create_ragged. Routing, in this order:
+ *   1. required == NULL, present == NULL or every missing shard wanted: exactly what
+ *      rs_plan_create_ragged returns.
+ *   2. all sizes equal and every stripe the same mask and wanted set: the uniform plan of
+ *      rs_plan_create over the wanted rows alone (every kernel form, tile orders, tuning and
+ *      ceilings as for any uniform plan). When no row is left (exactly k shards present,
+ *      nothing wanted) the plan has 0 launch groups, its launch enqueues nothing and
+ *      rs_plan_bytes is 0.
+ *   3. otherwise a required plan: a ragged plan whose stripes have their own row counts,
+ *      each launch group over a tile map of the stripes that have a row in it. Stripe b
+ *      with w_b wanted missing shards and c_b compared ones costs r_b = w_b + c_b rows; a
+ *      stripe with r_b = 0 is in no launch. It works with rs_plan_launch, _launch_timed
+ *      (which only enqueue: no allocation, no sync; graph-capturable), _status,
+ *      _stripe_status, _groups and _destroy as any plan does, and
+ *        rs_plan_bytes   returns the sum over the stripes with r_b > 0 of
+ *                        sizes[b] * (k + w_b + c_b);
+ *        rs_plan_forms   reports RS_ORDER_REQUIRED + RS_ORDER_CONSECUTIVE;
+ *        rs_plan_tune, rs_plan_set_orders and rs_plan_launch_ceiling behave as for a
+ *        ragged plan; no bit-sliced kernel, no hiprtc compile, no tune-table entry.
+ * rs_decode_dev_required is the one-shot form, as rs_decode_dev_ragged. */
+#define RS_ORDER_REQUIRED 2048
+int rs_plan_create_required(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                            const uint8_t* present, const uint8_t* required,
+                            uint8_t* const* shards, rs_plan** out);
+int rs_decode_dev_required(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                           const uint8_t* present, const uint8_t* required,
+                           uint8_t* const* shards, void* stream);
 
 /* ---- ShardChecksum on device-resident shards (codec.go:81-84; §8(f) of SURVEY.md) ----
  * SHA-256 of `count` messages already in HBM, one digest per message written to

@@ -30,6 +30,8 @@ rs_codec_encode_batch / rs_codec_decode_batch is timed through them (route "batc
 does not -- the parent commit's -- does the same job the two ways it can: route "a", a loop of
 rs_codec_encode / rs_codec_decode per object, and route "b", CPU Split + rs_encode_batch and
 rs_reconstruct_batch + CPU join (one copy per object each way, the cheapest a caller can do).
+A library that has rs_codec_decode_data_batch is also timed through it on the
+decode leg (route "data": only the lost data shards are rebuilt).
 
 `--crossover` instead times W3-like batches scaled from 64 KiB to 8 MiB of staging on one
 library; run it once with CALLFS_RS_SMALL_MAX_BYTES=0 (staged) and once with a large value (in
@@ -78,6 +80,9 @@ class Lib:
             self.so.rs_codec_decode_batch.argtypes = [
                 _vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp),
                 ctypes.POINTER(_i64), ctypes.POINTER(_int)]
+        self.has_decode_data = hasattr(self.so, "rs_codec_decode_data_batch")
+        if self.has_decode_data:
+            self.so.rs_codec_decode_data_batch.argtypes = self.so.rs_codec_decode_batch.argtypes
         self.ctx = _vp()
         rc = self.so.rs_init(ctypes.byref(self.ctx), 1)  # one device
         if rc:
@@ -288,7 +293,10 @@ class CodecBatch:
 
     def run(self, lib, route, leg):
         so, ctx, k, m, B, a = lib.so, lib.ctx, self.k, self.m, self.B, self.arr
-        if route == "batch":
+        if route == "data" and leg == "dec":
+            return so.rs_codec_decode_data_batch(ctx, k, m, B, self.shards, self.lens, self.out, self.orig,
+                                                 self.status)
+        if route in ("batch", "data"):
             if leg == "enc":
                 return so.rs_codec_encode_batch(ctx, k, m, B, self.data, self.clens, self.dst, self.caps, self.ss,
                                                 self.status)
@@ -336,7 +344,9 @@ def run_codec_workload(name, libs, rounds, out, seed):
     k, m, sizes = workload(name, rng)
     total = CodecBatch.nbytes(k, m, sizes)
     reps = 200 if total < (16 << 20) else 2
-    runs = [(lib, r) for lib in libs for r in (("batch",) if lib.has_codec_batch else ("a", "b"))]
+    all_runs = [(lib, r) for lib in libs
+                for r in ((("batch", "data") if lib.has_decode_data else ("batch",))
+                          if lib.has_codec_batch else ("a", "b"))]
     for mem in ("pageable", "pinned"):
         batches, frees = {}, []
         for lib in libs:
@@ -361,6 +371,7 @@ def run_codec_workload(name, libs, rounds, out, seed):
             fill_random(arr[:b.s_off[0]], np.random.default_rng(seed + 1))
             batches[lib.name] = b
         for leg in ("enc", "dec"):
+            runs = [(lib, r) for lib, r in all_runs if r != "data" or leg == "dec"]
             times = {(lib.name, r): [] for lib, r in runs}
             counters = {}
             for lib, r in runs:  # warm-up: allocations, tables; the encode also makes the shards valid

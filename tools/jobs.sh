@@ -451,6 +451,33 @@ rm -f $O/libcallfs_rs_copy.so
 tail -40 $O/codec_batch.log; exit $rc
 }
 
+# Only the shards a caller asks for, against the parent commit's build.
+# Device plans: a data-only required plan on the download shape of W1 (one lost data shard per
+# stripe, exactly k present) against the parent's full ragged plan (tools/required_plan_bench.py).
+# Host batches: rs_codec_decode_data_batch (route "data") beside rs_codec_decode_batch, the
+# parent's included (tools/host_batch_bench.py --codec), on W1 and W2. The current build is
+# loaded twice, the second time from a copy, for the spread. Output: <out dir>/required_plan.jsonl
+# and <out dir>/decode_data.jsonl (the lines kept in profiles/r14/required/).
+# Usage: PARENT_LIB=<path> bash tools/jobs.sh required_bench <out dir>
+job_required_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+O=${1:-required_out}; mkdir -p "$O" || exit $?
+[ -f "$PARENT_LIB" ] || { echo "PARENT_LIB must name the parent commit's libcallfs_rs.so" >&2; exit 2; }
+cp callfs_amd/libcallfs_rs.so $O/libcallfs_rs_copy.so || exit $?
+timeout -k 10 300 python3 -u tools/required_plan_bench.py --rounds 5 --full new \
+  --lib parent="$PARENT_LIB" --lib new=callfs_amd/libcallfs_rs.so --lib new2=$O/libcallfs_rs_copy.so \
+  --out $O/required_plan.jsonl > $O/required_plan.log 2>&1; rc=$?
+tail -8 $O/required_plan.log
+if [ $rc -eq 0 ]; then
+  timeout -k 10 700 python3 -u tools/host_batch_bench.py --codec --rounds 5 --workloads "${2:-W1,W2}" \
+    --lib parent="$PARENT_LIB" --lib new=callfs_amd/libcallfs_rs.so --lib new2=$O/libcallfs_rs_copy.so \
+    --out $O/decode_data.jsonl > $O/decode_data.log 2>&1; rc=$?
+  grep codec_dec $O/decode_data.log | tail -40
+fi
+rm -f $O/libcallfs_rs_copy.so
+exit $rc
+}
+
 # configs[1]/[2] shape in the layouts upstream produces: bench.py at S = 6,710,887 with the
 # io.ReadAll Split layout (decode into fresh buffers, as Reconstruct allocates them, and in
 # place) and the planar layout; plus the bench shape. Usage: bash tools/jobs.sh readall_bench <tag>
