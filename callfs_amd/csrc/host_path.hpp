@@ -1,7 +1,8 @@
 // The HIP-free parts of the host-memory path and of the plans' buffer layout: the registry
 // and pool of rs_host_alloc buffers, the chunk geometry of the pipeline, the join / tee
-// targets, the argument checks and the admission of a reconstruct stripe, the stripe grouping
-// and the routing of the batch calls, and the 256-byte packer of device buffers. Plain C++
+// targets, the argument checks and the admission of a reconstruct stripe (with or without a
+// wanted set: one function, one flag encoding per shard), the stripe grouping and the routing
+// of the batch calls, and the 256-byte packer of device buffers. Plain C++
 // with no HIP dependence, so tests/native/host_test.cpp checks it on the CPU under ASan+UBSan
 // and TSan; rs_context.cpp, rs_host.cpp (with its host_*.hpp) and rs_plan.cpp are the product
 // users.
@@ -241,17 +242,36 @@ inline int check_lens(int n, const size_t* lens, bool nilok, size_t* S, int* npr
   return RS_OK;
 }
 
-// Whether one stripe of a reconstruct (n shards, k of them data) is to run. In upstream's
-// order: check_lens' status, RS_E_TOO_FEW_SHARDS below k present shards, nothing to do (run
-// false, status RS_OK) when every shard is present and skip_complete (a reconstruct without
-// verify), RS_E_ARG for a NULL shard. Only a stripe to run has its n flags written to `present`.
+// A stripe's shards as the batch calls group, class and build tables by them: the flags
+// admission writes, and the only encoding of a wanted set (ReconstructSome) on the host path.
+// A plain 0 / 1 presence mask (the encode batches') reads the same: every missing shard wanted.
+constexpr uint8_t kShardWanted = 0;    // missing, to be rebuilt
+constexpr uint8_t kShardPresent = 1;
+constexpr uint8_t kShardUnwanted = 2;  // missing, neither written nor read
+
+// A flag row as the table builders' arguments: present[i] and wanted[i], 0 / 1 each.
+inline void shard_flags_split(const uint8_t* flags, size_t count, uint8_t* present, uint8_t* wanted) {
+  for (size_t i = 0; i < count; ++i) {
+    present[i] = flags[i] == kShardPresent;
+    wanted[i] = flags[i] == kShardWanted;
+  }
+}
+
+// Whether one stripe of a reconstruct (n shards, k of them data) is to run. wanted: n flags
+// (nonzero = wanted; flags on present shards count for nothing), or null: every missing shard.
+// In upstream's order: check_lens' status, RS_E_TOO_FEW_SHARDS below k present shards, nothing
+// to do (run false, status RS_OK) when no missing shard is wanted and nothing is compared
+// (!verify), RS_E_ARG for a NULL shard among those the call touches -- the present ones and the
+// wanted missing ones; an unwanted missing shard may be NULL. With verify, a stripe of exactly k
+// present shards that wants nothing has no row either: run false, status RS_OK, and `flags`
+// and S are still written (decode's join copies its data shards). flags: n of kShard*.
 struct StripeAdmission {
   int status = RS_OK;  // the stripe's own when it does not run
   bool run = false;
   size_t S = 0;
 };
 inline StripeAdmission admit_stripe(int n, int k, const uint8_t* const* shards, const size_t* lens,
-                                    bool skip_complete, uint8_t* present) {
+                                    const uint8_t* wanted, bool verify, uint8_t* flags) {
   StripeAdmission a;
   int np = 0;
   if ((a.status = check_lens(n, lens, true, &a.S, &np))) return a;
@@ -259,55 +279,21 @@ inline StripeAdmission admit_stripe(int n, int k, const uint8_t* const* shards, 
     a.status = RS_E_TOO_FEW_SHARDS;
     return a;
   }
-  if (np == n && skip_complete) return a;
-  for (int i = 0; i < n; ++i)
-    if (!shards[i]) {
-      a.status = RS_E_ARG;
-      return a;
-    }
-  for (int i = 0; i < n; ++i) present[i] = lens[i] != 0;
-  a.run = true;
-  return a;
-}
-
-// A stripe's shards in a call with a wanted set (ReconstructSome): the flags admission writes
-// and the batch calls group, class and build tables by. A call without one writes 0 / 1, which
-// read the same: every missing shard is wanted.
-constexpr uint8_t kShardWanted = 0;    // missing, to be rebuilt
-constexpr uint8_t kShardPresent = 1;
-constexpr uint8_t kShardUnwanted = 2;  // missing, neither written nor read
-
-// admit_stripe with a wanted set. wanted: n flags (nonzero = wanted; flags on present shards
-// count for nothing). In order: check_lens' status, RS_E_TOO_FEW_SHARDS, nothing to do (run
-// false, status RS_OK) when no missing shard is wanted and nothing is compared (!verify),
-// RS_E_ARG for a NULL shard among those the call touches -- the present ones and the wanted
-// missing ones; an unwanted missing shard may be NULL. With verify, a stripe of exactly k
-// present shards that wants nothing has no row either: run false, status RS_OK, and `flags`
-// and S are still written (decode's join copies its data shards). flags: n of kShard*.
-inline StripeAdmission admit_stripe_required(int n, int k, const uint8_t* const* shards,
-                                             const size_t* lens, const uint8_t* wanted, bool verify,
-                                             uint8_t* flags) {
-  StripeAdmission a;
-  int np = 0;
-  if ((a.status = check_lens(n, lens, true, &a.S, &np))) return a;
-  if (np < k) {
-    a.status = RS_E_TOO_FEW_SHARDS;
-    return a;
-  }
+  auto want = [&](int i) { return !wanted || wanted[i]; };
   int w = 0;
-  for (int i = 0; i < n; ++i) w += !lens[i] && wanted[i];
+  for (int i = 0; i < n; ++i) w += !lens[i] && want(i);
   if (w == 0 && !verify) return a;
   for (int i = 0; i < n; ++i)
-    if (!shards[i] && (lens[i] || wanted[i])) {
+    if (!shards[i] && (lens[i] || want(i))) {
       a.status = RS_E_ARG;
       return a;
     }
-  for (int i = 0; i < n; ++i) flags[i] = lens[i] ? kShardPresent : wanted[i] ? kShardWanted : kShardUnwanted;
+  for (int i = 0; i < n; ++i) flags[i] = lens[i] ? kShardPresent : want(i) ? kShardWanted : kShardUnwanted;
   a.run = w + (np - k) > 0;
   return a;
 }
 
-// Stripes grouped by (S, presence): each group shares one table set and one pipeline.
+// Stripes grouped by (S, flag row): each group shares one table set and one pipeline.
 struct BatchGroups {
   std::map<std::string, std::vector<int>> by_key;
   std::vector<int> stripes;  // every stripe added, in the order of the calls

@@ -1,6 +1,8 @@
 // The ragged pipeline of the host-memory path: a batch call whose runnable
 // stripes differ in shard size or erasure pattern runs as one pipeline over items
-// (ragged_chunks.hpp) instead of one uniform pipeline per (S, mask) group. It owns the runs of
+// (ragged_chunks.hpp) instead of one uniform pipeline per (S, flag row) group. A stripe's flag
+// row (host_path.hpp kShard*) says which shards are present, wanted or left alone; a call
+// without a wanted set is the all-wanted case of the same code. It owns the runs of
 // a call (RaggedRun), their pattern tables on a lane, the staged, in-place and direct
 // transports, the chunk loop over a lane's slots (run_ragged_chunks) and run_ragged, which
 // picks the device and the lane. Included by rs_host.cpp only.
@@ -22,7 +24,6 @@ struct RaggedRun {
   RaggedShape sh;
   std::vector<int> ids;
   const Join* joins;  // nullable: one per runnable stripe of the call (codec-level batches)
-  bool some = false;  // a call with a wanted set: patterns are (mask, wanted) pairs
   const Join* join_of(int id) const { return joins ? joins + id : nullptr; }
   const MixedPattern& pattern(int s) const { return mt.patterns[mt.pat[static_cast<size_t>(s)]]; }
   void count(size_t chunks, size_t copies) const {
@@ -32,15 +33,15 @@ struct RaggedRun {
   }
 };
 
-// What a lane's table cache is keyed by: the profile, the rows per pattern and the patterns.
+// What a lane's table cache is keyed by: the profile, the rows per pattern and the patterns
+// (one mask has as many patterns as wanted sets: their rows tell them apart).
 std::string ragged_key(const RaggedRun& r) {
   std::string key = std::to_string(r.k) + "," + std::to_string(r.m) + "," + std::to_string(r.mt.rows) + ":";
   for (const MixedPattern& p : r.mt.patterns) key.append(reinterpret_cast<const char*>(p.mask.data()), p.mask.size());
-  if (r.some)  // one mask has as many patterns as wanted sets: their rows tell them apart
-    for (const MixedPattern& p : r.mt.patterns) {
-      key.push_back('|');
-      for (int i : p.rows) key.push_back(static_cast<char>(i));
-    }
+  for (const MixedPattern& p : r.mt.patterns) {
+    key.push_back('|');
+    for (int i : p.rows) key.push_back(static_cast<char>(i));
+  }
   return key;
 }
 
@@ -93,7 +94,7 @@ hipError_t launch_ragged_chunk(const RaggedRun& r, const ChunkLayout& C, uint8_t
     x.tile_stripe = reinterpret_cast<const uint32_t*>(base + C.tile_stripe_off);
     x.tab_stride = static_cast<uint32_t>(g.tab_stride);
     x.ntiles = C.ntiles;
-    const hipError_t e = launch_ragged(a, x, C.any_tail, s);
+    const hipError_t e = launch_ragged(a, x, nullptr, C.any_tail, s);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -377,15 +378,13 @@ int run_ragged_direct(const RaggedRun& r, Lane& L, InF& in, OutF& out, int* flag
 }
 
 // A heterogeneous batch call on one device and lane. The call's runnable stripes are listed
-// by S[j] and present[j * n ..]; in(j, i) / out(j, i) give runnable stripe j's shard i.
-// by_missing: a reconstruct without verification, whose stripes run in classes by missing
-// count (a pattern's rows are its missing shards alone). flags[j] = 1 where stripe j's
-// compared rows mismatched.
-// some: a call with a wanted set. `present` then holds kShard* flags
-// (host_path.hpp), an unwanted missing shard is neither read nor written, and the stripes run
-// in classes by row count (ragged_classes_required), compared rows dropped when by_missing.
+// by S[j] and the kShard* flags (host_path.hpp) present[j * n ..]; in(j, i) / out(j, i) give
+// runnable stripe j's shard i. An unwanted missing shard is neither read nor
+// written. The stripes run in classes by row count (ragged_classes). by_missing: a reconstruct
+// without verification, whose patterns' rows are their wanted missing shards alone (the
+// compared rows are dropped). flags[j] = 1 where stripe j's compared rows mismatched.
 template <class InF, class OutF>
-int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_missing, bool some,
+int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_missing,
                        const std::vector<size_t>& S, const std::vector<uint8_t>& present, InF& in,
                        OutF& out, int* flags, const Join* joins) {
   HIPCHK(hipSetDevice(device));
@@ -397,8 +396,8 @@ int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_m
   bool direct = !ctx->pinned.empty() && total >= zero_copy_min(nn);
   for (int j = 0; direct && j < stripes; ++j)
     for (int i = 0; direct && i < n; ++i) {
-      const bool written = !present[static_cast<size_t>(j) * nn + i];
-      if (some && present[static_cast<size_t>(j) * nn + i] == kShardUnwanted) continue;
+      const bool written = present[static_cast<size_t>(j) * nn + i] == kShardWanted;
+      if (present[static_cast<size_t>(j) * nn + i] == kShardUnwanted) continue;
       if (by_missing && !written) {
         // only the first k present shards are read
         int before = 0;
@@ -409,40 +408,19 @@ int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_m
     }
   for (int j = 0; direct && joins && j < stripes; ++j)
     direct = joins[j].len == 0 || ctx->pinned.contains(joins[j].out, joins[j].len);
-  const std::vector<RaggedClass> classes =
-      some ? ragged_classes_required(n, k, stripes, present.data(), !by_missing)
-           : ragged_classes(n, stripes, present.data(), by_missing);
-  for (const RaggedClass& cls : classes) {
-    const int rows = by_missing || some ? cls.e : m;
-    const auto segments =
-        some ? ragged_segments_required(k, n, rows, cls.stripes, present.data(), kRaggedArenaBudget)
-             : ragged_segments(k, n, rows, cls.stripes, present.data(), kRaggedArenaBudget);
-    for (const auto& seg : segments) {
+  for (const RaggedClass& cls : ragged_classes(n, k, stripes, present.data(), !by_missing)) {
+    for (const auto& seg : ragged_segments(k, n, cls.rows, cls.stripes, present.data(), kRaggedArenaBudget)) {
       RaggedRun r{ctx, k, m, {}, {}, {}, joins};
-      r.some = some;
       r.ids.assign(cls.stripes.begin() + static_cast<ptrdiff_t>(seg.first),
                    cls.stripes.begin() + static_cast<ptrdiff_t>(seg.second));
-      std::vector<uint8_t> pres(r.ids.size() * nn);
+      std::vector<uint8_t> pres(r.ids.size() * nn), want(pres.size());
       for (size_t s = 0; s < r.ids.size(); ++s)
-        std::memcpy(&pres[s * nn], &present[static_cast<size_t>(r.ids[s]) * nn], nn);
+        shard_flags_split(&present[static_cast<size_t>(r.ids[s]) * nn], nn, &pres[s * nn], &want[s * nn]);
       const int count = static_cast<int>(r.ids.size());
-      MixedError me;
-      if (some) {
-        // every pattern of the class has `rows` rows: the tables are what the kernels expect
-        std::vector<uint8_t> want(pres.size());
-        for (size_t q = 0; q < pres.size(); ++q) {
-          want[q] = pres[q] == kShardWanted;
-          pres[q] = pres[q] == kShardPresent;
-        }
-        me = build_mixed_tables_required(k, m, count, pres.data(), want.data(), r.mt, !by_missing);
-        for (const MixedPattern& pt : r.mt.patterns)
-          if (me == MixedError::kOk && static_cast<int>(pt.rows.size()) != rows) me = MixedError::kRowCount;
-      } else {
-        me = by_missing ? build_mixed_tables_missing(k, m, rows, count, pres.data(), r.mt)
-                        : build_mixed_tables(k, m, count, pres.data(), r.mt);
-      }
-      if (me == MixedError::kSingular) return RS_E_SINGULAR;
-      if (me != MixedError::kOk) return RS_E_ARG;
+      const TableError me = build_mixed_tables(k, m, count, pres.data(), want.data(), r.mt, !by_missing);
+      if (me == TableError::kSingular) return RS_E_SINGULAR;
+      // every pattern of the class has its rows: the tables are what the kernels expect
+      if (me != TableError::kOk || !mixed_rows_are(r.mt, cls.rows)) return RS_E_ARG;
       r.sh.k = k;
       for (const MixedGroup& g : r.mt.groups) r.sh.group_rows.push_back(g.R);
       for (int s = 0; s < count; ++s) {
@@ -487,14 +465,14 @@ int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_m
 template <class InF, class OutF>
 int run_ragged(rs_ctx* ctx, int k, int m, bool by_missing, const std::vector<size_t>& S,
                const std::vector<uint8_t>& present, InF in, OutF out, int* flags,
-               const Join* joins = nullptr, bool some = false) {
+               const Join* joins = nullptr) {
   if (ctx->devs.empty()) return RS_E_HIP;
   ctx->n_calls.fetch_add(1, std::memory_order_relaxed);
   ctx->n_ragged_calls.fetch_add(1, std::memory_order_relaxed);
   // one device and lane, chosen round-robin like any call (split_ways does not apply)
   Device* dev = ctx->devs[device_slot(ctx->rr.fetch_add(1), 0, ctx->devs.size())].get();
   return with_lane(ctx, dev, [&](Lane& L) {
-    return run_ragged_on_lane(ctx, L, dev->id, k, m, by_missing, some, S, present, in, out, flags, joins);
+    return run_ragged_on_lane(ctx, L, dev->id, k, m, by_missing, S, present, in, out, flags, joins);
   });
 }
 

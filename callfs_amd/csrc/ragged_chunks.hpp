@@ -4,8 +4,9 @@
 // for a chunk), consecutive items are packed into chunks of at most the chunk budget, and a
 // chunk's staging is laid out so that it moves with one H2D and one D2H and runs as one
 // ragged launch per launch group (ragged_tables.hpp, "stripe" meaning item). Also the split of
-// a reconstruct without verification into classes by missing count, and of a call into
-// segments whose pattern tables stay within kRaggedArenaBudget. Plain C++ with no HIP
+// a call into classes by row count (a reconstruct without verification: by missing count), and
+// of a class into segments whose pattern tables stay within kRaggedArenaBudget. Both read the
+// kShard* flag rows that admission writes (host_path.hpp). Plain C++ with no HIP
 // dependence: tests/native/ragged_chunks_test.cpp builds it with g++ on the CPU.
 #pragma once
 
@@ -208,9 +209,10 @@ void fill_chunk_meta(const ChunkLayout& L, const RaggedShape& sh, const std::vec
     for (size_t j = 0; j < L.count; ++j)
       for (int r = 0; r < g.R; ++r) out[j * g.R + r] = row_ptr(j, g.row0 + r);
   }
-  RaggedTables tm;
-  (void)build_tile_map(static_cast<int>(L.count), widths.data(), tm);
-  std::memcpy(h + L.size_off, tm.size.data(), sizeof(uint64_t) * tm.size.size());
+  TileMap tm;
+  (void)build_tile_map(static_cast<int>(L.count), widths.data(), nullptr, tm);
+  auto* size = reinterpret_cast<uint64_t*>(h + L.size_off);
+  for (size_t j = 0; j < L.count; ++j) size[j] = widths[j];
   std::memcpy(h + L.tile0_off, tm.tile0.data(), sizeof(uint32_t) * tm.tile0.size());
   std::memcpy(h + L.tile_stripe_off, tm.tile_stripe.data(), sizeof(uint32_t) * tm.tile_stripe.size());
   auto* tab = reinterpret_cast<uint32_t*>(h + L.item_tab_off);
@@ -235,38 +237,17 @@ inline bool fold_item_status(const ChunkLayout& L, const std::vector<RaggedItem>
   return any;
 }
 
-// The stripes of a call by class. by_missing = false (encodes, verify != 0): one class of
-// every stripe. by_missing = true (reconstruct, verify == 0): one class per missing count e,
-// in ascending e; stripes with nothing missing are in no class. present: stripes * n flags.
+// The stripes of a call by class: one class per row count r = wanted missing shards + (verify:
+// present shards beyond the first k), in ascending r, so that every pattern of a class has
+// exactly r rows, which is what the ragged kernels rest on; `rows` holds r. Stripes with r = 0
+// are in no class. flags: stripes * n of kShard* (host_path.hpp). Where every missing shard is
+// wanted, verify gives r = m for every stripe (one class: encodes, verify != 0) and !verify
+// gives r = the missing count (a reconstruct with verify == 0).
 struct RaggedClass {
-  int e = 0;  // missing count (by_missing only)
+  int rows = 0;
   std::vector<int> stripes;
 };
-inline std::vector<RaggedClass> ragged_classes(int n, int stripes, const uint8_t* present, bool by_missing) {
-  std::vector<RaggedClass> out;
-  if (!by_missing) {
-    RaggedClass c;
-    for (int b = 0; b < stripes; ++b) c.stripes.push_back(b);
-    if (stripes) out.push_back(std::move(c));
-    return out;
-  }
-  std::vector<std::vector<int>> by(static_cast<size_t>(n) + 1);
-  for (int b = 0; b < stripes; ++b) {
-    int e = 0;
-    for (int i = 0; i < n; ++i) e += present[static_cast<size_t>(b) * n + i] == 0;
-    by[e].push_back(b);
-  }
-  for (int e = 1; e <= n; ++e)
-    if (!by[e].empty()) out.push_back({e, std::move(by[e])});
-  return out;
-}
-
-// The sibling for calls with a wanted set (flags: stripes * n of kShard*, host_path.hpp): one
-// class per row count r = wanted missing shards + (verify: present shards beyond the first k),
-// in ascending r, so that every pattern of a class has exactly r rows, which is what the
-// ragged kernels rest on; `e` holds r. Stripes with r = 0 are in no class.
-inline std::vector<RaggedClass> ragged_classes_required(int n, int k, int stripes, const uint8_t* flags,
-                                                        bool verify) {
+inline std::vector<RaggedClass> ragged_classes(int n, int k, int stripes, const uint8_t* flags, bool verify) {
   std::vector<std::vector<int>> by(static_cast<size_t>(n) + 1);
   for (int b = 0; b < stripes; ++b) {
     int w = 0, np = 0;
@@ -291,35 +272,11 @@ inline size_t pattern_arena_bytes(int k, int rows) {
 }
 
 // Cuts a class's stripe list into segments [begin, end) of consecutive entries whose distinct
-// patterns' tables stay within `budget` (one pattern always fits).
+// patterns' tables stay within `budget` (one pattern always fits). A pattern is a stripe's whole
+// row of kShard* flags: the mask and the wanted missing shards.
 inline std::vector<std::pair<size_t, size_t>> ragged_segments(int k, int n, int rows,
                                                               const std::vector<int>& stripes,
-                                                              const uint8_t* present, size_t budget) {
-  const size_t per = pattern_arena_bytes(k, rows);
-  const size_t max_patterns = std::max<size_t>(1, budget / std::max<size_t>(per, 1));
-  std::vector<std::pair<size_t, size_t>> segs;
-  std::set<std::string> seen;
-  size_t begin = 0;
-  for (size_t j = 0; j < stripes.size(); ++j) {
-    std::string key(static_cast<size_t>(n), '0');
-    for (int i = 0; i < n; ++i)
-      if (present[static_cast<size_t>(stripes[j]) * n + i]) key[static_cast<size_t>(i)] = '1';
-    if (!seen.count(key) && seen.size() == max_patterns) {
-      segs.push_back({begin, j});
-      begin = j;
-      seen.clear();
-    }
-    seen.insert(std::move(key));
-  }
-  if (begin < stripes.size()) segs.push_back({begin, stripes.size()});
-  return segs;
-}
-
-// ragged_segments for calls with a wanted set: a pattern is a stripe's whole row of kShard*
-// flags (the mask and the wanted missing shards).
-inline std::vector<std::pair<size_t, size_t>> ragged_segments_required(int k, int n, int rows,
-                                                                       const std::vector<int>& stripes,
-                                                                       const uint8_t* flags, size_t budget) {
+                                                              const uint8_t* flags, size_t budget) {
   const size_t per = pattern_arena_bytes(k, rows);
   const size_t max_patterns = std::max<size_t>(1, budget / std::max<size_t>(per, 1));
   std::vector<std::pair<size_t, size_t>> segs;

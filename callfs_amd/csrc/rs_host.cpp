@@ -6,7 +6,9 @@
 // reedsolomon methods it calls (Split/Encode at :31/:36, Reconstruct at :55, Verify at
 // :59). Stripes of one table set and shard size go through host_uniform.hpp, a batch of mixed
 // sizes or erasures through host_ragged.hpp; what a call admits, how a batch is routed and
-// Split's shape are the HIP-free host_path.hpp and codec_batch.hpp.
+// Split's shape are the HIP-free host_path.hpp and codec_batch.hpp. Every reconstruct, with a
+// wanted set (ReconstructSome / ReconstructData) or without, is admitted into the same kShard*
+// flag rows and takes the same path from there.
 #include "codec_batch.hpp"
 #include "host_ragged.hpp"
 #include "host_uniform.hpp"
@@ -30,15 +32,11 @@ std::shared_ptr<const Tables> encode_tables(rs_ctx* ctx, int k, int m) {
 int reconstruct_host(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
                      bool verify, uint8_t* out = nullptr, size_t original_size = 0,
                      bool* joined = nullptr, const uint8_t* wanted = nullptr) {
-  uint8_t present[256], want[256];
-  const StripeAdmission a = wanted ? admit_stripe_required(k + m, k, shards, lens, wanted, verify, present)
-                                   : admit_stripe(k + m, k, shards, lens, !verify, present);
+  uint8_t flags[256], present[256], want[256];
+  const StripeAdmission a = admit_stripe(k + m, k, shards, lens, wanted, verify, flags);
   if (!a.run) return a.status;
-  for (int i = 0; wanted && i < k + m; ++i) {
-    want[i] = present[i] != kShardUnwanted;
-    present[i] = present[i] == kShardPresent;
-  }
-  auto t = ctx->cache.get(k, m, present, verify, wanted ? want : nullptr);
+  shard_flags_split(flags, static_cast<size_t>(k + m), present, want);
+  auto t = ctx->cache.get(k, m, present, verify, want);
   if (!t) return RS_E_SINGULAR;
   if (t->groups.empty()) return RS_OK;
   const Join join = decode_join(k, a.S, out, original_size);
@@ -58,19 +56,17 @@ int first_error(const int* status, int batch) {
 }
 
 // A batch call's tables: whether they compare the present shards beyond the first k, and
-// whether a ragged run classes its stripes by missing count (a reconstruct without verify).
+// whether a ragged run drops the compared rows (a reconstruct without verify).
 struct BatchMode {
   bool verify;
   bool by_missing;
-  // a call with a wanted set: `present` holds kShard* flags (host_path.hpp), the group key is
-  // the (mask, wanted) pair and a ragged run classes its stripes by row count
-  bool some = false;
 };
 
 // The runnable stripes of a batch call (`groups`) on the route batch_route (host_path.hpp)
-// chooses: one ragged pipeline, or one uniform pipeline per (S, mask) group. S, present (n
-// flags each), joins (nullable) and flags are indexed by the call's stripes; in(b, i) /
-// out(b, i) give stripe b's shard i. flags[b] = 1 where stripe b's compared rows mismatched.
+// chooses: one ragged pipeline, or one uniform pipeline per (S, flag row) group. S, present (n
+// kShard* flags each, host_path.hpp), joins (nullable) and flags are indexed by the call's
+// stripes; in(b, i) / out(b, i) give stripe b's shard i. flags[b] = 1 where stripe b's compared
+// rows mismatched.
 // One call is counted: by run_ragged, or with the first group that runs (tables without
 // launch groups run nothing). Returns RS_OK or the error that ended the call.
 template <class InF, class OutF>
@@ -94,20 +90,15 @@ int run_batch(rs_ctx* ctx, int k, int m, BatchMode mode, const BatchGroups& grou
     const int rc = run_ragged(ctx, k, m, mode.by_missing, Sj, pres,
                               [&](int j, int i) { return in(ids[j], i); },
                               [&](int j, int i) { return out(ids[j], i); }, fj.data(),
-                              joins ? jj.data() : nullptr, mode.some);
+                              joins ? jj.data() : nullptr);
     for (size_t j = 0; j < ids.size(); ++j) flags[ids[j]] = fj[j];
     return rc;
   }
   bool first = true;
   for (const auto* kv : route.groups) {
     const std::vector<int>& ids = kv->second;
-    // the group's flags: 0 / 1 read as a mask whose missing shards are all wanted
-    const uint8_t* key = BatchGroups::present(kv->first);
     uint8_t pres[256], want[256];
-    for (size_t i = 0; i < n; ++i) {
-      pres[i] = mode.some ? key[i] == kShardPresent : key[i] != 0;
-      want[i] = !mode.some || key[i] != kShardUnwanted;
-    }
+    shard_flags_split(BatchGroups::present(kv->first), n, pres, want);
     auto t = ctx->cache.get(k, m, pres, mode.verify, want);
     if (!t) return RS_E_SINGULAR;
     if (t->groups.empty()) continue;
@@ -136,7 +127,6 @@ int reconstruct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const*
                            const int64_t* original_sizes, int* status,
                            const uint8_t* required = nullptr, bool data_only = false) {
   const size_t n = static_cast<size_t>(k + m), B = static_cast<size_t>(batch);
-  const bool some = required || data_only;
   std::vector<uint8_t> present(B * n, 0);
   std::vector<size_t> S(B, 0);  // nonzero for the stripes that run
   std::vector<Join> joins(out ? B : 0, Join{nullptr, 0, 0, k});
@@ -146,12 +136,11 @@ int reconstruct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const*
   BatchGroups groups;
   for (size_t b = 0; b < B; ++b) {
     const StripeAdmission a =
-        some ? admit_stripe_required(k + m, k, shards + b * n, lens + b * n,
-                                     data_only ? data_flags.data() : required + b * n, verify,
-                                     &present[b * n])
-             : admit_stripe(k + m, k, shards + b * n, lens + b * n, !verify, &present[b * n]);
+        admit_stripe(k + m, k, shards + b * n, lens + b * n,
+                     data_only ? data_flags.data() : required ? required + b * n : nullptr, verify,
+                     &present[b * n]);
     status[b] = a.status;
-    if (!a.run && some && out && a.status == RS_OK) {
+    if (!a.run && out && a.status == RS_OK) {
       // admitted, nothing to compute: every data shard is present (data_only)
       if (original_sizes[b] < 0 || (original_sizes[b] != 0 && !out[b])) {
         status[b] = RS_E_ARG;
@@ -181,7 +170,7 @@ int reconstruct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const*
   std::vector<int> flags(B, 0);
   auto shard = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
   if (!copies.empty()) ctx->pool.run(copies);
-  const int rc = run_batch(ctx, k, m, BatchMode{verify, !verify, some}, groups, S.data(),
+  const int rc = run_batch(ctx, k, m, BatchMode{verify, !verify}, groups, S.data(),
                            present.data(), out ? joins.data() : nullptr, shard, shard, flags.data());
   if (rc) return rc;
   for (size_t b = 0; b < B; ++b) {

@@ -242,9 +242,10 @@ constexpr uint32_t kRaggedLaunchTileVecs = 512;
 // each stripe's size % 16 tail inside it when any_tail (a stripe shorter than 16 bytes is one
 // tile that is all tail), unaligned 16-B accesses on misaligned shards. Consecutive tile
 // order, sliced like launch_mixed; never the bit-sliced path, the tune table or a tile-order
-// rule. ev as for launch_apply.
-hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, bool any_tail, hipStream_t stream,
-                         LaunchEvents ev = {});
+// rule. ev as for launch_apply. nrows (nullable): the patterns' row counts of a required launch
+// (RaggedSomeArgs below), which runs the required kernel; x.ntiles == 0 then enqueues nothing.
+hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, const uint32_t* nrows, bool any_tail,
+                         hipStream_t stream, LaunchEvents ev = {});
 
 // ---- required launches (rs_mixed.hip) ----------------------------------
 // A ragged launch group whose patterns have their own row counts (ReconstructSome: a
@@ -259,10 +260,6 @@ struct RaggedSomeArgs {
 
 // (kOrderRequired + the TileOrder it runs in, always consecutive: rs_plan_forms of a required plan)
 constexpr int kOrderRequired = 2048;
-
-// Enqueues the launch group as launch_ragged does; r.ntiles == 0 enqueues nothing.
-hipError_t launch_ragged_some(ApplyArgs a, const RaggedSomeArgs& x, bool any_tail,
-                              hipStream_t stream, LaunchEvents ev = {});
 
 // Tiles per slice of a sliced launch (launch_apply's rule) for `streams` shard streams.
 uint32_t launch_slice_tiles(int streams);

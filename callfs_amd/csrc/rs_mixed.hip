@@ -7,7 +7,8 @@
 // rs_apply.hpp; existing kernel instances are untouched.
 // Ragged launches run the same block body with the stripe, its tile and
 // its shard size read per block from a tile map: one launch group over stripes of
-// different shard sizes.
+// different shard sizes. Required launches (§5.10) are ragged launches that also read each
+// pattern's row count; one host function, launch_ragged, enqueues both.
 #include <algorithm>
 #include <array>
 
@@ -271,9 +272,10 @@ static_assert(kRaggedLaunchTileVecs == kMixedTileVecs, "the tile map counts the 
 // per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one, 2 the required one)
 DeviceOnce g_mixed_wide_lds;
 
-// The vector launch both kinds share: the dynamic-LDS opt-in (`once_key`: 0 the mixed
-// instance, 1 the ragged one), then `grid` tiles in equal consecutive slices, as launch_apply
-// cuts them. A slice boundary may fall inside a stripe (tiles are numbered over the whole grid).
+// The vector launch every kind shares: the dynamic-LDS opt-in (`once_key`: 0 the mixed
+// instance, 1 the ragged one, 2 the required one), then `grid` tiles in equal consecutive
+// slices, as launch_apply cuts them. A slice boundary may fall inside a stripe (tiles are
+// numbered over the whole grid).
 template <class X>
 hipError_t launch_tiles(void (*fn)(ApplyArgs, X), int once_key, uint32_t grid, ApplyArgs& a,
                         const X& x, hipStream_t stream, const LaunchEvents& ev) {
@@ -316,32 +318,22 @@ hipError_t launch_mixed(ApplyArgs a, const MixedArgs& x, hipStream_t stream, Lau
                       stream, ev);
 }
 
-hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, bool any_tail, hipStream_t stream,
-                         LaunchEvents ev) {
+hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, const uint32_t* nrows, bool any_tail,
+                         hipStream_t stream, LaunchEvents ev) {
   if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
-      !x.pat || !x.vmask || !x.size || !x.tile0 || !x.tile_stripe || !a.in_tab || !a.out_tab ||
-      !a.status || x.ntiles < static_cast<uint32_t>(a.batch) || x.ntiles > 0x7fffffffu)
+      !x.pat || !x.vmask || !x.size || !x.tile0 || !a.in_tab || !a.out_tab || !a.status ||
+      x.ntiles > 0x7fffffffu || (x.ntiles && !x.tile_stripe) ||
+      (!nrows && x.ntiles < static_cast<uint32_t>(a.batch)))  // without row counts every stripe has a tile
     return hipErrorInvalidValue;
+  if (x.ntiles == 0) return hipSuccess;  // no stripe has a row in this launch group
   a.t_base = 0;
   a.S = a.nvec = 0;  // per stripe, read by the kernel
   // the S % 16 tails: wave 0 of each stripe's first tile (rs_apply.hpp tail_lane); stripes
   // with no tail leave lds_tail at once
   a.tail_in_vec = any_tail ? 1u : 0u;
-  return launch_tiles(kRagged[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 1, x.ntiles, a, x, stream, ev);
-}
-
-hipError_t launch_ragged_some(ApplyArgs a, const RaggedSomeArgs& x, bool any_tail,
-                              hipStream_t stream, LaunchEvents ev) {
-  const RaggedArgs& r = x.r;
-  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
-      !r.pat || !r.vmask || !r.size || !r.tile0 || !x.nrows || !a.in_tab || !a.out_tab ||
-      !a.status || r.ntiles > 0x7fffffffu || (r.ntiles && !r.tile_stripe))
-    return hipErrorInvalidValue;
-  if (r.ntiles == 0) return hipSuccess;  // no stripe has a row in this launch group
-  a.t_base = 0;
-  a.S = a.nvec = 0;  // per stripe, read by the kernel
-  a.tail_in_vec = any_tail ? 1u : 0u;
-  return launch_tiles(kRaggedSome[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 2, r.ntiles, a, x, stream, ev);
+  const int inst = a.R > 8 ? 2 : a.R > 4 ? 1 : 0;
+  return nrows ? launch_tiles(kRaggedSome[inst], 2, x.ntiles, a, RaggedSomeArgs{x, nrows}, stream, ev)
+               : launch_tiles(kRagged[inst], 1, x.ntiles, a, x, stream, ev);
 }
 
 }  // namespace callfs

@@ -1,8 +1,10 @@
 // Device-resident plans of the C ABI (include/callfs_rs.h): tables uploaded once for
 // repeated, graph-capturable launches over shards in device memory -- uniform plans (one
 // erasure pattern, one shard size: every kernel form and tile order), mixed plans (a
-// pattern per stripe) and ragged plans (a shard size per stripe too,
-// §5.9) and required plans (only the missing shards a caller wants, §5.10) -- the tile-order tuner and the one-shot device calls built on them.
+// pattern per stripe), ragged plans (a shard size per stripe too, §5.9) and
+// required plans (only the missing shards a caller wants, §5.10), which share one layout, one
+// upload and one constructor tail -- the tile-order tuner and the one-shot device calls built
+// on them.
 #include <cstdio>
 
 #include "mixed_tables.hpp"
@@ -14,26 +16,27 @@ using namespace callfs;
 
 static_assert(kRaggedTileVecs == kRaggedLaunchTileVecs, "the tile map counts the kernel's tiles");
 
-// A mixed plan (rs_plan_create_mixed): the pattern tables and where each piece sits in the
-// plan's device buffer.
-// A ragged plan (rs_plan_create_ragged) is a mixed plan with a tile map: `ragged` is set,
-// the plan's S is the largest shard size (never 0) and each stripe's own size sits in the
-// device buffer with tile0 and tile_stripe (ragged_tables.hpp).
-// A required plan (rs_plan_create_required) is a ragged plan whose patterns have their own
-// row counts: `some` is set, every launch group has its own tile map (g_*) and the patterns'
-// row counts inside it (nrows_off).
+// A plan with per-stripe tables (`tables` of rs_plan is null): the pattern tables and where each
+// piece sits in the plan's device buffer. A mixed plan (rs_plan_create_mixed) has one shard size
+// and no tile map. A ragged plan (rs_plan_create_ragged) adds the stripes' sizes and one tile map
+// (ragged_tables.hpp) that every launch group names; the plan's S is the largest shard size
+// (never 0). A required plan (rs_plan_create_required) is a ragged plan whose patterns have their
+// own row counts: every launch group has its own tile map and launches with the patterns' row
+// counts inside it.
+enum class PlanKind { kMixed, kRagged, kRequired };
+
 struct MixedPlan {
   MixedTables t;
-  size_t in_off = 0, pat_off = 0;
-  std::vector<size_t> out_off, vmask_off, arena_off;  // per launch group
-  bool ragged = false;
-  bool any_tail = false;  // some stripe's size is no multiple of 16
-  uint32_t ntiles = 0;
-  size_t size_off = 0, tile0_off = 0, tile_stripe_off = 0;
-  bool some = false;
-  std::vector<size_t> nrows_off, g_tile0_off, g_tile_stripe_off;  // per launch group
-  std::vector<uint32_t> g_ntiles;
-  std::vector<uint8_t> g_any_tail;
+  PlanKind kind = PlanKind::kMixed;
+  size_t in_off = 0, pat_off = 0, size_off = 0;
+  struct Group {
+    size_t out_off, vmask_off, arena_off, nrows_off;
+    // the tile map the group launches with (none for a mixed plan)
+    size_t tile0_off = 0, tile_stripe_off = 0;
+    uint32_t ntiles = 0;
+    bool any_tail = false;  // some stripe of the map has a size that is no multiple of 16
+  };
+  std::vector<Group> groups;  // per launch group of `t`
 };
 
 struct rs_plan {
@@ -74,8 +77,9 @@ size_t plan_groups(const rs_plan& plan) {
   return plan.mixed ? plan.mixed->t.groups.size() : plan.tables->groups.size();
 }
 
-// The arguments of launch group gi. A mixed or ragged plan's per-stripe tables go to *x
-// (the MixedArgs fields, and the tile map of a ragged plan).
+// The arguments of launch group gi. A plan with per-stripe tables gives them as *x (the
+// MixedArgs fields, and the group's tile map unless the plan is a mixed one) and, for a required
+// plan, the patterns' row counts as *nrows (null otherwise).
 ApplyArgs plan_group_args(const rs_plan& plan, size_t gi, RaggedArgs* x = nullptr,
                           const uint32_t** nrows = nullptr) {
   auto* d = static_cast<uint8_t*>(plan.dmeta.p);
@@ -83,10 +87,11 @@ ApplyArgs plan_group_args(const rs_plan& plan, size_t gi, RaggedArgs* x = nullpt
     return group_args(*plan.tables, plan.layout, gi, plan.batch, d, plan.S, 1, plan.hint);
   const MixedPlan& mp = *plan.mixed;
   const MixedGroup& g = mp.t.groups[gi];
+  const MixedPlan::Group& at = mp.groups[gi];
   ApplyArgs a{};
   a.in_tab = reinterpret_cast<const uint8_t* const*>(d + mp.in_off);
-  a.out_tab = reinterpret_cast<uint8_t* const*>(d + mp.out_off[gi]);
-  a.ltabs = d + mp.arena_off[gi];
+  a.out_tab = reinterpret_cast<uint8_t* const*>(d + at.out_off);
+  a.ltabs = d + at.arena_off;
   a.S = plan.S;
   a.status = reinterpret_cast<int*>(d + plan.status_off);
   a.status_stride = 1;
@@ -95,21 +100,17 @@ ApplyArgs plan_group_args(const rs_plan& plan, size_t gi, RaggedArgs* x = nullpt
   a.batch = plan.batch;
   if (x) {
     x->pat = reinterpret_cast<const uint32_t*>(d + mp.pat_off);
-    x->vmask = reinterpret_cast<const uint32_t*>(d + mp.vmask_off[gi]);
+    x->vmask = reinterpret_cast<const uint32_t*>(d + at.vmask_off);
     x->tab_stride = static_cast<uint32_t>(g.tab_stride);
-    if (mp.ragged) {
+    if (mp.kind != PlanKind::kMixed) {
       x->size = reinterpret_cast<const uint64_t*>(d + mp.size_off);
-      x->tile0 = reinterpret_cast<const uint32_t*>(d + mp.tile0_off);
-      x->tile_stripe = reinterpret_cast<const uint32_t*>(d + mp.tile_stripe_off);
-      x->ntiles = mp.ntiles;
-    }
-    if (mp.some) {  // the launch group's own tile map
-      x->tile0 = reinterpret_cast<const uint32_t*>(d + mp.g_tile0_off[gi]);
-      x->tile_stripe = reinterpret_cast<const uint32_t*>(d + mp.g_tile_stripe_off[gi]);
-      x->ntiles = mp.g_ntiles[gi];
-      if (nrows) *nrows = reinterpret_cast<const uint32_t*>(d + mp.nrows_off[gi]);
+      x->tile0 = reinterpret_cast<const uint32_t*>(d + at.tile0_off);
+      x->tile_stripe = reinterpret_cast<const uint32_t*>(d + at.tile_stripe_off);
+      x->ntiles = at.ntiles;
     }
   }
+  if (nrows)
+    *nrows = mp.kind == PlanKind::kRequired ? reinterpret_cast<const uint32_t*>(d + at.nrows_off) : nullptr;
   return a;
 }
 
@@ -126,12 +127,9 @@ hipError_t plan_launch(const rs_plan& plan, hipStream_t s, const std::vector<int
     const uint32_t* nrows = nullptr;
     const ApplyArgs a = plan_group_args(plan, gi, &r, &nrows);
     const LaunchEvents g = group_events(ev, gi, ng);
-    const hipError_t e = plan.mixed->some
-                             ? launch_ragged_some(a, RaggedSomeArgs{r, nrows},
-                                                  plan.mixed->g_any_tail[gi] != 0, s, g)
-                         : plan.mixed->ragged
-                             ? launch_ragged(a, r, plan.mixed->any_tail, s, g)
-                             : launch_mixed(a, MixedArgs{r.pat, r.vmask, r.tab_stride}, s, g);
+    const hipError_t e = plan.mixed->kind == PlanKind::kMixed
+                             ? launch_mixed(a, MixedArgs{r.pat, r.vmask, r.tab_stride}, s, g)
+                             : launch_ragged(a, r, nrows, plan.mixed->groups[gi].any_tail, s, g);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -139,7 +137,39 @@ hipError_t plan_launch(const rs_plan& plan, hipStream_t s, const std::vector<int
 
 // ---- plan construction --------------------------------------------------------------------
 
-// The common head of the three constructors' argument checks done, a plan on `device`.
+// The head of every constructor: the profile, then the arguments (`given`: the pointers that
+// constructor requires).
+int check_plan_args(rs_ctx* ctx, int k, int m, int batch, bool given, rs_plan** out) {
+  if (const int rc = check_profile(k, m)) return rc;
+  if (!ctx || !given || !out || batch < 1) return RS_E_ARG;
+  *out = nullptr;
+  return RS_OK;
+}
+
+// What every stripe needs, whichever path the plan takes: a shard size (sizes nullable; upstream
+// Encode: ErrShardNoData), then k present shards (present nullable).
+int check_stripes(int k, int n, int batch, const size_t* sizes, const uint8_t* present) {
+  for (int b = 0; sizes && b < batch; ++b)
+    if (sizes[b] == 0) return RS_E_NO_DATA;
+  for (int b = 0; present && b < batch; ++b) {
+    int np = 0;
+    for (int i = 0; i < n; ++i) np += present[static_cast<size_t>(b) * n + i] != 0;
+    if (np < k) return RS_E_TOO_FEW_SHARDS;
+  }
+  return RS_OK;
+}
+
+int table_status(TableError e) {
+  switch (e) {
+    case TableError::kOk: break;
+    case TableError::kNoData: return RS_E_NO_DATA;
+    case TableError::kTooManyTiles: return RS_E_ARG;  // a grid past 2^31 - 1 tiles
+    case TableError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
+    case TableError::kSingular: return RS_E_SINGULAR;
+  }
+  return RS_OK;
+}
+
 std::unique_ptr<rs_plan> new_plan(int device, size_t S, int batch) {
   auto plan = std::make_unique<rs_plan>();
   plan->device = device;
@@ -148,160 +178,15 @@ std::unique_ptr<rs_plan> new_plan(int device, size_t S, int batch) {
   return plan;
 }
 
-// Lays out and uploads the device buffer of a mixed plan (plan.mixed->t built, plan.device
-// and plan.batch set): the status words, the shard-pointer tables, pat and per launch group
-// the compare masks and the table arena, each piece 256-B aligned. With `rg` (a ragged plan)
-// also the stripes' sizes, tile0 and tile_stripe. With `rq` (a required plan) the sizes and
-// per launch group its tile map and the patterns' row counts; an out_tab slot at or past a
-// stripe's row count holds null, and a shard no row names is in no table.
-int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rg,
-                 const RequiredTables* rq = nullptr) {
-  MixedPlan& mp = *plan.mixed;
-  const int k = mp.t.k, n = mp.t.k + mp.t.m, batch = plan.batch;
-  Packer pk;
-  const size_t P = mp.t.patterns.size();
-  plan.status_off = pk.take(sizeof(int) * static_cast<size_t>(batch));
-  mp.in_off = pk.take(sizeof(void*) * static_cast<size_t>(batch) * k);
-  mp.pat_off = pk.take(sizeof(uint32_t) * static_cast<size_t>(batch));
-  for (const MixedGroup& g : mp.t.groups) {
-    mp.out_off.push_back(pk.take(sizeof(void*) * static_cast<size_t>(batch) * g.R));
-    mp.vmask_off.push_back(pk.take(sizeof(uint32_t) * P));
-    mp.arena_off.push_back(pk.take(g.arena.size()));
-  }
-  if (rg) {
-    mp.size_off = pk.take(sizeof(uint64_t) * rg->size.size());
-    mp.tile0_off = pk.take(sizeof(uint32_t) * rg->tile0.size());
-    mp.tile_stripe_off = pk.take(sizeof(uint32_t) * rg->tile_stripe.size());
-  }
-  if (rq) {
-    mp.size_off = pk.take(sizeof(uint64_t) * rq->size.size());
-    for (size_t gi = 0; gi < mp.t.groups.size(); ++gi) {
-      const GroupTileMap& gm = rq->maps[gi];
-      mp.nrows_off.push_back(pk.take(sizeof(uint32_t) * P));
-      mp.g_tile0_off.push_back(pk.take(sizeof(uint32_t) * gm.tile0.size()));
-      mp.g_tile_stripe_off.push_back(pk.take(sizeof(uint32_t) * std::max<size_t>(1, gm.tile_stripe.size())));
-      mp.g_ntiles.push_back(gm.ntiles);
-      mp.g_any_tail.push_back(gm.any_tail);
-    }
-  }
-  std::vector<uint8_t> h(pk.off, 0);
-  auto shard_ptr = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
-  auto* in = reinterpret_cast<const uint8_t**>(h.data() + mp.in_off);
-  for (int b = 0; b < batch; ++b) {
-    const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
-    for (int i = 0; i < k; ++i) in[static_cast<size_t>(b) * k + i] = shard_ptr(b, pt.valid[i]);
-  }
-  std::memcpy(h.data() + mp.pat_off, mp.t.pat.data(), sizeof(uint32_t) * mp.t.pat.size());
-  for (size_t gi = 0; gi < mp.t.groups.size(); ++gi) {
-    const MixedGroup& g = mp.t.groups[gi];
-    auto* o = reinterpret_cast<uint8_t**>(h.data() + mp.out_off[gi]);
-    for (int b = 0; b < batch; ++b) {
-      const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
-      for (int r = 0; r < g.R; ++r)
-        o[static_cast<size_t>(b) * g.R + r] =
-            static_cast<size_t>(g.row0 + r) < pt.rows.size() ? shard_ptr(b, pt.rows[g.row0 + r]) : nullptr;
-    }
-    std::memcpy(h.data() + mp.vmask_off[gi], g.vmask.data(), sizeof(uint32_t) * P);
-    std::memcpy(h.data() + mp.arena_off[gi], g.arena.data(), g.arena.size());
-  }
-  if (rg) {
-    std::memcpy(h.data() + mp.size_off, rg->size.data(), sizeof(uint64_t) * rg->size.size());
-    std::memcpy(h.data() + mp.tile0_off, rg->tile0.data(), sizeof(uint32_t) * rg->tile0.size());
-    std::memcpy(h.data() + mp.tile_stripe_off, rg->tile_stripe.data(),
-                sizeof(uint32_t) * rg->tile_stripe.size());
-  }
-  if (rq) {
-    std::memcpy(h.data() + mp.size_off, rq->size.data(), sizeof(uint64_t) * rq->size.size());
-    for (size_t gi = 0; gi < mp.t.groups.size(); ++gi) {
-      const GroupTileMap& gm = rq->maps[gi];
-      std::memcpy(h.data() + mp.nrows_off[gi], mp.t.groups[gi].nrows.data(), sizeof(uint32_t) * P);
-      std::memcpy(h.data() + mp.g_tile0_off[gi], gm.tile0.data(), sizeof(uint32_t) * gm.tile0.size());
-      if (!gm.tile_stripe.empty())
-        std::memcpy(h.data() + mp.g_tile_stripe_off[gi], gm.tile_stripe.data(),
-                    sizeof(uint32_t) * gm.tile_stripe.size());
-    }
-  }
-  if (const int rc = upload(plan.dmeta, plan.device, h.data(), h.size())) return rc;
-  // the device copy is all a launch reads: the host arenas can go
-  for (MixedGroup& g : mp.t.groups) std::vector<uint8_t>().swap(g.arena);
-  return RS_OK;
-}
-
-// A timed launch that dispatches no kernel still records both events on the stream, so
-// the caller's elapsed time is this launch's (zero), never a stale earlier interval.
-int record_empty(void* stream, void* start_event, void* stop_event) {
-  const auto s = static_cast<hipStream_t>(stream);
-  if (start_event) HIPCHK(hipEventRecord(static_cast<hipEvent_t>(start_event), s));
-  if (stop_event) HIPCHK(hipEventRecord(static_cast<hipEvent_t>(stop_event), s));
-  return RS_OK;
-}
-
-// ---- the tuner's knobs ----------------------------------------------------------------------
-
-constexpr int kTuneRounds = 3;
-constexpr float kTuneWarmMs = 150.0f;
-constexpr int kTuneWarmBatches = 400;
-// CALLFS_RS_TUNE_BAR=<percent>: how much faster than the rule's order another order must
-// time to replace it (default 1)
-float tune_bar() {
-  static const float v = [] {
-    const char* e = std::getenv("CALLFS_RS_TUNE_BAR");
-    if (e && *e) {
-      const float x = std::strtof(e, nullptr);
-      if (x >= 0.0f && x < 50.0f) return x;
-    }
-    return 1.0f;
-  }();
-  return v;
-}
-
-// CALLFS_RS_TUNE_LOG=1: rs_plan_tune prints each candidate's time per launch to stderr
-bool tune_log() {
-  static const bool on = [] {
-    const char* e = std::getenv("CALLFS_RS_TUNE_LOG");
-    return e && *e && *e != '0';
-  }();
-  return on;
-}
-
-// The one-shot calls' second half: launch, status, free; RS_E_CORRUPT when a stripe mismatched.
-int launch_once(rs_plan* p, void* stream) {
-  int rc = rs_plan_launch(p, stream);
-  int corrupt = 0;
-  if (!rc) rc = rs_plan_status(p, stream, &corrupt);
-  rs_plan_destroy(p);
-  if (!rc && corrupt) rc = RS_E_CORRUPT;
-  return rc;
-}
-
 // rs_plan_create's body. wanted (k+m flags, or null: every missing shard): the missing shards
 // that get a row; a plan with no row at all has no launch group.
 int create_uniform(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                    const uint8_t* present, const uint8_t* wanted, uint8_t* const* shards,
-                   rs_plan** out);
-
-int one_shot(rs_ctx* ctx, int device, int k, int m, size_t S, int batch, const uint8_t* present,
-             uint8_t* const* shards, void* stream) {
-  rs_plan* p = nullptr;
-  const int rc = rs_plan_create(ctx, device, k, m, S, batch, present, shards, &p);
-  if (rc) return rc;
-  return launch_once(p, stream);
-}
-
-}  // namespace
-
-namespace {
-
-int create_uniform(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
-                   const uint8_t* present, const uint8_t* wanted, uint8_t* const* shards,
                    rs_plan** out) {
   DeviceGuard dg;
-  int rc = check_profile(k, m);
+  int rc = check_plan_args(ctx, k, m, batch, shards, out);
   if (rc) return rc;
-  if (!ctx || !shards || !out || batch < 1) return RS_E_ARG;
-  *out = nullptr;
-  Device* dev = ctx->device(device);
-  if (!dev) return RS_E_ARG;
+  if (!ctx->device(device)) return RS_E_ARG;
   const int n = k + m;
   uint8_t pres[256];
   int np = 0;
@@ -346,6 +231,159 @@ int create_uniform(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
   return RS_OK;
 }
 
+// Lays out and uploads the device buffer of a plan with per-stripe tables (plan.mixed->t built,
+// plan.device and plan.batch set): the status words, the shard-pointer tables, pat and per launch
+// group the compare masks, the table arena and the patterns' row counts, each piece 256-B
+// aligned. With `rt` (a ragged or required plan) also the stripes' sizes and the tile maps, and
+// every launch group is given its own. An out_tab slot at or past a stripe's row count holds
+// null, and a shard no row names is in no table.
+int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rt) {
+  MixedPlan& mp = *plan.mixed;
+  const int k = mp.t.k, n = mp.t.k + mp.t.m, batch = plan.batch;
+  Packer pk;
+  const size_t P = mp.t.patterns.size();
+  plan.status_off = pk.take(sizeof(int) * static_cast<size_t>(batch));
+  mp.in_off = pk.take(sizeof(void*) * static_cast<size_t>(batch) * k);
+  mp.pat_off = pk.take(sizeof(uint32_t) * static_cast<size_t>(batch));
+  for (const MixedGroup& g : mp.t.groups) {
+    MixedPlan::Group at{};
+    at.out_off = pk.take(sizeof(void*) * static_cast<size_t>(batch) * g.R);
+    at.vmask_off = pk.take(sizeof(uint32_t) * P);
+    at.arena_off = pk.take(g.arena.size());
+    at.nrows_off = pk.take(sizeof(uint32_t) * P);
+    mp.groups.push_back(at);
+  }
+  std::vector<size_t> tile0_off, tile_stripe_off;  // per map of rt
+  if (rt) {
+    mp.size_off = pk.take(sizeof(uint64_t) * rt->size.size());
+    for (const TileMap& tm : rt->maps) {
+      tile0_off.push_back(pk.take(sizeof(uint32_t) * tm.tile0.size()));
+      tile_stripe_off.push_back(pk.take(sizeof(uint32_t) * std::max<size_t>(1, tm.tile_stripe.size())));
+    }
+  }
+  std::vector<uint8_t> h(pk.off, 0);
+  auto put = [&](size_t off, const auto& v) {
+    if (!v.empty()) std::memcpy(h.data() + off, v.data(), sizeof(v[0]) * v.size());
+  };
+  auto shard_ptr = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
+  auto* in = reinterpret_cast<const uint8_t**>(h.data() + mp.in_off);
+  for (int b = 0; b < batch; ++b) {
+    const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
+    for (int i = 0; i < k; ++i) in[static_cast<size_t>(b) * k + i] = shard_ptr(b, pt.valid[i]);
+  }
+  put(mp.pat_off, mp.t.pat);
+  for (size_t gi = 0; gi < mp.t.groups.size(); ++gi) {
+    const MixedGroup& g = mp.t.groups[gi];
+    MixedPlan::Group& at = mp.groups[gi];
+    auto* o = reinterpret_cast<uint8_t**>(h.data() + at.out_off);
+    for (int b = 0; b < batch; ++b) {
+      const MixedPattern& pt = mp.t.patterns[mp.t.pat[b]];
+      for (int r = 0; r < g.R; ++r)
+        o[static_cast<size_t>(b) * g.R + r] =
+            static_cast<size_t>(g.row0 + r) < pt.rows.size() ? shard_ptr(b, pt.rows[g.row0 + r]) : nullptr;
+    }
+    put(at.vmask_off, g.vmask);
+    put(at.arena_off, g.arena);
+    put(at.nrows_off, g.nrows);
+    if (rt) {
+      const size_t mi = rt->maps.size() == 1 ? 0 : gi;
+      at.tile0_off = tile0_off[mi];
+      at.tile_stripe_off = tile_stripe_off[mi];
+      at.ntiles = rt->maps[mi].ntiles;
+      at.any_tail = rt->maps[mi].any_tail;
+    }
+  }
+  if (rt) {
+    put(mp.size_off, rt->size);
+    for (size_t mi = 0; mi < rt->maps.size(); ++mi) {
+      put(tile0_off[mi], rt->maps[mi].tile0);
+      put(tile_stripe_off[mi], rt->maps[mi].tile_stripe);
+    }
+  }
+  if (const int rc = upload(plan.dmeta, plan.device, h.data(), h.size())) return rc;
+  // the device copy is all a launch reads: the host arenas can go
+  for (MixedGroup& g : mp.t.groups) std::vector<uint8_t>().swap(g.arena);
+  return RS_OK;
+}
+
+// The tail of the three constructors of plans with per-stripe tables, once their routes to
+// simpler plans are not taken: the tables of `kind`, the plan and its device buffer. sizes and
+// required count for ragged and required plans, S for a mixed one.
+int create_tabled(rs_ctx* ctx, int device, int k, int m, PlanKind kind, size_t S, int batch,
+                  const size_t* sizes, const uint8_t* present, const uint8_t* required,
+                  uint8_t* const* shards, rs_plan** out) {
+  if (!ctx->device(device)) return RS_E_ARG;
+  const bool sized = kind != PlanKind::kMixed;
+  RaggedTables rt;
+  if (const int rc = table_status(sized ? build_ragged_tables(k, m, batch, sizes, present, required, rt)
+                                        : build_mixed_tables(k, m, batch, present, nullptr, rt.mixed)))
+    return rc;
+  auto plan = new_plan(device, sized ? *std::max_element(sizes, sizes + batch) : S, batch);
+  plan->mixed = std::make_unique<MixedPlan>();
+  plan->mixed->kind = kind;
+  plan->mixed->t = std::move(rt.mixed);
+  plan->fixed_form = RS_ORDER_CONSECUTIVE + (kind == PlanKind::kMixed    ? kOrderMixed
+                                             : kind == PlanKind::kRagged ? kOrderRagged
+                                                                         : kOrderRequired);
+  // per stripe with a row: the k shards read, the rows written and the rows compared. Every
+  // stripe of a mixed plan has m rows: n shards of S bytes each.
+  plan->bytes = sized ? rt.bytes : static_cast<uint64_t>(batch) * S * static_cast<uint64_t>(k + m);
+  if (const int rc = upload_mixed(*plan, shards, sized ? &rt : nullptr)) return rc;
+  *out = plan.release();
+  return RS_OK;
+}
+
+// A timed launch that dispatches no kernel still records both events on the stream, so
+// the caller's elapsed time is this launch's (zero), never a stale earlier interval.
+int record_empty(void* stream, void* start_event, void* stop_event) {
+  const auto s = static_cast<hipStream_t>(stream);
+  if (start_event) HIPCHK(hipEventRecord(static_cast<hipEvent_t>(start_event), s));
+  if (stop_event) HIPCHK(hipEventRecord(static_cast<hipEvent_t>(stop_event), s));
+  return RS_OK;
+}
+
+// ---- the tuner's knobs ----------------------------------------------------------------------
+
+constexpr int kTuneRounds = 3;
+constexpr float kTuneWarmMs = 150.0f;
+constexpr int kTuneWarmBatches = 400;
+// CALLFS_RS_TUNE_BAR=<percent>: how much faster than the rule's order another order must
+// time to replace it (default 1)
+float tune_bar() {
+  static const float v = [] {
+    const char* e = std::getenv("CALLFS_RS_TUNE_BAR");
+    if (e && *e) {
+      const float x = std::strtof(e, nullptr);
+      if (x >= 0.0f && x < 50.0f) return x;
+    }
+    return 1.0f;
+  }();
+  return v;
+}
+
+// CALLFS_RS_TUNE_LOG=1: rs_plan_tune prints each candidate's time per launch to stderr
+bool tune_log() {
+  static const bool on = [] {
+    const char* e = std::getenv("CALLFS_RS_TUNE_LOG");
+    return e && *e && *e != '0';
+  }();
+  return on;
+}
+
+// The one-shot calls: create(&plan), launch, status, free; RS_E_CORRUPT when a stripe mismatched.
+template <class Create>
+int one_shot(Create create, void* stream) {
+  rs_plan* p = nullptr;
+  int rc = create(&p);
+  if (rc) return rc;
+  rc = rs_plan_launch(p, stream);
+  int corrupt = 0;
+  if (!rc) rc = rs_plan_status(p, stream, &corrupt);
+  rs_plan_destroy(p);
+  if (!rc && corrupt) rc = RS_E_CORRUPT;
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -360,49 +398,22 @@ int rs_plan_create(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
 int rs_plan_create_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                          const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
   DeviceGuard dg;
-  int rc = check_profile(k, m);
+  int rc = check_plan_args(ctx, k, m, batch, shards && present, out);
+  if (!rc) rc = check_stripes(k, k + m, batch, nullptr, present);
   if (rc) return rc;
-  if (!ctx || !shards || !out || !present || batch < 1) return RS_E_ARG;
-  *out = nullptr;
-  const int n = k + m;
-  // every stripe needs k present shards, whichever path the plan takes
-  for (int b = 0; b < batch; ++b) {
-    int np = 0;
-    for (int i = 0; i < n; ++i) np += present[static_cast<size_t>(b) * n + i] != 0;
-    if (np < k) return RS_E_TOO_FEW_SHARDS;
-  }
   // all masks equal: exactly the uniform plan (its forms, bit-sliced kernels included)
-  if (mixed_masks_equal(n, batch, present))
+  if (required_pairs_equal(k + m, batch, present, nullptr))
     return rs_plan_create(ctx, device, k, m, S, batch, present, shards, out);
-  Device* dev = ctx->device(device);
-  if (!dev) return RS_E_ARG;
-  auto plan = new_plan(device, S, batch);
-  plan->mixed = std::make_unique<MixedPlan>();
-  plan->fixed_form = kOrderMixed + RS_ORDER_CONSECUTIVE;
-  switch (build_mixed_tables(k, m, batch, present, plan->mixed->t)) {
-    case MixedError::kOk: break;
-    case MixedError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
-    case MixedError::kSingular: return RS_E_SINGULAR;
-    case MixedError::kRowCount: return RS_E_ARG;  // the missing-rows form only
-  }
-  // reads: k valid shards + the compared shards; writes: the missing ones = n per stripe
-  plan->bytes = static_cast<uint64_t>(batch) * S * static_cast<uint64_t>(n);
-  rc = upload_mixed(*plan, shards, nullptr);
-  if (rc) return rc;
-  *out = plan.release();
-  return RS_OK;
+  return create_tabled(ctx, device, k, m, PlanKind::kMixed, S, batch, nullptr, present, nullptr, shards, out);
 }
 
 int rs_plan_create_ragged(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
                           const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
   DeviceGuard dg;
-  int rc = check_profile(k, m);
+  int rc = check_plan_args(ctx, k, m, batch, sizes && shards, out);
+  if (!rc) rc = check_stripes(k, k + m, batch, sizes, nullptr);
   if (rc) return rc;
-  if (!ctx || !sizes || !shards || !out || batch < 1) return RS_E_ARG;
-  *out = nullptr;
   const int n = k + m;
-  for (int b = 0; b < batch; ++b)
-    if (sizes[b] == 0) return RS_E_NO_DATA;  // upstream Encode: ErrShardNoData
   // no masks: every stripe is an encode
   std::vector<uint8_t> encode;
   if (!present) {
@@ -414,77 +425,24 @@ int rs_plan_create_ragged(rs_ctx* ctx, int device, int k, int m, int batch, cons
   // are equal too)
   if (ragged_sizes_equal(batch, sizes))
     return rs_plan_create_mixed(ctx, device, k, m, sizes[0], batch, present, shards, out);
-  Device* dev = ctx->device(device);
-  if (!dev) return RS_E_ARG;
-  RaggedTables rt;
-  switch (build_ragged_tables(k, m, batch, sizes, present, rt)) {
-    case RaggedError::kOk: break;
-    case RaggedError::kNoData: return RS_E_NO_DATA;
-    case RaggedError::kTooManyTiles: return RS_E_ARG;  // a grid past 2^31 - 1 tiles
-    case RaggedError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
-    case RaggedError::kSingular: return RS_E_SINGULAR;
-  }
-  auto plan = new_plan(device, *std::max_element(sizes, sizes + batch), batch);
-  plan->mixed = std::make_unique<MixedPlan>();
-  plan->fixed_form = kOrderRagged + RS_ORDER_CONSECUTIVE;
-  MixedPlan& mp = *plan->mixed;
-  mp.t = std::move(rt.mixed);
-  mp.ragged = true;
-  mp.any_tail = rt.any_tail;
-  mp.ntiles = rt.ntiles;
-  // every shard of every stripe is read, compared or written
-  plan->bytes = rt.total * static_cast<uint64_t>(n);
-  rc = upload_mixed(*plan, shards, &rt);
-  if (rc) return rc;
-  *out = plan.release();
-  return RS_OK;
+  return create_tabled(ctx, device, k, m, PlanKind::kRagged, 0, batch, sizes, present, nullptr, shards, out);
 }
 
 int rs_plan_create_required(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
                             const uint8_t* present, const uint8_t* required,
                             uint8_t* const* shards, rs_plan** out) {
   DeviceGuard dg;
-  int rc = check_profile(k, m);
+  int rc = check_plan_args(ctx, k, m, batch, sizes && shards, out);
   if (rc) return rc;
-  if (!ctx || !sizes || !shards || !out || batch < 1) return RS_E_ARG;
-  *out = nullptr;
   const int n = k + m;
   // nothing to leave out (no masks: every stripe an encode): exactly the ragged plan
-  if (!required || !present || required_all_wanted(n, batch, present, required))
+  if (!present || required_all_wanted(n, batch, present, required))
     return rs_plan_create_ragged(ctx, device, k, m, batch, sizes, present, shards, out);
-  for (int b = 0; b < batch; ++b)
-    if (sizes[b] == 0) return RS_E_NO_DATA;
-  for (int b = 0; b < batch; ++b) {
-    int np = 0;
-    for (int i = 0; i < n; ++i) np += present[static_cast<size_t>(b) * n + i] != 0;
-    if (np < k) return RS_E_TOO_FEW_SHARDS;
-  }
+  if ((rc = check_stripes(k, n, batch, sizes, present))) return rc;
   // one size, one (mask, wanted) pair: the uniform plan over the wanted rows
   if (ragged_sizes_equal(batch, sizes) && required_pairs_equal(n, batch, present, required))
     return create_uniform(ctx, device, k, m, sizes[0], batch, present, required, shards, out);
-  Device* dev = ctx->device(device);
-  if (!dev) return RS_E_ARG;
-  RequiredTables rq;
-  switch (build_required_tables(k, m, batch, sizes, present, required, rq)) {
-    case RaggedError::kOk: break;
-    case RaggedError::kNoData: return RS_E_NO_DATA;
-    case RaggedError::kTooManyTiles: return RS_E_ARG;
-    case RaggedError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
-    case RaggedError::kSingular: return RS_E_SINGULAR;
-  }
-  auto plan = new_plan(device, *std::max_element(sizes, sizes + batch), batch);
-  plan->mixed = std::make_unique<MixedPlan>();
-  plan->fixed_form = kOrderRequired + RS_ORDER_CONSECUTIVE;
-  MixedPlan& mp = *plan->mixed;
-  mp.t = std::move(rq.mixed);
-  mp.ragged = true;
-  mp.some = true;
-  // per stripe with a row: the k shards read, the rows written and the rows compared
-  plan->bytes = rq.bytes;
-  rc = upload_mixed(*plan, shards, nullptr, &rq);
-  if (rc) return rc;
-  *out = plan.release();
-  return RS_OK;
+  return create_tabled(ctx, device, k, m, PlanKind::kRequired, 0, batch, sizes, present, required, shards, out);
 }
 
 void rs_plan_destroy(rs_plan* plan) {
@@ -712,40 +670,39 @@ int rs_plan_groups(const rs_plan* plan) { return plan ? static_cast<int>(plan_gr
 
 int rs_encode_dev(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                   uint8_t* const* shards, void* stream) {
-  return one_shot(ctx, device, k, m, S, batch, nullptr, shards, stream);
+  return one_shot([&](rs_plan** p) { return rs_plan_create(ctx, device, k, m, S, batch, nullptr, shards, p); },
+                  stream);
 }
 
 int rs_decode_dev(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                   const uint8_t* present, uint8_t* const* shards, void* stream) {
   if (!present) return RS_E_ARG;
-  return one_shot(ctx, device, k, m, S, batch, present, shards, stream);
+  return one_shot([&](rs_plan** p) { return rs_plan_create(ctx, device, k, m, S, batch, present, shards, p); },
+                  stream);
 }
 
 int rs_decode_dev_mixed(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
                         const uint8_t* present, uint8_t* const* shards, void* stream) {
   if (!present) return RS_E_ARG;
-  rs_plan* p = nullptr;
-  const int rc = rs_plan_create_mixed(ctx, device, k, m, S, batch, present, shards, &p);
-  if (rc) return rc;
-  return launch_once(p, stream);
+  return one_shot(
+      [&](rs_plan** p) { return rs_plan_create_mixed(ctx, device, k, m, S, batch, present, shards, p); }, stream);
 }
 
 int rs_decode_dev_ragged(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
                          const uint8_t* present, uint8_t* const* shards, void* stream) {
-  rs_plan* p = nullptr;
-  const int rc = rs_plan_create_ragged(ctx, device, k, m, batch, sizes, present, shards, &p);
-  if (rc) return rc;
-  return launch_once(p, stream);
+  return one_shot(
+      [&](rs_plan** p) { return rs_plan_create_ragged(ctx, device, k, m, batch, sizes, present, shards, p); },
+      stream);
 }
 
 int rs_decode_dev_required(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
                            const uint8_t* present, const uint8_t* required,
                            uint8_t* const* shards, void* stream) {
-  rs_plan* p = nullptr;
-  const int rc = rs_plan_create_required(ctx, device, k, m, batch, sizes, present, required,
-                                         shards, &p);
-  if (rc) return rc;
-  return launch_once(p, stream);
+  return one_shot(
+      [&](rs_plan** p) {
+        return rs_plan_create_required(ctx, device, k, m, batch, sizes, present, required, shards, p);
+      },
+      stream);
 }
 
 }  // extern "C"

@@ -768,7 +768,7 @@ int main() {
       uint8_t pres[4];
       auto admit = [&](const uint8_t* const* sh, const size_t* ln, bool skip_complete) {
         std::memset(pres, 7, 4);
-        return admit_stripe(4, 2, sh, ln, skip_complete, pres);
+        return admit_stripe(4, 2, sh, ln, nullptr, /*verify=*/!skip_complete, pres);
       };
       auto untouched = [&] { return pres[0] == 7 && pres[1] == 7 && pres[2] == 7 && pres[3] == 7; };
       StripeAdmission a = admit(full, none, false);
@@ -800,6 +800,35 @@ int main() {
       // a size mismatch outranks too few shards
       const size_t odd1[4] = {0, 8, 9, 0};
       CHECK(admit(full, odd1, false).status == RS_E_SHARD_SIZE);
+
+      // a null wanted set is the all-ones one: every lens in {0, S, S'} per shard, every shard
+      // NULL or not, verify on and off agree on status, run, S and a runnable stripe's flags
+      const uint8_t ones[4] = {1, 1, 1, 1};
+      const size_t len_of[3] = {0, 8, 9};
+      int ran = 0, cases = 0;
+      for (int lc = 0; lc < 81; ++lc)
+        for (unsigned nulls = 0; nulls < 16; ++nulls)
+          for (bool verify : {false, true}) {
+            size_t ln[4];
+            const uint8_t* sh[4];
+            for (int i = 0, c = lc; i < 4; ++i, c /= 3) {
+              ln[i] = len_of[c % 3];
+              sh[i] = (nulls >> i) & 1u ? nullptr : buf;
+            }
+            uint8_t f0[4] = {7, 7, 7, 7}, f1[4] = {7, 7, 7, 7};
+            const StripeAdmission x = admit_stripe(4, 2, sh, ln, nullptr, verify, f0);
+            const StripeAdmission y = admit_stripe(4, 2, sh, ln, ones, verify, f1);
+            CHECK(x.status == y.status && x.run == y.run && x.S == y.S);
+            if (x.run) {
+              CHECK(std::memcmp(f0, f1, 4) == 0 && x.status == RS_OK && nulls == 0);
+              for (int i = 0; i < 4; ++i) CHECK(f0[i] == (ln[i] ? kShardPresent : kShardWanted));
+              ++ran;
+            }
+            ++cases;
+          }
+      // runnable: no NULL shard, one size, 2 or 3 present (6 + 4 masks, sizes 8 and 9) with or
+      // without verify, or all 4 present with verify
+      CHECK(cases == 81 * 16 * 2 && ran == 2 * (10 * 2 + 1));
     }
 
     // the routing decision: ragged from two groups on, when allowed; the runnable stripes in

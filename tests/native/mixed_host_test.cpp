@@ -58,8 +58,9 @@ void check_profile(int k, int m, int batch, unsigned seed) {
   const size_t S = 37;
   const std::vector<uint8_t> pres = seeded_masks(k, m, batch, seed);
   MixedTables t;
-  CHECK(build_mixed_tables(k, m, batch, pres.data(), t) == MixedError::kOk);
+  CHECK(build_mixed_tables(k, m, batch, pres.data(), nullptr, t) == TableError::kOk);
   CHECK(t.k == k && t.m == m && t.batch == batch);
+  CHECK(t.rows == m && t.uniform_rows && mixed_rows_are(t, m) && !mixed_rows_are(t, m - 1));
 
   // deduplication: P = number of distinct masks, pat[b] points at an equal mask
   std::set<std::string> distinct;
@@ -87,6 +88,7 @@ void check_profile(int k, int m, int batch, unsigned seed) {
     CHECK(g.tab_stride % 256 == 0);
     CHECK(g.arena.size() == static_cast<size_t>(t.P()) * g.tab_stride);
     CHECK(g.vmask.size() == static_cast<size_t>(t.P()));
+    CHECK(g.nrows == std::vector<uint32_t>(static_cast<size_t>(t.P()), static_cast<uint32_t>(g.R)));
     rows += g.R;
   }
   CHECK(rows == m);
@@ -157,22 +159,91 @@ void check_profile(int k, int m, int batch, unsigned seed) {
               t.groups.size());
 }
 
+// every field of two tables, byte for byte
+void check_same(const MixedTables& a, const MixedTables& b) {
+  CHECK(a.k == b.k && a.m == b.m && a.batch == b.batch && a.rows == b.rows);
+  CHECK(a.uniform_rows == b.uniform_rows && a.pat == b.pat && a.P() == b.P());
+  for (int p = 0; p < a.P(); ++p) {
+    CHECK(a.patterns[p].mask == b.patterns[p].mask && a.patterns[p].valid == b.patterns[p].valid);
+    CHECK(a.patterns[p].rows == b.patterns[p].rows && a.patterns[p].missing == b.patterns[p].missing);
+  }
+  CHECK(a.groups.size() == b.groups.size());
+  for (size_t g = 0; g < a.groups.size(); ++g) {
+    CHECK(a.groups[g].row0 == b.groups[g].row0 && a.groups[g].R == b.groups[g].R);
+    CHECK(a.groups[g].tab_stride == b.groups[g].tab_stride && a.groups[g].arena == b.groups[g].arena);
+    CHECK(a.groups[g].vmask == b.groups[g].vmask && a.groups[g].nrows == b.groups[g].nrows);
+  }
+}
+
+// The full reconstruct is the all-wanted case of the one builder: a null wanted set, every
+// missing shard flagged, and every shard flagged (flags on present shards count for nothing)
+// give the same tables, with and without the compared rows.
+void builder_identity(int k, int m, const std::vector<uint8_t>& pres) {
+  const int n = k + m, batch = static_cast<int>(pres.size()) / n;
+  std::vector<uint8_t> missing(pres.size()), ones(pres.size(), 1);
+  for (size_t j = 0; j < pres.size(); ++j) missing[j] = !pres[j];
+  for (bool with_check : {true, false}) {
+    MixedTables null, flagged, all;
+    CHECK(build_mixed_tables(k, m, batch, pres.data(), nullptr, null, with_check) == TableError::kOk);
+    CHECK(build_mixed_tables(k, m, batch, pres.data(), missing.data(), flagged, with_check) == TableError::kOk);
+    CHECK(build_mixed_tables(k, m, batch, pres.data(), ones.data(), all, with_check) == TableError::kOk);
+    check_same(null, flagged);
+    check_same(null, all);
+    int max_rows = 0;
+    for (const MixedPattern& pt : null.patterns) {
+      DecodePlan dp;
+      CHECK(decode_plan(k, m, pt.mask.data(), dp));
+      CHECK(pt.rows.size() == dp.missing.size() + (with_check ? dp.check.size() : 0));
+      max_rows = std::max(max_rows, static_cast<int>(pt.rows.size()));
+    }
+    CHECK(null.rows == max_rows);
+    if (!with_check) continue;
+    // every pattern has m rows: nrows is R in every group (the last group's R is the remainder)
+    CHECK(null.rows == m && null.uniform_rows);
+    CHECK(null.groups.size() == static_cast<size_t>((m + kMixedRowsPerLaunch - 1) / kMixedRowsPerLaunch));
+    for (const MixedGroup& g : null.groups)
+      for (uint32_t nr : g.nrows) CHECK(nr == static_cast<uint32_t>(g.R));
+  }
+  std::printf("RS(%d,%d) batch %d: null, flagged and all-ones wanted sets build equal tables ok\n", k, m, batch);
+}
+
 }  // namespace
 
 int main() {
   check_profile(10, 4, 40, 1);
   check_profile(20, 12, 24, 2);
+  {  // RS(4,2): every mask with at least k present, in ascending and then descending order
+    const int n = 6;
+    std::vector<uint8_t> pres;
+    for (int pass = 0; pass < 2; ++pass)
+      for (unsigned i = 0; i < (1u << n); ++i) {
+        const unsigned pm = pass ? (1u << n) - 1 - i : i;
+        if (__builtin_popcount(pm) < 4) continue;
+        for (int b = 0; b < n; ++b) pres.push_back((pm >> b) & 1u);
+      }
+    CHECK(pres.size() == 2u * 22 * n);
+    builder_identity(4, 2, pres);
+  }
+  {  // RS(3,20): 16 + 4 rows, two launch groups
+    const int n = 23;
+    const int lost[5] = {20, 0, 7, 20, 16};  // stripe s misses shards first[s] .. first[s] + lost[s] - 1
+    const int first[5] = {0, 0, 2, 3, 1};
+    std::vector<uint8_t> pres(5 * n, 1);
+    for (int s = 0; s < 5; ++s)
+      for (int i = 0; i < lost[s]; ++i) pres[s * n + first[s] + i] = 0;
+    builder_identity(3, 20, pres);
+  }
   {  // too few shards anywhere in the batch fails the whole build
     const int k = 10, m = 4, n = 14;
     std::vector<uint8_t> pres(3 * n, 1);
     for (int i = 0; i < 5; ++i) pres[n + i] = 0;
     MixedTables t;
-    CHECK(build_mixed_tables(k, m, 3, pres.data(), t) == MixedError::kTooFewShards);
-    CHECK(!mixed_masks_equal(n, 3, pres.data()));
+    CHECK(build_mixed_tables(k, m, 3, pres.data(), nullptr, t) == TableError::kTooFewShards);
+    CHECK(!required_pairs_equal(n, 3, pres.data(), nullptr));
     std::vector<uint8_t> same(3 * n, 1);
     same[2] = same[n + 2] = same[2 * n + 2] = 0;
     same[5] = 7;  // nonzero = present
-    CHECK(mixed_masks_equal(n, 3, same.data()));
+    CHECK(required_pairs_equal(n, 3, same.data(), nullptr));
   }
   std::printf("mixed_host_test ok\n");
   return 0;

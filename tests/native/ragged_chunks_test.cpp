@@ -7,7 +7,8 @@
 // overlap; the input rows form one range that holds the metadata, the output rows and status
 // words a second one disjoint from it; the tile map equals build_tile_map of the items'
 // widths; part flags fold onto the right stripe; the verify == 0 classes partition the stripes
-// by missing count and their patterns have that many rows; segments respect the arena budget.
+// by missing count and their patterns have that many rows; segments respect the arena budget;
+// all-wanted flag rows give the classes and segment cuts of a call without a wanted set.
 //
 // The budget: a part cannot be narrower than one 8,192-byte tile, and n shards of 8,192 bytes
 // plus metadata exceed 64 KiB for n > 7. There the bound that can hold is the staging of one
@@ -65,9 +66,8 @@ void check_run(int k, int m, int rows, bool missing_only, const std::vector<size
                const std::vector<uint8_t>& pres, size_t budget) {
   const int n = k + m, stripes = static_cast<int>(sizes.size());
   MixedTables mt;
-  CHECK((missing_only ? build_mixed_tables_missing(k, m, rows, stripes, pres.data(), mt)
-                      : build_mixed_tables(k, m, stripes, pres.data(), mt)) == MixedError::kOk);
-  CHECK(mt.rows == rows);
+  CHECK(build_mixed_tables(k, m, stripes, pres.data(), nullptr, mt, !missing_only) == TableError::kOk);
+  CHECK(mt.rows == rows && mixed_rows_are(mt, rows));
   RaggedShape sh;
   sh.k = k;
   for (const MixedGroup& g : mt.groups) sh.group_rows.push_back(g.R);
@@ -157,10 +157,11 @@ void check_run(int k, int m, int rows, bool missing_only, const std::vector<size
     fill_chunk_meta(C, sh, items, mt, mt.pat.data(), h.data(),
                     [&](size_t j, int i) { return base + C.items[j].in_off + C.items[j].pitch * i; },
                     [&](size_t j, int row) { return base + 1 + j * 1000 + row; });
-    RaggedTables tm;
-    CHECK(build_tile_map(static_cast<int>(C.count), widths.data(), tm) == RaggedError::kOk);
+    TileMap tm;
+    CHECK(build_tile_map(static_cast<int>(C.count), widths.data(), nullptr, tm) == TableError::kOk);
     CHECK(tm.ntiles == C.ntiles && tm.any_tail == C.any_tail);
-    CHECK(std::memcmp(h.data() + C.size_off, tm.size.data(), 8 * C.count) == 0);
+    const std::vector<uint64_t> size64(widths.begin(), widths.end());
+    CHECK(std::memcmp(h.data() + C.size_off, size64.data(), 8 * C.count) == 0);
     CHECK(std::memcmp(h.data() + C.tile0_off, tm.tile0.data(), 4 * (C.count + 1)) == 0);
     CHECK(std::memcmp(h.data() + C.tile_stripe_off, tm.tile_stripe.data(), 4 * static_cast<size_t>(C.ntiles)) == 0);
     const auto* in = reinterpret_cast<uint8_t* const*>(h.data() + C.in_tab_off);
@@ -196,39 +197,40 @@ void check_classes_and_segments(int k, int m, std::mt19937& rng) {
   const int n = k + m, stripes = 40;
   const std::vector<uint8_t> pres = random_masks(k, m, stripes, rng, 0);
   // with compares: one class of every stripe
-  auto one = ragged_classes(n, stripes, pres.data(), false);
-  CHECK(one.size() == 1 && static_cast<int>(one[0].stripes.size()) == stripes);
+  auto one = ragged_classes(n, k, stripes, pres.data(), true);
+  CHECK(one.size() == 1 && static_cast<int>(one[0].stripes.size()) == stripes && one[0].rows == m);
   // verify == 0: a partition of the stripes with something missing, by missing count
-  auto cls = ragged_classes(n, stripes, pres.data(), true);
+  auto cls = ragged_classes(n, k, stripes, pres.data(), false);
   std::vector<int> seen(stripes, 0);
   int last_e = 0;
   for (const RaggedClass& c : cls) {
-    CHECK(c.e > last_e && !c.stripes.empty());
-    last_e = c.e;
+    CHECK(c.rows > last_e && !c.stripes.empty());
+    last_e = c.rows;
     std::vector<uint8_t> sub;
     for (int b : c.stripes) {
       int e = 0;
       for (int i = 0; i < n; ++i) e += !pres[static_cast<size_t>(b) * n + i];
-      CHECK(e == c.e);
+      CHECK(e == c.rows);
       CHECK(!seen[b]++);
       sub.insert(sub.end(), pres.begin() + static_cast<size_t>(b) * n, pres.begin() + static_cast<size_t>(b + 1) * n);
     }
     MixedTables mt;
-    CHECK(build_mixed_tables_missing(k, m, c.e, static_cast<int>(c.stripes.size()), sub.data(), mt) == MixedError::kOk);
+    CHECK(build_mixed_tables(k, m, static_cast<int>(c.stripes.size()), sub.data(), nullptr, mt, false) == TableError::kOk);
+    CHECK(mixed_rows_are(mt, c.rows));
     int grows = 0;
     for (const MixedGroup& g : mt.groups) {
       grows += g.R;
       for (uint32_t v : g.vmask) CHECK(v == 0);  // every row written
       CHECK(g.arena.size() == mt.patterns.size() * g.tab_stride);
     }
-    CHECK(grows == c.e);
-    for (const MixedPattern& p : mt.patterns) CHECK(static_cast<int>(p.rows.size()) == c.e && p.missing == c.e);
+    CHECK(grows == c.rows);
+    for (const MixedPattern& p : mt.patterns) CHECK(static_cast<int>(p.rows.size()) == c.rows && p.missing == c.rows);
     // the rows are those of the full tables' missing rows
     MixedTables full;
-    CHECK(build_mixed_tables(k, m, static_cast<int>(c.stripes.size()), sub.data(), full) == MixedError::kOk);
+    CHECK(build_mixed_tables(k, m, static_cast<int>(c.stripes.size()), sub.data(), nullptr, full) == TableError::kOk);
     CHECK(full.rows == m && full.patterns.size() == mt.patterns.size());
     for (size_t p = 0; p < mt.patterns.size(); ++p)
-      for (int r = 0; r < c.e; ++r) {
+      for (int r = 0; r < c.rows; ++r) {
         CHECK(mt.patterns[p].rows[r] == full.patterns[p].rows[r]);
         const MixedGroup& a = mt.groups[r / 16];
         const MixedGroup& b = full.groups[r / 16];
@@ -237,7 +239,8 @@ void check_classes_and_segments(int k, int m, std::mt19937& rng) {
           CHECK(a.arena[p * a.tab_stride + i * 32 * Wa + Wa + r % 16] == b.arena[p * b.tab_stride + i * 32 * Wb + Wb + r % 16]);
       }
     // a wrong missing count is refused
-    if (c.e < m) CHECK(build_mixed_tables_missing(k, m, c.e + 1, 1, sub.data(), mt) == MixedError::kRowCount);
+    CHECK(build_mixed_tables(k, m, 1, sub.data(), nullptr, mt, false) == TableError::kOk);
+    CHECK(mixed_rows_are(mt, c.rows) && !mixed_rows_are(mt, c.rows + 1) && !mixed_rows_are(mt, c.rows - 1));
   }
   for (int b = 0; b < stripes; ++b) {
     int e = 0;
@@ -261,12 +264,70 @@ void check_classes_and_segments(int k, int m, std::mt19937& rng) {
       // the tables built over the segment are what the bound speaks of
       std::vector<uint8_t> sub(pres.begin() + s.first * n, pres.begin() + s.second * n);
       MixedTables mt;
-      CHECK(build_mixed_tables(k, m, static_cast<int>(s.second - s.first), sub.data(), mt) == MixedError::kOk);
+      CHECK(build_mixed_tables(k, m, static_cast<int>(s.second - s.first), sub.data(), nullptr, mt) == TableError::kOk);
       size_t arena = 0;
       for (const MixedGroup& g : mt.groups) arena += g.arena.size();
       CHECK(arena == distinct.size() * per);
     }
     CHECK(at == static_cast<size_t>(stripes));
+  }
+}
+
+// Flag rows that hold kShardWanted / kShardPresent alone (a plain 0 / 1 mask: every missing
+// shard wanted) give the classes and segments of a call without a wanted set. The expectation
+// is written out from those rules: with compares one class of every stripe (each has m rows);
+// without, one class per missing count in ascending order, stripes in call order, none for a
+// complete stripe; a segment ends before the stripe whose mask would be one distinct mask more
+// than max(1, budget / bytes per pattern).
+void check_all_wanted_rules(int k, int m, std::mt19937& rng) {
+  const int n = k + m, stripes = 60;
+  std::vector<uint8_t> pres = random_masks(k, m, stripes, rng, 0);
+  for (int b = 10; b < stripes; b += 3) {  // repeats of earlier masks
+    const int src = static_cast<int>(rng() % static_cast<unsigned>(b));
+    std::copy(pres.begin() + src * n, pres.begin() + (src + 1) * n, pres.begin() + b * n);
+  }
+  static_assert(kShardWanted == 0 && kShardPresent == 1, "a 0 / 1 mask is a flag row");
+  auto missing = [&](int b) {
+    int e = 0;
+    for (int i = 0; i < n; ++i) e += pres[static_cast<size_t>(b) * n + i] == 0;
+    return e;
+  };
+  const auto with = ragged_classes(n, k, stripes, pres.data(), true);
+  CHECK(with.size() == 1 && with[0].rows == m);
+  for (int b = 0; b < stripes; ++b) CHECK(with[0].stripes.at(b) == b);
+  std::vector<std::pair<int, std::vector<int>>> want;
+  for (int e = 1; e <= n; ++e) {
+    std::vector<int> ids;
+    for (int b = 0; b < stripes; ++b)
+      if (missing(b) == e) ids.push_back(b);
+    if (!ids.empty()) want.push_back({e, ids});
+  }
+  const auto without = ragged_classes(n, k, stripes, pres.data(), false);
+  CHECK(without.size() == want.size());
+  for (size_t c = 0; c < want.size(); ++c)
+    CHECK(without[c].rows == want[c].first && without[c].stripes == want[c].second);
+
+  std::vector<int> order(stripes);
+  for (int b = 0; b < stripes; ++b) order[b] = b;
+  std::shuffle(order.begin(), order.end(), rng);
+  const size_t per = pattern_arena_bytes(k, m);
+  for (size_t budget : {size_t(1), per, 2 * per, 5 * per + 7, 1000 * per}) {
+    const size_t cap = std::max<size_t>(1, budget / per);
+    std::vector<std::pair<size_t, size_t>> cuts;
+    std::vector<std::vector<uint8_t>> held;
+    size_t begin = 0;
+    for (size_t j = 0; j < order.size(); ++j) {
+      const std::vector<uint8_t> mask(pres.begin() + order[j] * n, pres.begin() + (order[j] + 1) * n);
+      const bool known = std::find(held.begin(), held.end(), mask) != held.end();
+      if (!known && held.size() == cap) {
+        cuts.push_back({begin, j});
+        begin = j;
+        held.clear();
+      }
+      if (!known) held.push_back(mask);
+    }
+    cuts.push_back({begin, order.size()});
+    CHECK(ragged_segments(k, n, m, order, pres.data(), budget) == cuts);
   }
 }
 
@@ -299,6 +360,7 @@ int main() {
       }
     }
     check_classes_and_segments(k, m, rng);
+    check_all_wanted_rules(k, m, rng);
   }
   // an RS(128,128) batch of 500 patterns stays within the arena budget per segment
   {

@@ -2,7 +2,7 @@
 // g++ -fsanitize=address,undefined by tests/test_native_required.py:
 //  - decode_plan with a wanted set is the matching subset of the full plan's rows, for RS(4,2)
 //    over every (mask, wanted) pair and for RS(10,4) over seeded pairs;
-//  - build_mixed_tables_required's arenas, applied with a scalar GF(2^8) lookup to the shards
+//  - build_mixed_tables' arenas for a wanted set, applied with a scalar GF(2^8) lookup to the shards
 //    a pattern reads, give the bytes of the shards its rows name (those of a consistent stripe:
 //    what a full reconstruct writes) for rows below nrows, and are zero past nrows;
 //  - patterns are deduplicated on the (mask, wanted) pair;
@@ -10,8 +10,8 @@
 //    16 + 4 rows); stripes with no row are in no map, a batch of such stripes has no group;
 //  - the index of an unwanted missing shard is in no pattern's `valid` or `rows`: its pointer
 //    reaches no in_tab or out_tab;
-//  - the host calls' admission with a wanted set (host_path.hpp admit_stripe_required) and the
-//    classes and segments their ragged runs are cut into (ragged_chunks.hpp).
+//  - the host calls' admission with a wanted set (host_path.hpp admit_stripe) and the classes
+//    and segments their ragged runs are cut into (ragged_chunks.hpp).
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -155,9 +155,9 @@ int rows_of(const MixedTables& t, int s) { return static_cast<int>(t.patterns[t.
 void check_required(int k, int m, int batch, unsigned seed) {
   const int n = k + m;
   const Batch b = make_batch(k, m, batch, seed);
-  RequiredTables rq;
-  CHECK(build_required_tables(k, m, batch, b.sizes.data(), b.pres.data(), b.want.data(), rq) ==
-        RaggedError::kOk);
+  RaggedTables rq;
+  CHECK(build_ragged_tables(k, m, batch, b.sizes.data(), b.pres.data(), b.want.data(), rq) ==
+        TableError::kOk);
   const MixedTables& t = rq.mixed;
   CHECK(t.k == k && t.m == m && t.batch == batch && static_cast<int>(t.pat.size()) == batch);
 
@@ -200,6 +200,9 @@ void check_required(int k, int m, int batch, unsigned seed) {
   }
   CHECK(rows_of(t, 0) == 0 && rows_of(t, 1) == m);
   CHECK(t.rows == max_rows);
+  bool uniform = true;
+  for (const MixedPattern& pt : t.patterns) uniform &= static_cast<int>(pt.rows.size()) == max_rows;
+  CHECK(t.uniform_rows == uniform && !uniform && !mixed_rows_are(t, max_rows));
   CHECK(static_cast<int>(t.groups.size()) == (max_rows + kMixedRowsPerLaunch - 1) / kMixedRowsPerLaunch);
   CHECK(rq.maps.size() == t.groups.size());
   for (int s = 0; s < batch; ++s)
@@ -241,7 +244,7 @@ void check_required(int k, int m, int batch, unsigned seed) {
           for (int c = nr; c < W; ++c) CHECK(tab[(static_cast<size_t>(i) * 32u + e) * W + c] == 0);
     }
     // the group's tile map: exactly the stripes with a row in the group, in order
-    const GroupTileMap& gm = rq.maps[gi];
+    const TileMap& gm = rq.maps[gi];
     CHECK(gm.tile0.size() == static_cast<size_t>(batch) + 1);
     uint32_t at = 0;
     int stripes = 0;
@@ -275,8 +278,8 @@ void two_groups() {
       pres[s * n + i] = 0;
       want[s * n + i] = i <= wanted[s];
     }
-  RequiredTables rq;
-  CHECK(build_required_tables(k, m, batch, sizes.data(), pres.data(), want.data(), rq) == RaggedError::kOk);
+  RaggedTables rq;
+  CHECK(build_ragged_tables(k, m, batch, sizes.data(), pres.data(), want.data(), rq) == TableError::kOk);
   for (int s = 0; s < batch; ++s) CHECK(rows_of(rq.mixed, s) == rows[s]);
   CHECK(rq.mixed.groups.size() == 2 && rq.mixed.groups[0].R == 16 && rq.mixed.groups[1].R == 4);
   CHECK(rq.maps[0].stripes == 5 && rq.maps[1].stripes == 3);
@@ -295,18 +298,33 @@ void no_rows_and_errors() {
   std::vector<uint8_t> pres = {1, 0, 1, 1, 0, 1, 0, 0, 1, 1, 1, 1};
   std::vector<uint8_t> want = {1, 0, 1, 1, 0, 1, 0, 0, 0, 0, 1, 0};
   std::vector<size_t> sizes = {100, 9000};
-  RequiredTables rq;
-  CHECK(build_required_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == RaggedError::kOk);
+  RaggedTables rq;
+  CHECK(build_ragged_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == TableError::kOk);
   CHECK(rq.mixed.groups.empty() && rq.maps.empty() && rq.bytes == 0 && rq.mixed.rows == 0);
   CHECK(rq.mixed.P() == 2 && rq.mixed.patterns[0].rows.empty());
   CHECK(!required_all_wanted(n, 2, pres.data(), want.data()));
   CHECK(!required_pairs_equal(n, 2, pres.data(), want.data()));
+  if (sizeof(size_t) >= 8) {
+    // the tile and byte limits count the stripes with a row alone; too few shards comes first
+    sizes[1] = ~static_cast<size_t>(0);
+    CHECK(build_ragged_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == TableError::kOk);
+    CHECK(rq.bytes == 0 && rq.maps.empty());
+    want[6] = 1;  // stripe 1 wants its shard 0: one row over 2^64 - 1 bytes
+    CHECK(build_ragged_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == TableError::kTooManyTiles);
+    sizes[1] = static_cast<size_t>(1) << 45;  // no byte overflow, 2^32 tiles
+    CHECK(build_ragged_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == TableError::kTooManyTiles);
+    pres[2] = 0;
+    CHECK(build_ragged_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == TableError::kTooFewShards);
+    pres[2] = 1;
+    want[6] = 0;
+    sizes[1] = 9000;
+  }
   // errors: a zero size, k - 1 present shards
   sizes[1] = 0;
-  CHECK(build_required_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == RaggedError::kNoData);
+  CHECK(build_ragged_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == TableError::kNoData);
   sizes[1] = 5;
   pres[2] = 0;
-  CHECK(build_required_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == RaggedError::kTooFewShards);
+  CHECK(build_ragged_tables(k, m, 2, sizes.data(), pres.data(), want.data(), rq) == TableError::kTooFewShards);
   // the routing predicates: flags on present shards count for nothing
   std::vector<uint8_t> p2 = {1, 0, 1, 1, 1, 1, 1, 0, 1, 1, 1, 1};
   std::vector<uint8_t> w2 = {0, 1, 0, 0, 0, 0, 1, 1, 1, 0, 0, 1};
@@ -329,7 +347,7 @@ void host_admission_and_classes() {
     std::vector<const uint8_t*> sh(n, buf);
     for (int i : null) sh[i] = nullptr;
     flags->assign(n, 9);
-    return admit_stripe_required(n, k, sh.data(), lens.data(), want.data(), verify, flags->data());
+    return admit_stripe(n, k, sh.data(), lens.data(), want.data(), verify, flags->data());
   };
   std::vector<uint8_t> f;
   // one wanted, one unwanted (NULL) missing shard
@@ -363,25 +381,25 @@ void host_admission_and_classes() {
       W, W, P, P, P, P,  // w 2, c 0
       P, U, P, P, P, P,  // w 0, c 1
   };
-  auto cls = ragged_classes_required(n, k, 6, flags.data(), true);
-  CHECK(cls.size() == 2 && cls[0].e == 1 && cls[1].e == 2);
+  auto cls = ragged_classes(n, k, 6, flags.data(), true);
+  CHECK(cls.size() == 2 && cls[0].rows == 1 && cls[1].rows == 2);
   CHECK((cls[0].stripes == std::vector<int>{0, 5}) && (cls[1].stripes == std::vector<int>{2, 3, 4}));
-  cls = ragged_classes_required(n, k, 6, flags.data(), false);
-  CHECK(cls.size() == 2 && cls[0].e == 1 && cls[1].e == 2);
+  cls = ragged_classes(n, k, 6, flags.data(), false);
+  CHECK(cls.size() == 2 && cls[0].rows == 1 && cls[1].rows == 2);
   CHECK((cls[0].stripes == std::vector<int>{0, 2}) && (cls[1].stripes == std::vector<int>{4}));
-  CHECK(ragged_classes_required(n, k, 1, flags.data() + n, true).empty());
+  CHECK(ragged_classes(n, k, 1, flags.data() + n, true).empty());
   // segments: one mask with two wanted sets is two patterns
   const std::vector<uint8_t> two = {P, W, P, P, P, U, P, U, P, P, P, W, P, W, P, P, P, U};
   const size_t per = pattern_arena_bytes(k, 1);
-  auto segs = ragged_segments_required(k, n, 1, {0, 1, 2}, two.data(), per);
+  auto segs = ragged_segments(k, n, 1, {0, 1, 2}, two.data(), per);
   CHECK(segs.size() == 3);
-  segs = ragged_segments_required(k, n, 1, {0, 2, 1}, two.data(), per);
+  segs = ragged_segments(k, n, 1, {0, 2, 1}, two.data(), per);
   CHECK(segs.size() == 2 && segs[0] == std::make_pair(size_t(0), size_t(2)));
-  segs = ragged_segments_required(k, n, 1, {0, 1, 2}, two.data(), 2 * per);
+  segs = ragged_segments(k, n, 1, {0, 1, 2}, two.data(), 2 * per);
   CHECK(segs.size() == 1);
   // every pattern of a class has the class's rows: the tables the ragged kernels expect
   for (bool verify : {true, false})
-    for (const RaggedClass& c : ragged_classes_required(n, k, 6, flags.data(), verify)) {
+    for (const RaggedClass& c : ragged_classes(n, k, 6, flags.data(), verify)) {
       std::vector<uint8_t> pres, want;
       for (int b : c.stripes)
         for (int i = 0; i < n; ++i) {
@@ -389,10 +407,10 @@ void host_admission_and_classes() {
           want.push_back(flags[b * n + i] == W);
         }
       MixedTables t;
-      CHECK(build_mixed_tables_required(k, m, static_cast<int>(c.stripes.size()), pres.data(), want.data(), t,
-                                        verify) == MixedError::kOk);
-      CHECK(t.rows == c.e);
-      for (const MixedPattern& pt : t.patterns) CHECK(static_cast<int>(pt.rows.size()) == c.e);
+      CHECK(build_mixed_tables(k, m, static_cast<int>(c.stripes.size()), pres.data(), want.data(), t, verify) ==
+            TableError::kOk);
+      CHECK(t.rows == c.rows && t.uniform_rows && mixed_rows_are(t, c.rows) && !mixed_rows_are(t, c.rows + 1));
+      for (const MixedPattern& pt : t.patterns) CHECK(static_cast<int>(pt.rows.size()) == c.rows);
       for (const MixedGroup& g : t.groups)
         for (uint32_t nr : g.nrows) CHECK(static_cast<int>(nr) == g.R);
     }

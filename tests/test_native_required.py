@@ -1,6 +1,6 @@
 """Host-side tables of required device plans (decode_plan with a wanted set,
-callfs_amd/csrc/mixed_tables.hpp build_mixed_tables_required, ragged_tables.hpp
-build_required_tables) built with g++ under AddressSanitizer+UBSan and run on the CPU as a
+callfs_amd/csrc/mixed_tables.hpp build_mixed_tables, ragged_tables.hpp build_ragged_tables
+with a wanted set) built with g++ under AddressSanitizer+UBSan and run on the CPU as a
 stand-alone program, and the C ABI's side of it: the header declares the new calls and the
 library exports them."""
 import os
