@@ -118,6 +118,15 @@ SIGNATURES = {
                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rs_decode_dev_required": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p, _u8p,
                                       ctypes.POINTER(_vp), _vp]),
+    "rs_plan_create_update": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
+                                     ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                     ctypes.POINTER(_vp)]),
+    "rs_update": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                         ctypes.POINTER(_vp)]),
+    "rs_encode_idx": (_int, [_vp, _int, _int, _sz, _vp, _int, ctypes.POINTER(_vp)]),
+    "rs_update_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_sz), ctypes.POINTER(_vp),
+                               ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_int)]),
+    "rs_codec_overwrite": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), _i64, _vp, _sz]),
     "rs_sha256_plan_create": (_int, [_vp, _int, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64),
                                      _int, ctypes.POINTER(_vp)]),
     "rs_sha256_plan_launch": (_int, [_vp, _vp, _vp]),

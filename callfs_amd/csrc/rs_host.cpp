@@ -12,6 +12,8 @@
 #include "codec_batch.hpp"
 #include "host_ragged.hpp"
 #include "host_uniform.hpp"
+#include "host_update.hpp"
+#include "overwrite_plan.hpp"
 
 using namespace callfs;
 
@@ -185,6 +187,38 @@ int reconstruct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const*
   return first_error(status, batch);
 }
 
+// Shared by rs_update, rs_encode_idx, rs_update_batch and rs_codec_overwrite: stripe b's shard i
+// changed where new_data[b*k + i] is non-NULL; old_data null (the array) is EncodeIdx mode.
+// status[b]: RS_OK, RS_E_NO_DATA (a change in a stripe of size 0) or RS_E_ARG (a changed shard
+// without its old bytes, a NULL parity pointer); the other stripes run. Stripes without a
+// change are RS_OK and reach no device.
+int update_batch_host(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes,
+                      const uint8_t* const* old_data, const uint8_t* const* new_data,
+                      uint8_t* const* parity, int* status) {
+  const size_t B = static_cast<size_t>(batch), K = static_cast<size_t>(k);
+  std::vector<uint8_t> changed(B * K, 0);
+  std::vector<int> ids;
+  for (size_t b = 0; b < B; ++b) {
+    status[b] = RS_OK;
+    bool any = false, bad = false;
+    for (size_t i = 0; i < K; ++i) {
+      if (!new_data[b * K + i]) continue;
+      any = true;
+      changed[b * K + i] = 1;
+      bad |= old_data && !old_data[b * K + i];
+    }
+    if (!any) continue;
+    for (int j = 0; j < m; ++j) bad |= !parity[b * static_cast<size_t>(m) + j];
+    if (sizes[b] == 0) status[b] = RS_E_NO_DATA;
+    else if (bad) status[b] = RS_E_ARG;
+    else ids.push_back(static_cast<int>(b));
+  }
+  return run_update(ctx, k, m, old_data != nullptr, ids, sizes, changed.data(),
+                    [&](int b, int i) { return old_data[static_cast<size_t>(b) * K + i]; },
+                    [&](int b, int i) { return new_data[static_cast<size_t>(b) * K + i]; },
+                    [&](int b, int j) { return parity[static_cast<size_t>(b) * m + j]; });
+}
+
 // rs_codec_decode, and with data_only rs_codec_decode_data: upstream ReconstructData in
 // Reconstruct's place, so missing parity stays missing.
 int codec_decode(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens, uint8_t* out,
@@ -354,6 +388,90 @@ int rs_reconstruct_some_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* con
   if (!ctx || batch < 0 || (batch && (!shards || !lens || !status))) return RS_E_ARG;
   return reconstruct_batch_host(ctx, k, m, batch, shards, lens, verify != 0, nullptr, nullptr, status,
                                 required);
+}
+
+// ---- exported: parity updated in place --------------------------------
+
+int rs_update_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes,
+                    const uint8_t* const* old_data, const uint8_t* const* new_data,
+                    uint8_t* const* parity, int* status) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!sizes || !new_data || !parity || !status))) return RS_E_ARG;
+  if ((rc = update_batch_host(ctx, k, m, batch, sizes, old_data, new_data, parity, status))) return rc;
+  return first_error(status, batch);
+}
+
+int rs_update(rs_ctx* ctx, int k, int m, size_t S, const uint8_t* const* old_data,
+              const uint8_t* const* new_data, uint8_t* const* parity) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !old_data || !new_data || !parity) return RS_E_ARG;
+  // upstream Update: ErrInvalidInput for a new shard without its old one, before anything runs
+  for (int i = 0; i < k; ++i)
+    if (new_data[i] && !old_data[i]) return RS_E_ARG;
+  int status = RS_OK;
+  if ((rc = update_batch_host(ctx, k, m, 1, &S, old_data, new_data, parity, &status))) return rc;
+  return status;
+}
+
+int rs_encode_idx(rs_ctx* ctx, int k, int m, size_t S, const uint8_t* shard, int idx,
+                  uint8_t* const* parity) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shard || !parity || idx < 0 || idx >= k) return RS_E_ARG;  // upstream ErrInvalidShardIdx
+  std::vector<const uint8_t*> one(static_cast<size_t>(k), nullptr);
+  one[static_cast<size_t>(idx)] = shard;
+  int status = RS_OK;
+  if ((rc = update_batch_host(ctx, k, m, 1, &S, nullptr, one.data(), parity, &status))) return rc;
+  return status;
+}
+
+int rs_codec_overwrite(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* shards, int64_t offset,
+                       const uint8_t* data, size_t len) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shards || !data || offset < 0) return RS_E_ARG;
+  std::vector<OverwriteInterval> iv;
+  if (!overwrite_plan(k, S, static_cast<uint64_t>(offset), len, iv)) return RS_E_ARG;
+  const size_t K = static_cast<size_t>(k), M = static_cast<size_t>(m);
+  const size_t first = static_cast<size_t>(offset) / S, last = (static_cast<size_t>(offset) + len - 1) / S;
+  for (size_t i = first; i <= last; ++i)
+    if (!shards[i]) return RS_E_ARG;
+  for (size_t j = 0; j < M; ++j)
+    if (!shards[K + j]) return RS_E_ARG;
+  // one stripe per column interval: its changed shards' old bytes in the shards, their new
+  // bytes in `data`, its parity columns
+  const size_t B = iv.size();
+  std::vector<size_t> sizes(B);
+  std::vector<const uint8_t*> old_data(B * K, nullptr), new_data(B * K, nullptr);
+  std::vector<uint8_t*> parity(B * M);
+  for (size_t b = 0; b < B; ++b) {
+    sizes[b] = iv[b].col1 - iv[b].col0;
+    for (int i = iv[b].shard0; i <= iv[b].shard1; ++i) {
+      old_data[b * K + i] = shards[i] + iv[b].col0;
+      new_data[b * K + i] = data + (static_cast<size_t>(i) * S + iv[b].col0 - static_cast<size_t>(offset));
+    }
+    for (size_t j = 0; j < M; ++j) parity[b * M + j] = shards[K + j] + iv[b].col0;
+  }
+  std::vector<int> status(B, RS_OK);
+  if ((rc = update_batch_host(ctx, k, m, static_cast<int>(B), sizes.data(), old_data.data(),
+                              new_data.data(), parity.data(), status.data())))
+    return rc;
+  if ((rc = first_error(status.data(), static_cast<int>(B)))) return rc;
+  // the parity is new: now the data shards
+  std::vector<CopyPool::Seg> segs;
+  for (size_t i = first; i <= last; ++i) {
+    const size_t lo = std::max(static_cast<size_t>(offset), i * S);
+    const size_t hi = std::min(static_cast<size_t>(offset) + len, (i + 1) * S);
+    segs.push_back({shards[i] + (lo - i * S), data + (lo - static_cast<size_t>(offset)), hi - lo});
+  }
+  ctx->pool.run(segs);
+  return RS_OK;
 }
 
 // ---- exported: codec-level batches (objects in, objects out) ----------------------------

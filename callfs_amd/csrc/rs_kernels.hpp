@@ -261,6 +261,36 @@ struct RaggedSomeArgs {
 // (kOrderRequired + the TileOrder it runs in, always consecutive: rs_plan_forms of a required plan)
 constexpr int kOrderRequired = 2048;
 
+// ---- update launches (rs_update.hpp in rs_mixed.hip) ---------------------
+// Upstream Update / EncodeIdx: a ragged launch group whose rows start from the destination's
+// current bytes. Stripe s reads the nsrc[pat[s]] changed shards of its pattern alone and does
+//   out[s][r] ^= XOR_{i < nsrc} coef[r][i] * d_i,   d_i = old_i ^ new_i (pair) or the shard (single)
+// in_tab is pitched at in_stride pointers per stripe: source i of a pair launch is
+// (in_tab[s][2i], in_tab[s][2i + 1]) = (old, new), of a single launch in_tab[s][i]. The tile
+// map holds only the stripes with a changed shard; a.K is the largest source count of a
+// pattern (the tables' pitch and the LDS size), out_tab is pitched at a.R. No verify mask and
+// no status word: a.status, vmask and a.verify_mask are not read.
+struct UpdateArgs {
+  const uint32_t* pat;          // [batch] pattern of each stripe
+  const uint32_t* nsrc;         // [P] changed shards of each pattern, 1..a.K
+  const uint64_t* size;         // [batch] shard bytes of each stripe (>= 1 where it has a tile)
+  const uint32_t* tile0;        // [batch + 1] first tile of each stripe
+  const uint32_t* tile_stripe;  // [ntiles] owning stripe of each tile
+  uint32_t tab_stride;          // bytes between two patterns' tables (a multiple of 256)
+  uint32_t ntiles;
+  uint32_t in_stride;           // pointers per stripe in in_tab: a.K, or 2 * a.K for pairs
+};
+
+// (kOrderUpdate + the TileOrder it runs in, always consecutive: rs_plan_forms of an update plan)
+constexpr int kOrderUpdate = 4096;
+
+// Enqueues the launch group: rs_update_ragged over every mapped stripe's [0, size), the
+// size % 16 tails inside it when any_tail, unaligned 16-B accesses on misaligned shards.
+// Consecutive tile order, sliced like launch_ragged; x.ntiles == 0 enqueues nothing. NOT
+// idempotent: every launch applies the delta again. ev as for launch_apply.
+hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_tail,
+                         hipStream_t stream, LaunchEvents ev = {});
+
 // Tiles per slice of a sliced launch (launch_apply's rule) for `streams` shard streams.
 uint32_t launch_slice_tiles(int streams);
 

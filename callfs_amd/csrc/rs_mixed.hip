@@ -17,6 +17,7 @@
 #include "dispatch.hpp"
 #include "launch_util.hpp"
 #include "rs_apply.hpp"
+#include "rs_update.hpp"
 
 namespace callfs {
 
@@ -268,17 +269,26 @@ static_assert(dev::MixedPolicy<4>::BS == 512 && dev::MixedPolicy<8>::BS == 512 &
 constexpr uint32_t kMixedBlock = 512, kMixedTileVecs = 512;
 static_assert(kRaggedLaunchTileVecs == kMixedTileVecs, "the tile map counts the instances' tiles");
 
+// Update launches (rs_update.hpp): [pair][0: R <= 4, 1: R 5..8, 2: R 9..16]
+using UpdateFn = void (*)(ApplyArgs, UpdateArgs);
+template <int RT, bool PAIR>
+constexpr UpdateFn kUpdateInstance = &dev::rs_update_ragged<RT, dev::UpdatePolicyFor<RT, PAIR>, PAIR>;
+const std::array<std::array<UpdateFn, 3>, 2> kUpdate = {{
+    {kUpdateInstance<4, false>, kUpdateInstance<8, false>, kUpdateInstance<16, false>},
+    {kUpdateInstance<4, true>, kUpdateInstance<8, true>, kUpdateInstance<16, true>}}};
+
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
-// per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one, 2 the required one)
+// per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one, 2 the
+// required one, 3 the single-source update instance, 4 the pair one)
 DeviceOnce g_mixed_wide_lds;
 
 // The vector launch every kind shares: the dynamic-LDS opt-in (`once_key`: 0 the mixed
-// instance, 1 the ragged one, 2 the required one), then `grid` tiles in equal consecutive
-// slices, as launch_apply cuts them. A slice boundary may fall inside a stripe (tiles are
-// numbered over the whole grid).
+// instance, 1 the ragged one, 2 the required one, 3 and 4 the update ones), then `grid` tiles
+// in equal consecutive slices of `streams` shard streams, as launch_apply cuts them. A slice
+// boundary may fall inside a stripe (tiles are numbered over the whole grid).
 template <class X>
 hipError_t launch_tiles(void (*fn)(ApplyArgs, X), int once_key, uint32_t grid, ApplyArgs& a,
-                        const X& x, hipStream_t stream, const LaunchEvents& ev) {
+                        const X& x, int streams, hipStream_t stream, const LaunchEvents& ev) {
   const size_t lds = dev::lds_bytes(a.K, a.R > 8 ? 16 : 8);
   if (lds > (64u << 10)) {
     int device = -1;
@@ -288,7 +298,7 @@ hipError_t launch_tiles(void (*fn)(ApplyArgs, X), int once_key, uint32_t grid, A
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
     });
   }
-  launch_slices(grid, launch_slice_tiles(a.K + a.R), a, [&](uint32_t blocks, bool first, bool last) {
+  launch_slices(grid, launch_slice_tiles(streams), a, [&](uint32_t blocks, bool first, bool last) {
     dispatch(fn, dim3(blocks), dim3(kMixedBlock), lds, stream, ev, first, last, a, x);
   });
   return hipGetLastError();
@@ -315,7 +325,7 @@ hipError_t launch_mixed(ApplyArgs a, const MixedArgs& x, hipStream_t stream, Lau
   const uint64_t ntiles = tps * static_cast<uint64_t>(a.batch);
   if (ntiles > 0x7fffffffull) return hipErrorInvalidValue;
   return launch_tiles(kMixed[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 0, static_cast<uint32_t>(ntiles), a, x,
-                      stream, ev);
+                      a.K + a.R, stream, ev);
 }
 
 hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, const uint32_t* nrows, bool any_tail,
@@ -332,8 +342,25 @@ hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, const uint32_t* nrows
   // with no tail leave lds_tail at once
   a.tail_in_vec = any_tail ? 1u : 0u;
   const int inst = a.R > 8 ? 2 : a.R > 4 ? 1 : 0;
-  return nrows ? launch_tiles(kRaggedSome[inst], 2, x.ntiles, a, RaggedSomeArgs{x, nrows}, stream, ev)
-               : launch_tiles(kRagged[inst], 1, x.ntiles, a, x, stream, ev);
+  return nrows ? launch_tiles(kRaggedSome[inst], 2, x.ntiles, a, RaggedSomeArgs{x, nrows}, a.K + a.R, stream, ev)
+               : launch_tiles(kRagged[inst], 1, x.ntiles, a, x, a.K + a.R, stream, ev);
+}
+
+hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_tail,
+                         hipStream_t stream, LaunchEvents ev) {
+  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
+      !x.pat || !x.nsrc || !x.size || !x.tile0 || !a.in_tab || !a.out_tab ||
+      x.ntiles > 0x7fffffffu || (x.ntiles && !x.tile_stripe) ||
+      x.in_stride != static_cast<uint32_t>(a.K) * (pair ? 2u : 1u))
+    return hipErrorInvalidValue;
+  if (x.ntiles == 0) return hipSuccess;  // no stripe has a changed shard
+  a.t_base = 0;
+  a.S = a.nvec = 0;  // per stripe, read by the kernel
+  a.verify_mask = 0;
+  a.tail_in_vec = any_tail ? 1u : 0u;  // wave 0 of each stripe's first tile
+  // per tile: the sources (twice for pairs), and every row read and written
+  return launch_tiles(kUpdate[pair ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0], pair ? 4 : 3, x.ntiles, a, x,
+                      a.K * (pair ? 2 : 1) + 2 * a.R, stream, ev);
 }
 
 }  // namespace callfs

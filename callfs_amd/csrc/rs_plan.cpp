@@ -11,6 +11,7 @@
 #include "ragged_tables.hpp"
 #include "rs_internal.hpp"
 #include "tune_table.hpp"
+#include "update_tables.hpp"
 
 using namespace callfs;
 
@@ -39,6 +40,23 @@ struct MixedPlan {
   std::vector<Group> groups;  // per launch group of `t`
 };
 
+// An update plan (rs_plan_create_update): where the pieces of
+// update_tables.hpp sit in the plan's device buffer. One tile map, over the stripes with a
+// changed shard, for every launch group; no launch group at all when nothing changed.
+struct UpdatePlan {
+  bool pair = true;  // sources are (old, new) pairs; false: EncodeIdx mode
+  int cmax = 0;
+  size_t in_off = 0, pat_off = 0, nsrc_off = 0, size_off = 0, tile0_off = 0, tile_stripe_off = 0;
+  uint32_t ntiles = 0;
+  bool any_tail = false;
+  struct Group {
+    int R;
+    size_t out_off, arena_off;
+    uint32_t tab_stride;
+  };
+  std::vector<Group> groups;
+};
+
 struct rs_plan {
   int device = 0;
   size_t S = 0;
@@ -57,6 +75,8 @@ struct rs_plan {
   // A mixed or ragged plan (`tables` is null): one kernel form in one tile order,
   // `fixed_form`, for every launch group; nothing to tune, pin or bound by a ceiling.
   std::unique_ptr<MixedPlan> mixed;
+  // An update plan (`tables` and `mixed` are null): `fixed_form` too, and no status to flag.
+  std::unique_ptr<UpdatePlan> update;
   int fixed_form = -1;
 
   bool has_orders() const { return fixed_form < 0; }
@@ -74,6 +94,7 @@ namespace {
 // ---- what differs between uniform, mixed and ragged plans -------------------------------
 
 size_t plan_groups(const rs_plan& plan) {
+  if (plan.update) return plan.update->groups.size();
   return plan.mixed ? plan.mixed->t.groups.size() : plan.tables->groups.size();
 }
 
@@ -118,6 +139,33 @@ ApplyArgs plan_group_args(const rs_plan& plan, size_t gi, RaggedArgs* x = nullpt
 // have tile orders.
 hipError_t plan_launch(const rs_plan& plan, hipStream_t s, const std::vector<int>& orders,
                        LaunchEvents ev) {
+  if (plan.update) {
+    const UpdatePlan& up = *plan.update;
+    auto* d = static_cast<uint8_t*>(plan.dmeta.p);
+    const size_t ng = up.groups.size();
+    for (size_t gi = 0; gi < ng; ++gi) {
+      const UpdatePlan::Group& g = up.groups[gi];
+      ApplyArgs a{};
+      a.in_tab = reinterpret_cast<const uint8_t* const*>(d + up.in_off);
+      a.out_tab = reinterpret_cast<uint8_t* const*>(d + g.out_off);
+      a.ltabs = d + g.arena_off;
+      a.K = up.cmax;
+      a.R = g.R;
+      a.batch = plan.batch;
+      UpdateArgs x{};
+      x.pat = reinterpret_cast<const uint32_t*>(d + up.pat_off);
+      x.nsrc = reinterpret_cast<const uint32_t*>(d + up.nsrc_off);
+      x.size = reinterpret_cast<const uint64_t*>(d + up.size_off);
+      x.tile0 = reinterpret_cast<const uint32_t*>(d + up.tile0_off);
+      x.tile_stripe = reinterpret_cast<const uint32_t*>(d + up.tile_stripe_off);
+      x.tab_stride = g.tab_stride;
+      x.ntiles = up.ntiles;
+      x.in_stride = static_cast<uint32_t>(up.cmax) * (up.pair ? 2u : 1u);
+      const hipError_t e = launch_update(a, x, up.pair, up.any_tail, s, group_events(ev, gi, ng));
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
   if (!plan.mixed)
     return launch_groups(*plan.tables, plan.layout, plan.batch, static_cast<uint8_t*>(plan.dmeta.p),
                          plan.S, s, /*status_stride=*/1, plan.hint, &orders, ev);
@@ -443,6 +491,94 @@ int rs_plan_create_required(rs_ctx* ctx, int device, int k, int m, int batch, co
   if (ragged_sizes_equal(batch, sizes) && required_pairs_equal(n, batch, present, required))
     return create_uniform(ctx, device, k, m, sizes[0], batch, present, required, shards, out);
   return create_tabled(ctx, device, k, m, PlanKind::kRequired, 0, batch, sizes, present, required, shards, out);
+}
+
+int rs_plan_create_update(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                          const uint8_t* changed, const uint8_t* const* old_data,
+                          const uint8_t* const* new_data, uint8_t* const* parity, rs_plan** out) {
+  DeviceGuard dg;
+  // (old_data NULL is EncodeIdx mode, not an error)
+  int rc = check_plan_args(ctx, k, m, batch, sizes && changed && new_data && parity, out);
+  if (rc) return rc;
+  const bool pair = old_data != nullptr;
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < k; ++i)
+      if (changed[static_cast<size_t>(b) * k + i] && sizes[b] == 0) return RS_E_NO_DATA;
+  for (int b = 0; b < batch; ++b) {
+    bool any = false;
+    for (int i = 0; i < k; ++i) {
+      const size_t at = static_cast<size_t>(b) * k + i;
+      if (!changed[at]) continue;
+      any = true;
+      if (!new_data[at] || (pair && !old_data[at])) return RS_E_ARG;
+    }
+    for (int j = 0; any && j < m; ++j)
+      if (!parity[static_cast<size_t>(b) * m + j]) return RS_E_ARG;
+  }
+  if (!ctx->device(device)) return RS_E_ARG;
+  UpdateTables t;
+  if ((rc = table_status(build_update_tables(k, m, batch, sizes, changed, t)))) return rc;
+  size_t smax = 0;
+  for (int b = 0; b < batch; ++b)
+    if (t.has[static_cast<size_t>(b)]) smax = std::max(smax, sizes[b]);
+  auto plan = new_plan(device, smax, batch);
+  plan->update = std::make_unique<UpdatePlan>();
+  UpdatePlan& up = *plan->update;
+  up.pair = pair;
+  up.cmax = t.cmax;
+  up.ntiles = t.map.ntiles;
+  up.any_tail = t.map.any_tail;
+  plan->fixed_form = RS_ORDER_CONSECUTIVE + kOrderUpdate;
+  plan->bytes = pair ? t.bytes_pair : t.bytes_single;
+  const size_t stride = static_cast<size_t>(t.cmax) * (pair ? 2 : 1);
+  Packer pk;
+  plan->status_off = pk.take(sizeof(int) * static_cast<size_t>(batch));
+  up.in_off = pk.take(sizeof(void*) * std::max<size_t>(1, static_cast<size_t>(batch) * stride));
+  up.pat_off = pk.take(sizeof(uint32_t) * static_cast<size_t>(batch));
+  up.nsrc_off = pk.take(sizeof(uint32_t) * std::max<size_t>(1, t.nsrc.size()));
+  up.size_off = pk.take(sizeof(uint64_t) * static_cast<size_t>(batch));
+  up.tile0_off = pk.take(sizeof(uint32_t) * t.map.tile0.size());
+  up.tile_stripe_off = pk.take(sizeof(uint32_t) * std::max<size_t>(1, t.map.tile_stripe.size()));
+  for (const UpdateGroup& g : t.groups)
+    up.groups.push_back({g.R, pk.take(sizeof(void*) * static_cast<size_t>(batch) * g.R),
+                         pk.take(g.arena.size()), static_cast<uint32_t>(g.tab_stride)});
+  std::vector<uint8_t> h(pk.off, 0);
+  auto put = [&](size_t off, const auto& v) {
+    if (!v.empty()) std::memcpy(h.data() + off, v.data(), sizeof(v[0]) * v.size());
+  };
+  // sources of stripe b: its pattern's changed shards in ascending order, (old, new) for pairs;
+  // slots past its source count, and every slot of an unchanged stripe, stay null and unread
+  auto* in = reinterpret_cast<const uint8_t**>(h.data() + up.in_off);
+  for (int b = 0; b < batch; ++b) {
+    if (!t.has[static_cast<size_t>(b)]) continue;
+    const std::vector<int>& idx = t.patterns[t.pat[static_cast<size_t>(b)]];
+    for (size_t c = 0; c < idx.size(); ++c) {
+      const size_t at = static_cast<size_t>(b) * k + idx[c];
+      if (pair) {
+        in[b * stride + 2 * c] = old_data[at];
+        in[b * stride + 2 * c + 1] = new_data[at];
+      } else {
+        in[b * stride + c] = new_data[at];
+      }
+    }
+  }
+  put(up.pat_off, t.pat);
+  put(up.nsrc_off, t.nsrc);
+  put(up.size_off, t.size);
+  put(up.tile0_off, t.map.tile0);
+  put(up.tile_stripe_off, t.map.tile_stripe);
+  for (size_t gi = 0; gi < t.groups.size(); ++gi) {
+    const UpdateGroup& g = t.groups[gi];
+    auto* o = reinterpret_cast<uint8_t**>(h.data() + up.groups[gi].out_off);
+    for (int b = 0; b < batch; ++b)
+      for (int r = 0; r < g.R; ++r)
+        o[static_cast<size_t>(b) * g.R + r] =
+            t.has[static_cast<size_t>(b)] ? parity[static_cast<size_t>(b) * m + g.row0 + r] : nullptr;
+    put(up.groups[gi].arena_off, g.arena);
+  }
+  if ((rc = upload(plan->dmeta, device, h.data(), h.size()))) return rc;
+  *out = plan.release();
+  return RS_OK;
 }
 
 void rs_plan_destroy(rs_plan* plan) {

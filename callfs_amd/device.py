@@ -306,6 +306,38 @@ class Plan:
         dev = rb.device.index if rb.device.index is not None else 0
         return cls.ragged(rb.k, rb.m, rb.sizes, rb.pointers(), present, dev, context, required)
 
+    @classmethod
+    def update(cls, k: int, m: int, sizes: Sequence[int], changed, old_ptrs, new_ptrs,
+               parity_ptrs, device: int = 0, context: Optional[N.Context] = None) -> "Plan":
+        """rs_plan_create_update: upstream Update / EncodeIdx on device
+        memory. changed: batch rows of k flags; old_ptrs / new_ptrs: batch*k device pointers
+        (read where changed; 0 elsewhere is fine), parity_ptrs: batch*m. old_ptrs=None is
+        EncodeIdx mode: the flagged new shards' products are added to the parity. A launch
+        sets parity ^= P[:, changed] * (old ^ new) in place. NOT idempotent: a second launch
+        applies the delta again and restores the parity the first started from."""
+        batch = len(sizes)
+        rows = _mask_rows(changed)
+        if rows is None or len(rows) != batch or any(len(r) != k for r in rows):
+            raise ValueError("changed: batch rows of k flags")
+        if len(new_ptrs) != batch * k or len(parity_ptrs) != batch * m or (
+                old_ptrs is not None and len(old_ptrs) != batch * k):
+            raise ValueError("need batch*k old / new pointers and batch*m parity pointers")
+        self = cls.__new__(cls)
+        self.ctx = context or N.default_context()
+        self.k, self.m, self.S, self.batch, self.device = k, m, None, batch, device
+        self.sizes = [int(s) for s in sizes]
+        self.handle = None
+        flags = (ctypes.c_uint8 * max(1, batch * k))(*[1 if f else 0 for r in rows for f in r])
+        szs = (ctypes.c_size_t * max(1, batch))(*self.sizes)
+        arr = lambda p: (ctypes.c_void_p * max(1, len(p)))(*p)  # noqa: E731
+        h = ctypes.c_void_p()
+        N.check(N.lib.rs_plan_create_update(self.ctx.handle, device, k, m, batch, szs, flags,
+                                            None if old_ptrs is None else arr(old_ptrs),
+                                            arr(new_ptrs), arr(parity_ptrs), ctypes.byref(h)),
+                "rs_plan_create_update")
+        self.handle = h
+        return self
+
     @property
     def bytes(self) -> int:
         """Algorithmic HBM bytes one launch moves."""
@@ -359,7 +391,7 @@ class Plan:
                    166: "realign64-x32", 192: "dma", 194: "dma-g2", 195: "dma-q8",
                    198: "dma-x32", 224: "tridb-g4", 225: "tridb-g8", 256: "bs", 257: "bs-g8",
                    258: "bs-g2", 259: "bs-q8", 260: "bs-q16", 261: "bs-x8", 262: "bs-x32",
-                   512: "mixed", 1024: "ragged", 2048: "required"}
+                   512: "mixed", 1024: "ragged", 2048: "required", 4096: "update"}
 
     def tune(self, reps: int = 5, stream: Optional[torch.cuda.Stream] = None) -> list:
         """rs_plan_tune: time each launch group in every tile order its kernel offers

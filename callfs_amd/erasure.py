@@ -78,6 +78,18 @@ class ErrSingular(ErasureError):
     text = "matrix is singular"
 
 
+class ErrInvalidInput(ErasureError):
+    """upstream Update: a changed shard was given without its old bytes."""
+
+    text = "invalid input"
+
+
+class ErrInvalidShardIdx(ErasureError):
+    """upstream EncodeIdx: the shard index is not a data shard's."""
+
+    text = "invalid shard index"
+
+
 class ErrUnsupportedProfile(ErasureError):
     """k+m > 256: upstream reedsolomon.New switches to Leopard GF(2^16); the GPU codec
     does not implement it and the Go shim keeps the CPU codec for such profiles."""
@@ -342,6 +354,34 @@ class Codec:
         return objects, errors
 
 
+    def overwrite(self, shards: List, profile: ErasureProfile, offset: int, data) -> None:
+        """rs_codec_overwrite: bytes [offset, offset + len(data)) of the object
+        whose shards these are (encode's layout: object byte x in data shard x // S at column
+        x % S) become `data`. Only the affected parity columns are updated (upstream Update on
+        at most three column intervals) and the data shards the range touches are rewritten;
+        afterwards `shards` equal encode() of the overwritten object. The touched data shards
+        and all parity shards must be writable buffers of one size; the others may be None."""
+        k, m = profile.data_shards, profile.parity_shards
+        if k < 1 or m < 1:
+            raise ErrInvalidProfile()
+        if k + m > 256:
+            raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create encoder")
+        if len(shards) != k + m:
+            raise ErrTooFewShards()
+        src = memoryview(data).cast("B")
+        S = next((len(s) for s in shards if s is not None and len(s)), 0)
+        if any(s is not None and len(s) not in (0, S) for s in shards):
+            raise ErrShardSize()
+        if S and len(src) and 0 <= offset and offset + len(src) <= k * S:
+            touched = list(range(offset // S, (offset + len(src) - 1) // S + 1)) + list(range(k, k + m))
+            if not all(shards[i] is not None and _writable(shards[i]) for i in touched):
+                raise TypeError("the touched data shards and the parity shards must be writable")
+        rc = N.lib.rs_codec_overwrite(self.context.handle, k, m, S, _shard_ptrs(shards), int(offset),
+                                      _addr(src) if len(src) else None, len(src))
+        if rc != N.RS_OK:
+            raise _wrapped(rc, "erasure: failed to update parity")
+
+
 # ---- reedsolomon.Encoder-level helpers over host shards -----------------------------
 
 def _shard_ptrs(shards: Sequence) -> ctypes.Array:
@@ -402,6 +442,93 @@ def reconstruct_some(shards: List, k: int, m: int, required: Sequence[bool],
     for i in range(n):
         if (shards[i] is None or len(shards[i]) == 0) and lens[i]:
             shards[i] = bufs[i]
+
+
+def update(shards: List, new_data: Sequence, k: int, m: int,
+           context: Optional[N.Context] = None) -> None:
+    """upstream enc.Update(shards, newDatashards): shards holds the old data shards (only
+    those that changed are read; the others may be None) and the m parity shards, updated in
+    place; new_data has k entries, None = unchanged. The data entries of `shards` are left as
+    they are (upstream: "the data shards will remain the same"). A changed shard without its
+    old bytes raises ErrInvalidInput, as upstream (the native call's RS_E_ARG)."""
+    ctx = context or N.default_context()
+    if len(shards) != k + m:
+        raise ErrTooFewShards()
+    if len(new_data) != k:
+        raise ErrTooFewShards()
+    changed = [i for i in range(k) if new_data[i] is not None and len(new_data[i])]
+    for i in changed:
+        if shards[i] is None or len(shards[i]) == 0:
+            raise ErrInvalidInput()
+    S = next((len(new_data[i]) for i in changed), 0) or next(
+        (len(s) for s in shards if s is not None and len(s)), 0)
+    if any(len(new_data[i]) != S or len(shards[i]) != S for i in changed) or any(
+            s is None or len(s) != S for s in shards[k:]):
+        raise ErrShardSize()
+    if not all(_writable(s) for s in shards[k:]):
+        raise TypeError("parity shards must be writable")
+    old = _shard_ptrs([shards[i] if i in changed else None for i in range(k)])
+    rc = N.lib.rs_update(ctx.handle, k, m, S, old, _shard_ptrs(list(new_data)), _shard_ptrs(shards[k:]))
+    if rc != N.RS_OK:
+        raise _wrapped(rc, "update")
+
+
+def encode_idx(shard, idx: int, parity: List, k: int, m: int,
+               context: Optional[N.Context] = None) -> None:
+    """upstream enc.EncodeIdx(dataShard, idx, parity): adds data shard idx's contribution to
+    the m parity shards in place. Zero the parity before the first shard; the k shards may
+    then arrive in any order."""
+    ctx = context or N.default_context()
+    if not 0 <= idx < k:
+        raise ErrInvalidShardIdx()
+    if len(parity) != m:
+        raise ErrTooFewShards()
+    S = len(shard)
+    if any(p is None or len(p) != S for p in parity):
+        raise ErrShardSize()
+    if not all(_writable(p) for p in parity):
+        raise TypeError("parity shards must be writable")
+    rc = N.lib.rs_encode_idx(ctx.handle, k, m, S, _addr(shard) if S else None, idx, _shard_ptrs(parity))
+    if rc != N.RS_OK:
+        raise _wrapped(rc, "encode_idx")
+
+
+def update_batch(old_data: Optional[Sequence[Sequence]], new_data: Sequence[Sequence],
+                 parity: Sequence[Sequence], k: int, m: int,
+                 context: Optional[N.Context] = None) -> List[int]:
+    """rs_update_batch: stripe b has new_data[b] (k entries, None or empty = unchanged), old_data[b] (k
+    entries, read where changed) and parity[b] (m writable shards, updated in place). Stripes
+    may differ in shard size and in what changed. old_data=None is EncodeIdx mode for the
+    whole batch. Returns status[b] (RS_OK, RS_E_NO_DATA, RS_E_ARG)."""
+    ctx = context or N.default_context()
+    B = len(new_data)
+    if len(parity) != B or (old_data is not None and len(old_data) != B):
+        raise ValueError("one row of old / new / parity shards per stripe")
+    sizes = (ctypes.c_size_t * max(B, 1))()
+    for b in range(B):
+        if len(new_data[b]) != k or len(parity[b]) != m or (old_data is not None and len(old_data[b]) != k):
+            raise ErrTooFewShards()
+        ref = [s for s in parity[b] if s is not None]
+        S = len(ref[0]) if ref else 0
+        rows = list(parity[b]) + [s for s in new_data[b] if s is not None]
+        if old_data is not None:
+            rows += [old_data[b][i] for i in range(k) if new_data[b][i] is not None and old_data[b][i] is not None]
+        if any(s is not None and len(s) != S for s in rows):
+            raise ErrShardSize()
+        if not all(s is None or _writable(s) for s in parity[b]):
+            raise TypeError("parity shards must be writable")
+        sizes[b] = S
+    def ptrs(rows):
+        return _shard_ptrs([s for row in rows for s in row] or [None])
+
+    status = (ctypes.c_int * max(B, 1))()
+    rc = N.lib.rs_update_batch(ctx.handle, k, m, B, sizes,
+                               None if old_data is None else ptrs(old_data), ptrs(new_data),
+                               ptrs(parity), status)
+    out = list(status)[:B]
+    if rc != N.RS_OK and rc not in out:
+        N.check(rc, "rs_update_batch")
+    return out
 
 
 def verify(shards: List, k: int, m: int, context: Optional[N.Context] = None) -> bool:

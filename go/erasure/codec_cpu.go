@@ -98,3 +98,40 @@ func FreeHostBuffer(b []byte) {}
 func (c *Codec) DecodePinned(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, error) {
 	return c.cpuDecode(shards, profile, originalSize)
 }
+
+// UpdateParity is upstream enc.Update(shards, newData) on builds without the GPU codec: the m
+// parity entries of shards are updated in place from the old (shards) and new (newData, nil =
+// unchanged) bytes of the changed data shards.
+func (c *Codec) UpdateParity(shards, newData [][]byte, profile ErasureProfile) error {
+	if profile.DataShards < 1 || profile.ParityShards < 1 {
+		return ErrInvalidProfile
+	}
+	return cpuUpdateParity(shards, newData, profile.DataShards, profile.ParityShards)
+}
+
+// EncodeIdx is upstream enc.EncodeIdx(dataShard, idx, parity) on builds without the GPU codec.
+func (c *Codec) EncodeIdx(dataShard []byte, idx int, parity [][]byte, profile ErasureProfile) error {
+	if profile.DataShards < 1 || profile.ParityShards < 1 {
+		return ErrInvalidProfile
+	}
+	return cpuEncodeIdx(dataShard, idx, parity, profile.DataShards, profile.ParityShards)
+}
+
+// UpdateBatch is UpdateParity per stripe on builds without the GPU codec.
+func (c *Codec) UpdateBatch(shards, newData [][][]byte, profile ErasureProfile) []error {
+	errs := make([]error, len(shards))
+	for b := range shards {
+		if len(newData) != len(shards) {
+			errs[b] = fmt.Errorf("erasure: %d new-data rows for %d stripes", len(newData), len(shards))
+			continue
+		}
+		errs[b] = c.UpdateParity(shards[b], newData[b], profile)
+	}
+	return errs
+}
+
+// Overwrite replaces object bytes [offset, offset+len(data)) in the data shards and updates
+// the affected parity columns with upstream Update, on builds without the GPU codec.
+func (c *Codec) Overwrite(shards [][]byte, profile ErasureProfile, offset int64, data []byte) error {
+	return cpuOverwrite(shards, profile.DataShards, profile.ParityShards, offset, data)
+}

@@ -715,3 +715,239 @@ func cpuRepair(shards [][]byte, k, m int) error {
 	}
 	return nil
 }
+
+// ---- parity updated in place (upstream Update / EncodeIdx; DESIGN.md §5.11) -------------
+
+// updateErr maps the codes of the update calls: the erasure sentinels by identity, anything
+// upstream Update would have reported inside Encode's wrapper.
+func updateErr(rc C.int) error {
+	switch rc {
+	case C.RS_OK:
+		return nil
+	case C.RS_E_INVALID_PROFILE:
+		return ErrInvalidProfile
+	case C.RS_E_ARG:
+		return fmt.Errorf("erasure: failed to update parity: %w", reedsolomon.ErrInvalidInput)
+	}
+	return fmt.Errorf("erasure: failed to update parity: %w", upstreamErr(rc))
+}
+
+// checkUpdate is upstream Update's argument check, in its order: the shard counts, a changed
+// shard without its old bytes (ErrInvalidInput), then the sizes. Returns the shard size.
+func checkUpdate(shards, newData [][]byte, k, m int) (int, error) {
+	wrap := func(err error) error { return fmt.Errorf("erasure: failed to update parity: %w", err) }
+	if len(shards) != k+m || len(newData) != k {
+		return 0, wrap(reedsolomon.ErrTooFewShards)
+	}
+	S := 0
+	for i, nd := range newData {
+		if nd != nil && shards[i] == nil {
+			return 0, wrap(reedsolomon.ErrInvalidInput)
+		}
+	}
+	for _, s := range shards {
+		if len(s) > 0 {
+			S = len(s)
+			break
+		}
+	}
+	if S == 0 {
+		return 0, wrap(reedsolomon.ErrShardNoData)
+	}
+	for i, s := range shards {
+		if (i >= k || newData[i] != nil) && len(s) != S {
+			return 0, wrap(reedsolomon.ErrShardSize)
+		}
+	}
+	for _, nd := range newData {
+		if nd != nil && len(nd) != S {
+			return 0, wrap(reedsolomon.ErrShardSize)
+		}
+	}
+	return S, nil
+}
+
+// UpdateParity is upstream enc.Update(shards, newData) (rs_update): shards holds the old data
+// shards -- only those that changed are read, the others may be nil -- and the m parity
+// shards, which are updated in place; newData has k entries, nil = unchanged. The data entries
+// of shards stay as they are. An update of c shards moves (2c+2m)*S bytes where a full Encode
+// moves (k+m)*S and needs all k data shards. Not in the reference API.
+func (c *Codec) UpdateParity(shards, newData [][]byte, profile ErasureProfile) error {
+	k, m := profile.DataShards, profile.ParityShards
+	if k < 1 || m < 1 {
+		return ErrInvalidProfile
+	}
+	if k+m > 256 || device() == nil {
+		return cpuUpdateParity(shards, newData, k, m)
+	}
+	S, err := checkUpdate(shards, newData, k, m)
+	if err != nil {
+		return err
+	}
+	olds, news, par := newCArray(k), newCArray(k), newCArray(m)
+	defer olds.free()
+	defer news.free()
+	defer par.free()
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for i, nd := range newData {
+		if nd == nil {
+			continue
+		}
+		pin.Pin(&nd[0])
+		pin.Pin(&shards[i][0])
+		news.set(i, unsafe.Pointer(&nd[0]))
+		olds.set(i, unsafe.Pointer(&shards[i][0]))
+	}
+	for j := 0; j < m; j++ {
+		pin.Pin(&shards[k+j][0])
+		par.set(j, unsafe.Pointer(&shards[k+j][0]))
+	}
+	return updateErr(C.rs_update(gpuCtx, C.int(k), C.int(m), C.size_t(S), olds.at(0), news.at(0), par.at(0)))
+}
+
+// EncodeIdx is upstream enc.EncodeIdx(dataShard, idx, parity) (rs_encode_idx): it adds data
+// shard idx's contribution to the m parity shards in place. Zero the parity before the first
+// shard; the k shards may then arrive in any order. Not in the reference API.
+func (c *Codec) EncodeIdx(dataShard []byte, idx int, parity [][]byte, profile ErasureProfile) error {
+	k, m := profile.DataShards, profile.ParityShards
+	if k < 1 || m < 1 {
+		return ErrInvalidProfile
+	}
+	if k+m > 256 || device() == nil {
+		return cpuEncodeIdx(dataShard, idx, parity, k, m)
+	}
+	wrap := func(err error) error { return fmt.Errorf("erasure: failed to update parity: %w", err) }
+	// upstream's order: the parity count, the index, then the sizes
+	if len(parity) != m {
+		return wrap(reedsolomon.ErrTooFewShards)
+	}
+	if idx < 0 || idx >= k {
+		return wrap(reedsolomon.ErrInvalidShardIdx)
+	}
+	if len(dataShard) == 0 {
+		return wrap(reedsolomon.ErrShardNoData)
+	}
+	par := newCArray(m)
+	defer par.free()
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for j, p := range parity {
+		if len(p) != len(dataShard) {
+			return wrap(reedsolomon.ErrShardSize)
+		}
+		pin.Pin(&p[0])
+		par.set(j, unsafe.Pointer(&p[0]))
+	}
+	pin.Pin(&dataShard[0])
+	return updateErr(C.rs_encode_idx(gpuCtx, C.int(k), C.int(m), C.size_t(len(dataShard)),
+		(*C.uint8_t)(unsafe.Pointer(&dataShard[0])), C.int(idx), par.at(0)))
+}
+
+// UpdateBatch is UpdateParity for many stripes of one profile in one call (rs_update_batch:
+// one pipeline over all of them, whatever their sizes and changed sets). shards[b] and
+// newData[b] are stripe b's arguments to UpdateParity; errs[b] is what it would report.
+func (c *Codec) UpdateBatch(shards, newData [][][]byte, profile ErasureProfile) []error {
+	k, m := profile.DataShards, profile.ParityShards
+	errs := make([]error, len(shards))
+	if len(newData) != len(shards) {
+		for b := range errs {
+			errs[b] = fmt.Errorf("erasure: %d new-data rows for %d stripes", len(newData), len(shards))
+		}
+		return errs
+	}
+	if k < 1 || m < 1 {
+		for b := range errs {
+			errs[b] = ErrInvalidProfile
+		}
+		return errs
+	}
+	if len(shards) == 0 {
+		return errs
+	}
+	if k+m > 256 || device() == nil {
+		for b := range shards {
+			errs[b] = cpuUpdateParity(shards[b], newData[b], k, m)
+		}
+		return errs
+	}
+	B := len(shards)
+	olds, news, par := newCArray(B*k), newCArray(B*k), newCArray(B*m)
+	defer olds.free()
+	defer news.free()
+	defer par.free()
+	sizes := make([]C.size_t, B)
+	status := make([]C.int, B)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for b := range shards {
+		S, err := checkUpdate(shards[b], newData[b], k, m)
+		if err != nil {
+			errs[b] = err
+			continue // no pointers: the stripe has no change for the library
+		}
+		sizes[b] = C.size_t(S)
+		for i, nd := range newData[b] {
+			if nd == nil {
+				continue
+			}
+			pin.Pin(&nd[0])
+			pin.Pin(&shards[b][i][0])
+			news.set(b*k+i, unsafe.Pointer(&nd[0]))
+			olds.set(b*k+i, unsafe.Pointer(&shards[b][i][0]))
+		}
+		for j := 0; j < m; j++ {
+			pin.Pin(&shards[b][k+j][0])
+			par.set(b*m+j, unsafe.Pointer(&shards[b][k+j][0]))
+		}
+	}
+	rc := C.rs_update_batch(gpuCtx, C.int(k), C.int(m), C.int(B), &sizes[0], olds.at(0), news.at(0),
+		par.at(0), &status[0])
+	if rc != C.RS_OK && !hasStatus(status, rc) { // a call-level error: no status was written
+		for b := range errs {
+			if errs[b] == nil {
+				errs[b] = updateErr(rc)
+			}
+		}
+		return errs
+	}
+	for b := range errs {
+		if errs[b] == nil {
+			errs[b] = updateErr(status[b])
+		}
+	}
+	return errs
+}
+
+// Overwrite replaces bytes [offset, offset+len(data)) of the object whose n shards these are
+// (Encode's layout: object byte x in data shard x/S at column x%S) and brings the parity up to
+// date (rs_codec_overwrite): only the affected parity columns are read and rewritten, through
+// one update batch of at most three column intervals, then data is copied into the data
+// shards. Afterwards shards equal Encode of the overwritten object. The data shards the range
+// does not touch may be nil. Not in the reference API.
+func (c *Codec) Overwrite(shards [][]byte, profile ErasureProfile, offset int64, data []byte) error {
+	k, m := profile.DataShards, profile.ParityShards
+	if k < 1 || m < 1 {
+		return ErrInvalidProfile
+	}
+	if k+m > 256 || device() == nil {
+		return cpuOverwrite(shards, k, m, offset, data)
+	}
+	S, err := checkOverwrite(shards, k, m, offset, data)
+	if err != nil {
+		return err
+	}
+	ptrs := newCArray(k + m)
+	defer ptrs.free()
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for i, s := range shards {
+		if len(s) == S {
+			pin.Pin(&s[0])
+			ptrs.set(i, unsafe.Pointer(&s[0]))
+		}
+	}
+	pin.Pin(&data[0])
+	return updateErr(C.rs_codec_overwrite(gpuCtx, C.int(k), C.int(m), C.size_t(S), ptrs.at(0),
+		C.int64_t(offset), (*C.uint8_t)(unsafe.Pointer(&data[0])), C.size_t(len(data))))
+}

@@ -221,6 +221,46 @@ int rs_codec_decode_data_batch(rs_ctx* ctx, int k, int m, int batch,
                                uint8_t* const* shards, size_t* lens,
                                uint8_t* const* out, const int64_t* original_sizes, int* status);
 
+/* ---- Parity updated in place, host memory -------------------------
+ * Upstream Update(shards, newDatashards) and EncodeIdx(dataShard, idx, parity): the parity is
+ * read, changed and written back; no unchanged data shard is read, and data shards are never
+ * written ("the data shards will remain the same").
+ * rs_update: new_data[i] == NULL means data shard i is unchanged; for every other i,
+ *   parity[j] ^= P[j][i] * (old_data[i] ^ new_data[i]) over S bytes, after which the parity is
+ *   what rs_encode of the new data gives. A changed shard whose old_data entry is NULL is
+ *   RS_E_ARG (upstream ErrInvalidInput), S == 0 with a change RS_E_NO_DATA. Nothing changed:
+ *   RS_OK with no device work and no counter moved.
+ * rs_encode_idx: parity[j] ^= P[j][idx] * shard, added to whatever the parity holds
+ *   (upstream has the caller zero it before the first shard); the k shards of a stripe may
+ *   arrive in any order. idx outside [0, k) is RS_E_ARG (upstream ErrInvalidShardIdx).
+ * rs_update_batch: stripe b has sizes[b]-byte shards, old_data / new_data[b*k + i] and
+ *   parity[b*m + j], each stripe as rs_update; old_data == NULL (the array) is EncodeIdx mode
+ *   for the whole batch (every non-NULL new_data entry is added). status[b] is RS_OK,
+ *   RS_E_NO_DATA or RS_E_ARG (a changed shard without old bytes, a NULL parity pointer); the
+ *   return value follows rs_encode_batch's rule. No parity byte of one stripe may overlap a
+ *   parity byte of another stripe or any source.
+ * rs_codec_overwrite: `shards` are the n = k+m S-byte shards of an object laid out as
+ *   rs_codec_encode lays it (object byte x in data shard x / S at column x % S). Bytes
+ *   [offset, offset + len) of the object become `data`: the affected parity columns are
+ *   updated through one rs_update_batch of at most three stripes (disjoint column intervals,
+ *   each with its own changed shards), then `data` is copied into the data shards. Afterwards
+ *   the shards equal rs_codec_encode of the overwritten object bit for bit, and no column
+ *   outside the range is touched in any shard. Every data shard the range touches and all m
+ *   parity shards must be non-NULL (RS_E_ARG), as must data; a range past k*S, offset < 0 or
+ *   len == 0 is RS_E_ARG. `data` must not overlap the shards.
+ * All four take the staged ragged pipeline (a chunk: one H2D of the changed sources and the
+ * parity rows, one launch per group of 16 parity rows, one D2H of the parity rows), whatever
+ * memory the buffers are in, on one device; rs_host_counters counts them like the other calls. */
+int rs_update(rs_ctx* ctx, int k, int m, size_t S, const uint8_t* const* old_data,
+              const uint8_t* const* new_data, uint8_t* const* parity);
+int rs_encode_idx(rs_ctx* ctx, int k, int m, size_t S, const uint8_t* shard, int idx,
+                  uint8_t* const* parity);
+int rs_update_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes,
+                    const uint8_t* const* old_data, const uint8_t* const* new_data,
+                    uint8_t* const* parity, int* status);
+int rs_codec_overwrite(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* shards,
+                       int64_t offset, const uint8_t* data, size_t len);
+
 /* ---- counters of the host-memory path -----------------------------------------------
  * Monotonic per-context counts (relaxed atomics; what an operator graphs, and what shows
  * that a batch cost one round trip):
@@ -442,6 +482,42 @@ int rs_plan_create_required(rs_ctx* ctx, int device, int k, int m, int batch, co
 int rs_decode_dev_required(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
                            const uint8_t* present, const uint8_t* required,
                            uint8_t* const* shards, void* stream);
+
+/* ---- update plans: parity updated in place -------------------------
+ * Upstream Update(shards, newDatashards) and EncodeIdx(dataShard, idx, parity) for
+ * device-resident batches. Stripe b has sizes[b]-byte shards and k flags at changed + b*k
+ * (nonzero = data shard i changed). A launch sets, for every stripe with a changed shard,
+ *     parity[b*m + j] ^= sum over the changed i of P[j][i] * (old_data[b*k+i] ^ new_data[b*k+i])
+ * (P the parity rows of rs_encode_matrix), reading nothing but the old and new bytes of the
+ * changed shards and the parity itself: after one launch the parity is what an encode of the
+ * new data gives. old_data == NULL (the whole array) is EncodeIdx mode: the launch adds
+ * P[j][i] * new_data[b*k+i] for every flagged i to whatever the parity holds (upstream has
+ * the caller zero it before the first shard arrives). Entries of unflagged shards are never
+ * read and may be NULL, as may every pointer of a stripe with no flag; data shards are never
+ * written.
+ * A LAUNCH IS NOT IDEMPOTENT: it applies the delta to the parity's current bytes. A second
+ * launch applies it again, which restores the parity the first launch started from.
+ * The caller's contract: no parity byte of one stripe may overlap a parity byte of another
+ * stripe or any source.
+ * It is an ordinary plan: rs_plan_launch / _launch_timed only enqueue (no allocation, no
+ * sync; graph-capturable), one launch per group of 16 parity rows, none when no stripe has a
+ * flag; _groups, _destroy as for any plan, and
+ *   rs_plan_bytes   returns the sum over the stripes with c_b > 0 flags of
+ *                   sizes[b] * (c_b * (2, or 1 in EncodeIdx mode) + 2m);
+ *   rs_plan_forms   reports RS_ORDER_UPDATE + RS_ORDER_CONSECUTIVE;
+ *   rs_plan_status  reports 0 (nothing is compared);
+ *   rs_plan_tune    times nothing (it never touches the parity) and fills -1,
+ *                   rs_plan_set_orders accepts only -1, and the ceiling launches return
+ *                   RS_E_ARG; no bit-sliced kernel, no hiprtc compile, no tune-table entry.
+ * Errors, in this order: the profile (RS_E_INVALID_PROFILE, RS_E_UNSUPPORTED); a NULL
+ * sizes, changed, new_data, parity or out, or batch < 1 (RS_E_ARG); sizes[b] == 0 on a stripe
+ * with a flag (RS_E_NO_DATA); a flag whose new_data entry (or, with old_data, whose old_data
+ * entry) is NULL, or a NULL parity entry of such a stripe (RS_E_ARG). Nothing is created on
+ * an error. */
+#define RS_ORDER_UPDATE 4096
+int rs_plan_create_update(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                          const uint8_t* changed, const uint8_t* const* old_data,
+                          const uint8_t* const* new_data, uint8_t* const* parity, rs_plan** out);
 
 /* ---- ShardChecksum on device-resident shards (codec.go:81-84; §8(f) of SURVEY.md) ----
  * SHA-256 of `count` messages already in HBM, one digest per message written to

@@ -478,6 +478,17 @@ rm -f $O/libcallfs_rs_copy.so
 exit $rc
 }
 
+# Update plans against the full encode of the same batch (tools/update_bench.py, DESIGN.md
+# §5.11): RS(10,4) and RS(32,4), 256 stripes of 1 MiB, 1 and k/2 changed shards per stripe. One
+# JSON line per (shape, changed count) on stdout and in <out dir>/update_bench.jsonl (the lines
+# kept in profiles/r12/update/). Usage: bash tools/jobs.sh update_bench <out dir> [update_bench.py args]
+job_update_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+O=${1:-update_out}; mkdir -p "$O" || exit $?
+shift
+timeout -k 10 400 python3 -u tools/update_bench.py "$@" | tee $O/update_bench.jsonl || exit $?
+}
+
 # configs[1]/[2] shape in the layouts upstream produces: bench.py at S = 6,710,887 with the
 # io.ReadAll Split layout (decode into fresh buffers, as Reconstruct allocates them, and in
 # place) and the planar layout; plus the bench shape. Usage: bash tools/jobs.sh readall_bench <tag>
