@@ -22,6 +22,9 @@ from .erasure import (  # noqa: F401
     decode_rows,
     encode_matrix,
     encode_shards,
+    heal_batch,
+    locate,
+    locate_batch,
     reconstruct,
     reconstruct_some,
     shard_checksum,
@@ -34,5 +37,6 @@ __all__ = [
     "ErrShardCorrupted", "ErrShardNotFound", "ErrShortData", "ErrTooFewShards",
     "ErrShardNoData", "ErrShardSize", "ErrSingular", "ErrUnsupportedProfile",
     "decode_rows", "encode_matrix", "encode_shards", "reconstruct", "reconstruct_some", "verify",
+    "locate", "locate_batch", "heal_batch",
     "shard_checksum", "shard_layout",
 ]

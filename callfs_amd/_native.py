@@ -121,6 +121,17 @@ SIGNATURES = {
     "rs_plan_create_update": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                      ctypes.POINTER(_vp)]),
+    "rs_plan_create_locate": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
+                                     ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rs_plan_blame": (_int, [_vp, _vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "rs_locate": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+                         ctypes.POINTER(ctypes.c_uint64)]),
+    "rs_locate_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_int)]),
+    "rs_heal_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _u8p,
+                             ctypes.POINTER(_int)]),
+    "rs_codec_decode_heal": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _vp,
+                                    _i64, _u8p]),
     "rs_update": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                          ctypes.POINTER(_vp)]),
     "rs_encode_idx": (_int, [_vp, _int, _int, _sz, _vp, _int, ctypes.POINTER(_vp)]),

@@ -8,8 +8,10 @@
 // sizes or erasures through host_ragged.hpp; what a call admits, how a batch is routed and
 // Split's shape are the HIP-free host_path.hpp and codec_batch.hpp. Every reconstruct, with a
 // wanted set (ReconstructSome / ReconstructData) or without, is admitted into the same kShard*
-// flag rows and takes the same path from there.
+// flag rows and takes the same path from there. Locate (which shard is corrupt, DESIGN.md
+// §5.12) runs through host_locate.hpp, and the heal calls compose it with the reconstructs.
 #include "codec_batch.hpp"
+#include "host_locate.hpp"
 #include "host_ragged.hpp"
 #include "host_uniform.hpp"
 #include "host_update.hpp"
@@ -249,6 +251,98 @@ int codec_decode(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens
   return RS_OK;
 }
 
+// Shared by rs_locate, rs_locate_batch and the heal calls: admission as a reconstruct with
+// verify that wants nothing (so a stripe of exactly k present shards is RS_OK with zero counts
+// and no device work), then the locate pipeline over the stripes with a compared shard.
+// counts: batch * (k + m + 1), written for every stripe; status[b] = RS_E_CORRUPT where a
+// syndrome of stripe b was nonzero.
+int locate_batch_host(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* shards,
+                      const size_t* lens, uint64_t* counts, int* status) {
+  const size_t n = static_cast<size_t>(k + m), B = static_cast<size_t>(batch);
+  std::fill(counts, counts + B * (n + 1), 0);
+  std::vector<uint8_t> present(B * n, 0), none(n, 0), row(n, 0);
+  std::vector<size_t> S(B, 0);
+  std::vector<int> ids;
+  for (size_t b = 0; b < B; ++b) {
+    const StripeAdmission a = admit_stripe(k + m, k, shards + b * n, lens + b * n, none.data(), true, row.data());
+    status[b] = a.status;
+    if (!a.run) continue;
+    S[b] = a.S;
+    for (size_t i = 0; i < n; ++i) present[b * n + i] = row[i] == kShardPresent;
+    ids.push_back(static_cast<int>(b));
+  }
+  std::vector<int> flags(B, 0);
+  const int rc = run_locate(ctx, k, m, ids, S.data(), present.data(),
+                            [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; }, counts,
+                            flags.data());
+  if (rc) return rc;
+  for (size_t b = 0; b < B; ++b)
+    if (flags[b]) status[b] = RS_E_CORRUPT;
+  return RS_OK;
+}
+
+// rs_heal_batch's body (and, for one stripe, rs_codec_decode_heal's): reconstruct + verify;
+// the corrupt stripes are located over their original presence; where every mismatching column
+// is explained by a set B of shards and a compared row is left without them, B and the
+// originally missing shards (rebuilt from corrupt inputs the first time) are rebuilt and the
+// rest verified again. Present shards outside B are never written.
+int heal_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards, size_t* lens,
+                    uint8_t* healed, int* status) {
+  const size_t n = static_cast<size_t>(k + m), B = static_cast<size_t>(batch);
+  std::fill(healed, healed + B * n, 0);
+  const std::vector<size_t> lens0(lens, lens + B * n);
+  int rc = reconstruct_batch_host(ctx, k, m, batch, shards, lens, true, nullptr, nullptr, status);
+  if (rc != RS_OK && rc != first_error(status, batch)) return rc;  // call-level
+  std::vector<int> bad;
+  for (size_t b = 0; b < B; ++b)
+    if (status[b] == RS_E_CORRUPT) bad.push_back(static_cast<int>(b));
+  if (bad.empty()) return rc;
+  // (b) locate, over the original presence
+  const size_t nb = bad.size();
+  std::vector<const uint8_t*> sh1(nb * n);
+  std::vector<size_t> ln1(nb * n);
+  for (size_t j = 0; j < nb; ++j)
+    for (size_t i = 0; i < n; ++i) {
+      sh1[j * n + i] = shards[static_cast<size_t>(bad[j]) * n + i];
+      ln1[j * n + i] = lens0[static_cast<size_t>(bad[j]) * n + i];
+    }
+  std::vector<uint64_t> counts(nb * (n + 1));
+  std::vector<int> st1(nb, RS_OK);
+  if ((rc = locate_batch_host(ctx, k, m, static_cast<int>(nb), sh1.data(), ln1.data(), counts.data(), st1.data())))
+    return rc;
+  // (c) the stripes whose blamed set leaves a row to confirm with
+  std::vector<int> cand;  // indices into bad
+  std::vector<uint8_t*> sh2;
+  std::vector<size_t> ln2;
+  for (size_t j = 0; j < nb; ++j) {
+    const uint64_t* c = &counts[j * (n + 1)];
+    size_t blamed = 0, np = 0;
+    for (size_t i = 0; i < n; ++i) {
+      blamed += c[i] != 0;
+      np += ln1[j * n + i] != 0;
+    }
+    if (c[n] != 0 || blamed == 0 || np - blamed < static_cast<size_t>(k) + 1) continue;
+    cand.push_back(static_cast<int>(j));
+    for (size_t i = 0; i < n; ++i) {
+      sh2.push_back(shards[static_cast<size_t>(bad[j]) * n + i]);
+      ln2.push_back(c[i] != 0 ? 0 : ln1[j * n + i]);
+    }
+  }
+  if (!cand.empty()) {
+    std::vector<int> st2(cand.size(), RS_OK);
+    rc = reconstruct_batch_host(ctx, k, m, static_cast<int>(cand.size()), sh2.data(), ln2.data(), true,
+                                nullptr, nullptr, st2.data());
+    if (rc != RS_OK && rc != first_error(st2.data(), static_cast<int>(cand.size()))) return rc;
+    for (size_t q = 0; q < cand.size(); ++q) {
+      if (st2[q] != RS_OK) continue;
+      const size_t j = static_cast<size_t>(cand[q]), b = static_cast<size_t>(bad[j]);
+      status[b] = RS_OK;
+      for (size_t i = 0; i < n; ++i) healed[b * n + i] = counts[j * (n + 1) + i] != 0;
+    }
+  }
+  return first_error(status, batch);
+}
+
 }  // namespace
 
 // ---- exported: per-object calls ---------------------------------------------------------
@@ -342,6 +436,68 @@ int rs_codec_decode(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* l
 int rs_codec_decode_data(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
                          uint8_t* out, int64_t original_size) {
   return codec_decode(ctx, k, m, shards, lens, out, original_size, true);
+}
+
+// ---- exported: locate and heal ----------------------------------------
+
+int rs_locate_batch(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* shards,
+                    const size_t* lens, uint64_t* counts, int* status) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!shards || !lens || !counts || !status))) return RS_E_ARG;
+  if ((rc = locate_batch_host(ctx, k, m, batch, shards, lens, counts, status))) return rc;
+  return first_error(status, batch);
+}
+
+int rs_locate(rs_ctx* ctx, int k, int m, const uint8_t* const* shards, const size_t* lens,
+              uint64_t* counts) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shards || !lens || !counts) return RS_E_ARG;
+  int status = RS_OK;
+  if ((rc = locate_batch_host(ctx, k, m, 1, shards, lens, counts, &status))) return rc;
+  return status;
+}
+
+int rs_heal_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards, size_t* lens,
+                  uint8_t* healed, int* status) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!shards || !lens || !healed || !status))) return RS_E_ARG;
+  if (batch == 0) return RS_OK;
+  return heal_batch_host(ctx, k, m, batch, shards, lens, healed, status);
+}
+
+int rs_codec_decode_heal(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                         uint8_t* out, int64_t original_size, uint8_t* healed) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shards || !lens || !healed || original_size < 0 || (original_size && !out)) return RS_E_ARG;
+  const size_t n = static_cast<size_t>(k + m);
+  std::fill(healed, healed + n, 0);
+  const std::vector<size_t> lens0(lens, lens + n);
+  rc = codec_decode(ctx, k, m, shards, lens, out, original_size, false);
+  if (rc != RS_E_CORRUPT) return rc;
+  // Verify failed: heal from the original presence, then join as rs_codec_decode does
+  std::copy(lens0.begin(), lens0.end(), lens);
+  int status = RS_OK;
+  rc = heal_batch_host(ctx, k, m, 1, shards, lens, healed, &status);
+  if (rc) return rc;
+  const size_t S = lens[0];
+  if (static_cast<uint64_t>(S) * k < static_cast<uint64_t>(original_size)) return RS_E_INSUFFICIENT;
+  size_t left = static_cast<size_t>(original_size);
+  std::vector<CopyPool::Seg> segs;
+  for (int i = 0; i < k && left; ++i) {
+    const size_t c = std::min(S, left);
+    segs.push_back({out + S * i, shards[i], c});
+    left -= c;
+  }
+  ctx->pool.run(segs);
+  return RS_OK;
 }
 
 // ---- exported: batched host-memory calls ------------------------------------------------

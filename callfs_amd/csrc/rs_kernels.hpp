@@ -291,6 +291,33 @@ constexpr int kOrderUpdate = 4096;
 hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_tail,
                          hipStream_t stream, LaunchEvents ev = {});
 
+// ---- locate launches (rs_mixed.hip) --------------------------------------
+// A required launch group in which every row is compared and none written, and a mismatching
+// byte column is classified instead of only flagged: locate_classify (locate_tables.hpp) turns
+// its a.R' syndromes into the shard to blame or "unexplained", and the kernel adds the columns
+// per verdict into counts[stripe * nbins + shard] (unexplained: bin nbins - 1). r, nrows and
+// out_tab as in RaggedSomeArgs; the status words are ORed as in every compare. Sums are formed
+// per wave and only nonzero ones reach memory, as 64-bit atomic adds; no shard byte is written.
+struct LocateArgs {
+  RaggedArgs r;
+  const uint32_t* nrows;  // [P] compared rows r' of each pattern, 1..a.R for a mapped stripe
+  const uint8_t* gf;      // log[256], exp[512]
+  const uint8_t* loc;     // [P] pattern blocks of loc_stride bytes (locate_tables.hpp kLoc*)
+  uint64_t* counts;       // [batch][nbins]
+  uint32_t loc_stride;
+  uint32_t nbins;         // k + m + 1
+};
+
+// (kOrderLocate + the TileOrder it runs in, always consecutive: rs_plan_forms of a locate plan)
+constexpr int kOrderLocate = 8192;
+
+// Enqueues the launch group: rs_apply_locate over every mapped stripe's [0, size), tails and
+// misaligned shards as launch_ragged. Consecutive tile order, sliced like launch_ragged;
+// x.r.ntiles == 0 enqueues nothing. Counts accumulate from launch to launch. ev as for
+// launch_apply.
+hipError_t launch_locate(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
+                         LaunchEvents ev = {});
+
 // Tiles per slice of a sliced launch (launch_apply's rule) for `streams` shard streams.
 uint32_t launch_slice_tiles(int streams);
 

@@ -8,7 +8,9 @@
 // Ragged launches run the same block body with the stripe, its tile and
 // its shard size read per block from a tile map: one launch group over stripes of
 // different shard sizes. Required launches (§5.10) are ragged launches that also read each
-// pattern's row count; one host function, launch_ragged, enqueues both.
+// pattern's row count; one host function, launch_ragged, enqueues both. Locate launches
+// (§5.12) are required launches that compare every row and classify the mismatching byte
+// columns into per-stripe, per-shard counts.
 #include <algorithm>
 #include <array>
 
@@ -16,6 +18,7 @@
 
 #include "dispatch.hpp"
 #include "launch_util.hpp"
+#include "locate_tables.hpp"
 #include "rs_apply.hpp"
 #include "rs_update.hpp"
 
@@ -34,6 +37,83 @@ template <int RT>
 using MixedPolicy = typename std::conditional<
     (RT > 8), MixedPolicy16, typename std::conditional<(RT > 4), MixedPolicy8, MixedPolicy4>::type>::type;
 
+// ---- locate ---------------------------------------------------------------
+// XORs byte b into row r of an accumulator element (r static under an unrolled loop).
+template <int RT>
+__device__ __forceinline__ void lds_xor_byte(typename LdsAcc<RT>::T& t, int r, uint32_t b) {
+  if constexpr (RT > 8) t.v[r >> 2] ^= b << (8 * (r & 3));
+  else if constexpr (RT > 4) t ^= static_cast<uint64_t>(b) << (8 * r);
+  else t ^= b << (8 * r);
+}
+
+// One byte column's verdict from its syndromes, one per row in the accumulator element.
+template <int RT>
+__device__ __forceinline__ uint32_t locate_column(const typename LdsAcc<RT>::T& t, int rows, int K,
+                                                  const uint8_t* gf, const uint8_t* pt) {
+  uint32_t s[RT / 4];
+  if constexpr (RT > 8) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = t.v[i];
+  } else if constexpr (RT > 4) {
+    s[0] = static_cast<uint32_t>(t);
+    s[1] = static_cast<uint32_t>(t >> 32);
+  } else {
+    s[0] = t;
+  }
+  return locate_classify(s, rows, K, gf, pt);
+}
+
+// Adds every lane's n (0..16) columns of verdict v (kLocateClean: none) into the stripe's
+// bins: one 64-bit atomic per distinct verdict in the wave, issued by one lane. Sums are
+// formed from ballots alone, so lanes that have left the kernel count as nothing; every lane
+// still in the wave must arrive together (no barrier, no LDS).
+__device__ __forceinline__ void locate_wave_add(uint64_t* bins, uint32_t nbins, uint32_t v, uint32_t n) {
+  uint64_t live = __ballot(v != kLocateClean);
+  while (live) {  // wave-uniform
+    const int lead = __builtin_ctzll(live);
+    const uint32_t lv = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), lead));
+    const bool mine = v == lv;
+    uint32_t sum = 0;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) sum += static_cast<uint32_t>(__popcll(__ballot(mine && ((n >> b) & 1u)))) << b;
+    if ((threadIdx.x & 63u) == static_cast<uint32_t>(lead) && sum)
+      atomicAdd(reinterpret_cast<unsigned long long*>(bins + (lv == kLocateUnexplained ? nbins - 1 : lv)),
+                static_cast<unsigned long long>(sum));
+    live &= ~__ballot(mine);
+  }
+}
+
+// The S % 16 tail of a locate launch: lds_tail with every row compared, and a mismatching
+// byte classified and counted. Every thread of the waves that call it reaches the ballots.
+template <int RT>
+__device__ __forceinline__ void locate_tail(const ApplyArgs& a, const LocateArgs& x, cptr<const uint8_t*> in,
+                                            cptr<uint8_t*> out, uint32_t stripe, uint32_t p,
+                                            uint32_t lds0, uint32_t j) {
+  constexpr int W = LdsAcc<RT>::W;
+  const uint32_t nt = static_cast<uint32_t>(a.S - a.nvec * 16);
+  uint32_t v = kLocateClean;
+  if (j < nt) {
+    const uint64_t b = a.nvec * 16 + j;
+    typename LdsAcc<RT>::T t = lds_zero<RT>();
+    for (int i0 = 0; i0 < a.K; i0 += tail_loads<RT>()) {
+      uint32_t xb[tail_loads<RT>()];
+      tail_bytes<RT>(in, b, i0, a.K, xb);
+      for (int jj = 0; jj < tail_loads<RT>() && i0 + jj < a.K; ++jj) {
+        const uint32_t base = lds0 + static_cast<uint32_t>(i0 + jj) * 32u * W;
+        t = t ^ lds_lookup<RT>(base + (xb[jj] & 15u) * W) ^
+            lds_lookup<RT>(base + 16u * W + (xb[jj] >> 4) * W);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+      if (r < a.R) lds_xor_byte<RT>(t, r, out[r][b]);
+    v = locate_column<RT>(t, a.R, a.K, x.gf, x.loc + static_cast<size_t>(p) * x.loc_stride);
+  }
+  if (__ballot(v != kLocateClean) == 0) return;  // wave-uniform
+  if (v != kLocateClean) atomicOr(a.status + static_cast<size_t>(stripe) * a.status_stride, 1);
+  locate_wave_add(x.counts + static_cast<size_t>(stripe) * x.nbins, x.nbins, v, v != kLocateClean ? 1u : 0u);
+}
+
 // One tile of one stripe: the body every mixed and ragged block runs once it knows its
 // stripe, its tile within the stripe, the stripe's pattern p and (in `a`) the stripe's S,
 // nvec and verify mask. Stages pattern p's tables into LDS, runs the S % 16 tail where
@@ -41,9 +121,17 @@ using MixedPolicy = typename std::conditional<
 // SOME (the required plans' kernel): a.R is the stripe's own row count and
 // out_stride the launch group's, the pitch of out_tab; rows at and past a.R have no pointer
 // there and none is loaded.
-template <int RT, class P, bool SOME = false>
+// LOCATE (the locate plans' kernel, §5.12; with SOME): every row is compared. A lane whose 16
+// bytes match in every row does what a verify lane does. A wave with a mismatching lane turns
+// that lane's accumulators into the rows' syndromes (the stored bytes XORed in, read again),
+// classifies its 16 byte columns with locate_classify and adds the columns per verdict into
+// lx->counts, one atomic per verdict and wave (locate_wave_add); nothing block-wide follows the
+// table prologue's barrier.
+template <int RT, class P, bool SOME = false, bool LOCATE = false>
 __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t stripe, uint32_t tile,
-                                           uint32_t p, uint32_t tab_stride, uint32_t out_stride = 0) {
+                                           uint32_t p, uint32_t tab_stride, uint32_t out_stride = 0,
+                                           const LocateArgs* lx = nullptr) {
+  static_assert(!LOCATE || SOME, "a locate launch reads the patterns' row counts");
   constexpr int BS = P::BS;
   constexpr int W = LdsAcc<RT>::W;
   static_assert(P::REALIGN == 0 && P::WIX == 0 && P::DMA == 0 && !P::NOMATH && !P::PERSIST && P::ORD == 0,
@@ -77,7 +165,11 @@ __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t
       reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*)smem));
   if (a.tail_in_vec) {
     const uint32_t j = tail_lane<BS>(a.tail_in_vec, tile);
-    if (j != ~0u) lds_tail<RT>(a, in, out, stripe, lds0, j);
+    if constexpr (LOCATE) {
+      if (j != ~0u) locate_tail<RT>(a, *lx, in, out, stripe, p, lds0, j);
+    } else {
+      if (j != ~0u) lds_tail<RT>(a, in, out, stripe, lds0, j);
+    }
   }
   if (!active) return;
   AccT acc[4][4];
@@ -142,6 +234,44 @@ __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t
     }
   }
   if (bad) atomicOr(a.status + static_cast<size_t>(stripe) * a.status_stride, 1);
+  if constexpr (LOCATE) {
+    if (__ballot(bad) == 0) return;  // wave-uniform: the lanes still here stay together below
+    if (bad) {
+      // acc's byte r holds row r's computed byte: XORing the stored one in leaves the syndrome
+#pragma unroll
+      for (int r = 0; r < RT; ++r) {
+        if (r >= R) continue;
+        uint4 y;
+        if constexpr (kVpf) y = vpre[r];
+        else y = load16<P>(reinterpret_cast<const uint4*>(out[r]) + v0);
+        const uint32_t yw[4] = {y.x, y.y, y.z, y.w};
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) lds_xor_byte<RT>(acc[w][j], r, (yw[w] >> (8 * j)) & 0xffu);
+      }
+    }
+    const uint8_t* pt = lx->loc + static_cast<size_t>(p) * lx->loc_stride;
+    uint64_t* bins = lx->counts + static_cast<size_t>(stripe) * lx->nbins;
+    // a lane's columns almost always share one verdict: it keeps (verdict, columns) and the
+    // wave adds a lane's run when its verdict changes, and every run at the end
+    uint32_t run_v = kLocateClean, run_n = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        uint32_t v = kLocateClean;
+        if (bad) v = locate_column<RT>(acc[w][j], R, K, lx->gf, pt);
+        const bool flush = v != kLocateClean && run_n != 0 && v != run_v;
+        if (__ballot(flush) != 0) locate_wave_add(bins, lx->nbins, flush ? run_v : kLocateClean, run_n);
+        if (flush) run_n = 0;
+        if (v != kLocateClean) {
+          run_v = v;
+          ++run_n;
+        }
+      }
+    locate_wave_add(bins, lx->nbins, run_n ? run_v : kLocateClean, run_n);
+  }
 }
 
 // An RT instance serves every R <= RT (rows >= R are computed and dropped). One tile of
@@ -211,6 +341,27 @@ void rs_apply_ragged_some(ApplyArgs a, RaggedSomeArgs xs) {
   mixed_tile<RT, P, true>(a, smem, stripe, tile, p, x.tab_stride, stride);
 }
 
+// Locate launches: the required block setup, every row compared, and the
+// mismatching byte columns classified and counted (mixed_tile LOCATE).
+template <int RT, class P>
+__global__ __launch_bounds__(P::BS) __attribute__((amdgpu_waves_per_eu(P::WPE, lds_max_waves<RT>())))
+void rs_apply_locate(ApplyArgs a, LocateArgs xl) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  static_assert(P::TILE_VECS == P::BS, "one vector per thread: the tile map counts 512-vector tiles");
+  const RaggedArgs& x = xl.r;
+  const uint32_t t = a.t_base + blockIdx.x;
+  if (t >= x.ntiles) return;  // block-uniform
+  const uint32_t stripe = as_const(x.tile_stripe)[t];
+  const uint32_t tile = t - as_const(x.tile0)[stripe];
+  const uint32_t p = as_const(x.pat)[stripe];
+  a.S = as_const(x.size)[stripe];
+  a.nvec = a.S / 16;
+  a.verify_mask = as_const(x.vmask)[p];
+  const uint32_t stride = static_cast<uint32_t>(a.R);
+  a.R = static_cast<int>(as_const(xl.nrows)[p]);
+  mixed_tile<RT, P, true, true>(a, smem, stripe, tile, p, x.tab_stride, stride, &xl);
+}
+
 // S < 16: one byte position per thread, 16 threads per stripe; the nibble tables are read
 // from the arena in global memory (a launch of batch * S bytes has nothing to amortise an
 // LDS prologue over). An RT instance (8 or 16: the entry width) serves every R <= RT.
@@ -262,6 +413,10 @@ using RaggedSomeFn = void (*)(ApplyArgs, RaggedSomeArgs);
 const std::array<RaggedSomeFn, 3> kRaggedSome = {&dev::rs_apply_ragged_some<4, dev::MixedPolicy<4>>,
                                                  &dev::rs_apply_ragged_some<8, dev::MixedPolicy<8>>,
                                                  &dev::rs_apply_ragged_some<16, dev::MixedPolicy<16>>};
+using LocateFn = void (*)(ApplyArgs, LocateArgs);
+const std::array<LocateFn, 3> kLocate = {&dev::rs_apply_locate<4, dev::MixedPolicy<4>>,
+                                         &dev::rs_apply_locate<8, dev::MixedPolicy<8>>,
+                                         &dev::rs_apply_locate<16, dev::MixedPolicy<16>>};
 static_assert(dev::MixedPolicy<4>::BS == 512 && dev::MixedPolicy<8>::BS == 512 &&
                   dev::MixedPolicy<16>::BS == 512 && dev::MixedPolicy<4>::TILE_VECS == 512 &&
                   dev::MixedPolicy<8>::TILE_VECS == 512 && dev::MixedPolicy<16>::TILE_VECS == 512,
@@ -279,11 +434,12 @@ const std::array<std::array<UpdateFn, 3>, 2> kUpdate = {{
 
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
 // per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one, 2 the
-// required one, 3 the single-source update instance, 4 the pair one)
+// required one, 3 the single-source update instance, 4 the pair one, 5 the locate one)
 DeviceOnce g_mixed_wide_lds;
 
 // The vector launch every kind shares: the dynamic-LDS opt-in (`once_key`: 0 the mixed
-// instance, 1 the ragged one, 2 the required one, 3 and 4 the update ones), then `grid` tiles
+// instance, 1 the ragged one, 2 the required one, 3 and 4 the update ones, 5 the locate one),
+// then `grid` tiles
 // in equal consecutive slices of `streams` shard streams, as launch_apply cuts them. A slice
 // boundary may fall inside a stripe (tiles are numbered over the whole grid).
 template <class X>
@@ -344,6 +500,21 @@ hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, const uint32_t* nrows
   const int inst = a.R > 8 ? 2 : a.R > 4 ? 1 : 0;
   return nrows ? launch_tiles(kRaggedSome[inst], 2, x.ntiles, a, RaggedSomeArgs{x, nrows}, a.K + a.R, stream, ev)
                : launch_tiles(kRagged[inst], 1, x.ntiles, a, x, a.K + a.R, stream, ev);
+}
+
+hipError_t launch_locate(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
+                         LaunchEvents ev) {
+  const RaggedArgs& r = x.r;
+  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
+      !r.pat || !r.vmask || !r.size || !r.tile0 || !a.in_tab || !a.out_tab || !a.status ||
+      r.ntiles > 0x7fffffffu || (r.ntiles && !r.tile_stripe) || !x.nrows || !x.gf || !x.loc ||
+      !x.counts || x.loc_stride != locate_stride(a.K) || x.nbins < 2)
+    return hipErrorInvalidValue;
+  if (r.ntiles == 0) return hipSuccess;  // no stripe has a row
+  a.t_base = 0;
+  a.S = a.nvec = 0;  // per stripe, read by the kernel
+  a.tail_in_vec = any_tail ? 1u : 0u;  // wave 0 of each stripe's first tile
+  return launch_tiles(kLocate[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 5, r.ntiles, a, x, a.K + a.R, stream, ev);
 }
 
 hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_tail,

@@ -2,11 +2,12 @@
 // repeated, graph-capturable launches over shards in device memory -- uniform plans (one
 // erasure pattern, one shard size: every kernel form and tile order), mixed plans (a
 // pattern per stripe), ragged plans (a shard size per stripe too, §5.9) and
-// required plans (only the missing shards a caller wants, §5.10), which share one layout, one
-// upload and one constructor tail -- the tile-order tuner and the one-shot device calls built
-// on them.
+// required plans (only the missing shards a caller wants, §5.10) and locate plans (which shard
+// is corrupt, §5.12), which share one layout, one upload and one constructor tail -- the
+// tile-order tuner and the one-shot device calls built on them.
 #include <cstdio>
 
+#include "locate_tables.hpp"
 #include "mixed_tables.hpp"
 #include "ragged_tables.hpp"
 #include "rs_internal.hpp"
@@ -23,8 +24,10 @@ static_assert(kRaggedTileVecs == kRaggedLaunchTileVecs, "the tile map counts the
 // (ragged_tables.hpp) that every launch group names; the plan's S is the largest shard size
 // (never 0). A required plan (rs_plan_create_required) is a ragged plan whose patterns have their
 // own row counts: every launch group has its own tile map and launches with the patterns' row
-// counts inside it.
-enum class PlanKind { kMixed, kRagged, kRequired };
+// counts inside it. A locate plan (rs_plan_create_locate) is a required plan with nothing
+// wanted, cut to its first launch group, plus what the classification reads (the shared log / exp
+// block and a block per pattern) and the per-stripe, per-shard counts it adds into.
+enum class PlanKind { kMixed, kRagged, kRequired, kLocate };
 
 struct MixedPlan {
   MixedTables t;
@@ -38,6 +41,8 @@ struct MixedPlan {
     bool any_tail = false;  // some stripe of the map has a size that is no multiple of 16
   };
   std::vector<Group> groups;  // per launch group of `t`
+  // a locate plan's pieces: locate_tables.hpp's blocks and the batch * (k + m + 1) counts
+  size_t gf_off = 0, loc_off = 0, loc_stride = 0, counts_off = 0;
 };
 
 // An update plan (rs_plan_create_update): where the pieces of
@@ -131,7 +136,9 @@ ApplyArgs plan_group_args(const rs_plan& plan, size_t gi, RaggedArgs* x = nullpt
     }
   }
   if (nrows)
-    *nrows = mp.kind == PlanKind::kRequired ? reinterpret_cast<const uint32_t*>(d + at.nrows_off) : nullptr;
+    *nrows = mp.kind == PlanKind::kRequired || mp.kind == PlanKind::kLocate
+                 ? reinterpret_cast<const uint32_t*>(d + at.nrows_off)
+                 : nullptr;
   return a;
 }
 
@@ -175,9 +182,19 @@ hipError_t plan_launch(const rs_plan& plan, hipStream_t s, const std::vector<int
     const uint32_t* nrows = nullptr;
     const ApplyArgs a = plan_group_args(plan, gi, &r, &nrows);
     const LaunchEvents g = group_events(ev, gi, ng);
-    const hipError_t e = plan.mixed->kind == PlanKind::kMixed
-                             ? launch_mixed(a, MixedArgs{r.pat, r.vmask, r.tab_stride}, s, g)
-                             : launch_ragged(a, r, nrows, plan.mixed->groups[gi].any_tail, s, g);
+    const MixedPlan& mp = *plan.mixed;
+    hipError_t e;
+    if (mp.kind == PlanKind::kMixed) {
+      e = launch_mixed(a, MixedArgs{r.pat, r.vmask, r.tab_stride}, s, g);
+    } else if (mp.kind == PlanKind::kLocate) {
+      auto* d = static_cast<uint8_t*>(plan.dmeta.p);
+      const LocateArgs x{r, nrows, d + mp.gf_off, d + mp.loc_off,
+                         reinterpret_cast<uint64_t*>(d + mp.counts_off),
+                         static_cast<uint32_t>(mp.loc_stride), static_cast<uint32_t>(mp.t.k + mp.t.m + 1)};
+      e = launch_locate(a, x, mp.groups[gi].any_tail, s, g);
+    } else {
+      e = launch_ragged(a, r, nrows, mp.groups[gi].any_tail, s, g);
+    }
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -284,8 +301,10 @@ int create_uniform(rs_ctx* ctx, int device, int k, int m, size_t S, int batch,
 // group the compare masks, the table arena and the patterns' row counts, each piece 256-B
 // aligned. With `rt` (a ragged or required plan) also the stripes' sizes and the tile maps, and
 // every launch group is given its own. An out_tab slot at or past a stripe's row count holds
-// null, and a shard no row names is in no table.
-int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rt) {
+// null, and a shard no row names is in no table. With `lt` (a locate plan; rt is its ragged
+// part) also the classification's blocks and the zeroed counts.
+int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rt,
+                 const LocateTables* lt = nullptr) {
   MixedPlan& mp = *plan.mixed;
   const int k = mp.t.k, n = mp.t.k + mp.t.m, batch = plan.batch;
   Packer pk;
@@ -309,10 +328,20 @@ int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rt) 
       tile_stripe_off.push_back(pk.take(sizeof(uint32_t) * std::max<size_t>(1, tm.tile_stripe.size())));
     }
   }
+  if (lt) {
+    mp.gf_off = pk.take(lt->gf.size());
+    mp.loc_stride = lt->stride;
+    mp.loc_off = pk.take(std::max<size_t>(1, lt->loc.size()));
+    mp.counts_off = pk.take(sizeof(uint64_t) * static_cast<size_t>(batch) * (n + 1));
+  }
   std::vector<uint8_t> h(pk.off, 0);
   auto put = [&](size_t off, const auto& v) {
     if (!v.empty()) std::memcpy(h.data() + off, v.data(), sizeof(v[0]) * v.size());
   };
+  if (lt) {
+    put(mp.gf_off, lt->gf);
+    put(mp.loc_off, lt->loc);
+  }
   auto shard_ptr = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
   auto* in = reinterpret_cast<const uint8_t**>(h.data() + mp.in_off);
   for (int b = 0; b < batch; ++b) {
@@ -362,21 +391,25 @@ int create_tabled(rs_ctx* ctx, int device, int k, int m, PlanKind kind, size_t S
                   uint8_t* const* shards, rs_plan** out) {
   if (!ctx->device(device)) return RS_E_ARG;
   const bool sized = kind != PlanKind::kMixed;
-  RaggedTables rt;
-  if (const int rc = table_status(sized ? build_ragged_tables(k, m, batch, sizes, present, required, rt)
-                                        : build_mixed_tables(k, m, batch, present, nullptr, rt.mixed)))
+  LocateTables lt;
+  RaggedTables& rt = lt.ragged;
+  if (const int rc = table_status(kind == PlanKind::kLocate ? build_locate_tables(k, m, batch, sizes, present, lt)
+                                  : sized ? build_ragged_tables(k, m, batch, sizes, present, required, rt)
+                                          : build_mixed_tables(k, m, batch, present, nullptr, rt.mixed)))
     return rc;
   auto plan = new_plan(device, sized ? *std::max_element(sizes, sizes + batch) : S, batch);
   plan->mixed = std::make_unique<MixedPlan>();
   plan->mixed->kind = kind;
   plan->mixed->t = std::move(rt.mixed);
-  plan->fixed_form = RS_ORDER_CONSECUTIVE + (kind == PlanKind::kMixed    ? kOrderMixed
-                                             : kind == PlanKind::kRagged ? kOrderRagged
-                                                                         : kOrderRequired);
+  plan->fixed_form = RS_ORDER_CONSECUTIVE + (kind == PlanKind::kMixed      ? kOrderMixed
+                                             : kind == PlanKind::kRagged   ? kOrderRagged
+                                             : kind == PlanKind::kRequired ? kOrderRequired
+                                                                           : kOrderLocate);
   // per stripe with a row: the k shards read, the rows written and the rows compared. Every
   // stripe of a mixed plan has m rows: n shards of S bytes each.
   plan->bytes = sized ? rt.bytes : static_cast<uint64_t>(batch) * S * static_cast<uint64_t>(k + m);
-  if (const int rc = upload_mixed(*plan, shards, sized ? &rt : nullptr)) return rc;
+  if (const int rc = upload_mixed(*plan, shards, sized ? &rt : nullptr, kind == PlanKind::kLocate ? &lt : nullptr))
+    return rc;
   *out = plan.release();
   return RS_OK;
 }
@@ -491,6 +524,22 @@ int rs_plan_create_required(rs_ctx* ctx, int device, int k, int m, int batch, co
   if (ragged_sizes_equal(batch, sizes) && required_pairs_equal(n, batch, present, required))
     return create_uniform(ctx, device, k, m, sizes[0], batch, present, required, shards, out);
   return create_tabled(ctx, device, k, m, PlanKind::kRequired, 0, batch, sizes, present, required, shards, out);
+}
+
+int rs_plan_create_locate(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                          const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
+  DeviceGuard dg;
+  int rc = check_plan_args(ctx, k, m, batch, sizes && shards, out);
+  if (!rc) rc = check_stripes(k, k + m, batch, sizes, nullptr);
+  if (rc) return rc;
+  // no masks: every shard of every stripe is present
+  std::vector<uint8_t> all;
+  if (!present) {
+    all.assign(static_cast<size_t>(batch) * (k + m), 1);
+    present = all.data();
+  }
+  // (no route to a simpler plan: only this kind counts)
+  return create_tabled(ctx, device, k, m, PlanKind::kLocate, 0, batch, sizes, present, nullptr, shards, out);
 }
 
 int rs_plan_create_update(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
@@ -795,6 +844,23 @@ int rs_plan_status(rs_plan* plan, void* stream, int* corrupt) {
   const int rc = rs_plan_stripe_status(plan, stream, flags.data());
   if (rc) return rc;
   *corrupt = std::any_of(flags.begin(), flags.end(), [](int f) { return f != 0; });
+  return RS_OK;
+}
+
+// The counts a locate plan's launches have added since the last read, then cleared (as
+// rs_plan_stripe_status does with the flags): a plan launched twice before a read reports
+// every count doubled.
+int rs_plan_blame(rs_plan* plan, void* stream, uint64_t* counts) {
+  DeviceGuard dg;
+  if (!plan || !counts || !plan->mixed || plan->mixed->kind != PlanKind::kLocate) return RS_E_ARG;
+  HIPCHK(hipSetDevice(plan->device));
+  auto s = static_cast<hipStream_t>(stream);
+  const MixedPlan& mp = *plan->mixed;
+  auto* c = static_cast<uint8_t*>(plan->dmeta.p) + mp.counts_off;
+  const size_t bytes = sizeof(uint64_t) * static_cast<size_t>(plan->batch) * (mp.t.k + mp.t.m + 1);
+  HIPCHK(hipMemcpyAsync(counts, c, bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemsetAsync(c, 0, bytes, s));
+  HIPCHK(hipStreamSynchronize(s));
   return RS_OK;
 }
 

@@ -218,7 +218,8 @@ class Plan:
     present parity is re-verified (codec.go:55,59). A flat sequence of k+m flags is one
     mask for the whole batch; a batch x (k+m) sequence or array gives every stripe its own
     mask (a mixed plan, DESIGN.md §5.8: one launch repairs stripes with different erasures).
-    `Plan.ragged` builds a plan over stripes of different shard sizes.
+    `Plan.ragged` builds a plan over stripes of different shard sizes,
+    `Plan.locate` one that tells which shard of a stripe is corrupt (§5.12).
     """
 
     def __init__(self, k: int, m: int, S: int, batch: int, pointers: Sequence[int],
@@ -302,9 +303,56 @@ class Plan:
         return self
 
     @classmethod
-    def for_ragged(cls, rb: "RaggedBatch", present=None, context=None, required=None) -> "Plan":
+    def for_ragged(cls, rb: "RaggedBatch", present=None, context=None, required=None,
+                   locate: bool = False) -> "Plan":
         dev = rb.device.index if rb.device.index is not None else 0
+        if locate:
+            if required is not None:
+                raise ValueError("a locate plan writes nothing: no required set")
+            return cls.locate(rb.k, rb.m, rb.sizes, rb.pointers(), present, dev, context)
         return cls.ragged(rb.k, rb.m, rb.sizes, rb.pointers(), present, dev, context, required)
+
+    @classmethod
+    def locate(cls, k: int, m: int, sizes: Sequence[int], pointers: Sequence[int],
+               present=None, device: int = 0, context: Optional[N.Context] = None) -> "Plan":
+        """rs_plan_create_locate: a plan that writes nothing and tells which
+        shard of a stripe is corrupt. present: None (every shard present) or batch rows of k+m
+        flags. A launch compares each stripe's present shards beyond the first k (16 at the
+        most) and classifies every mismatching byte column; `blame()` reads the counts."""
+        n, batch = k + m, len(sizes)
+        if len(pointers) != batch * n:
+            raise ValueError("need batch*(k+m) shard pointers")
+        pres = None
+        if present is not None:
+            rows = _mask_rows(present)
+            if rows is None or len(rows) != batch or any(len(r) != n for r in rows):
+                raise ValueError("present: None, or batch rows of k+m flags")
+            pres = (ctypes.c_uint8 * (batch * n))(*[1 if p else 0 for r in rows for p in r])
+        self = cls.__new__(cls)
+        self.ctx = context or N.default_context()
+        self.k, self.m, self.S, self.batch, self.device = k, m, None, batch, device
+        self.sizes = [int(s) for s in sizes]
+        self.handle = None
+        ptrs = (ctypes.c_void_p * max(1, len(pointers)))(*pointers)
+        szs = (ctypes.c_size_t * max(1, batch))(*self.sizes)
+        h = ctypes.c_void_p()
+        N.check(N.lib.rs_plan_create_locate(self.ctx.handle, device, k, m, batch, szs, pres, ptrs,
+                                            ctypes.byref(h)), "rs_plan_create_locate")
+        self.handle = h
+        return self
+
+    def blame(self, stream: Optional[torch.cuda.Stream] = None):
+        """rs_plan_blame of a locate plan: synchronises the stream and returns a
+        (batch, k+m+1) uint64 array: [b, i] = byte columns of stripe b blamed on shard i,
+        [b, k+m] = its unexplained columns. Clears the counts; launches accumulate until the
+        next read, so two launches before one read give every count doubled."""
+        import numpy as np
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        out = np.zeros((self.batch, self.k + self.m + 1), dtype=np.uint64)
+        N.check(N.lib.rs_plan_blame(self.handle, ctypes.c_void_p(s.cuda_stream),
+                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))),
+                "rs_plan_blame")
+        return out
 
     @classmethod
     def update(cls, k: int, m: int, sizes: Sequence[int], changed, old_ptrs, new_ptrs,
@@ -391,7 +439,8 @@ class Plan:
                    166: "realign64-x32", 192: "dma", 194: "dma-g2", 195: "dma-q8",
                    198: "dma-x32", 224: "tridb-g4", 225: "tridb-g8", 256: "bs", 257: "bs-g8",
                    258: "bs-g2", 259: "bs-q8", 260: "bs-q16", 261: "bs-x8", 262: "bs-x32",
-                   512: "mixed", 1024: "ragged", 2048: "required", 4096: "update"}
+                   512: "mixed", 1024: "ragged", 2048: "required", 4096: "update",
+                   8192: "locate"}
 
     def tune(self, reps: int = 5, stream: Optional[torch.cuda.Stream] = None) -> list:
         """rs_plan_tune: time each launch group in every tile order its kernel offers

@@ -252,6 +252,45 @@ class Codec:
             return out
         raise _decode_error(rc)
 
+    def decode_heal(self, shards: List, profile: ErasureProfile,
+                    original_size: int) -> Tuple[bytearray, List[int]]:
+        """rs_codec_decode_heal: decode() that repairs what it can where
+        decode() raises ErrShardCorrupted. The corrupt shards are located from the parity
+        syndromes; when they explain every mismatching column and a compared shard is left
+        to confirm with, they are rebuilt in place (writable buffers) with the missing ones.
+        Returns (data, healed shard indices); every other error is decode()'s."""
+        k, m = profile.data_shards, profile.parity_shards
+        if k < 1 or m < 1:
+            raise ErrInvalidProfile()
+        n = k + m
+        if k + m > 256:
+            raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create decoder")
+        if len(shards) != n:
+            raise ErrTooFewShards(f"erasure: reconstruction failed: {ErrTooFewShards.text}")
+        lens = (ctypes.c_size_t * n)()
+        for i, s in enumerate(shards):
+            lens[i] = 0 if s is None else len(s)
+        S = next((lens[i] for i in range(n) if lens[i]), 0)
+        bufs = list(shards)
+        for i in range(n):
+            if lens[i] == 0 and S:
+                bufs[i] = bytearray(S)
+            elif lens[i] and not _writable(bufs[i]):
+                raise TypeError("decode_heal rebuilds corrupt shards in place: writable buffers")
+        ptrs = (ctypes.c_void_p * n)(*[_addr(b) if b is not None and len(b) else 0
+                                      for b in bufs])
+        out = bytearray(max(int(original_size), 0))
+        healed = (ctypes.c_uint8 * n)()
+        rc = N.lib.rs_codec_decode_heal(self.context.handle, k, m, ptrs, lens,
+                                        _addr(out) if out else None, int(original_size), healed)
+        if rc in (N.RS_OK, N.RS_E_CORRUPT, N.RS_E_INSUFFICIENT):
+            for i in range(n):
+                if (shards[i] is None or len(shards[i]) == 0) and lens[i]:
+                    shards[i] = bufs[i]
+        if rc == N.RS_OK:
+            return out, [i for i in range(n) if healed[i]]
+        raise _decode_error(rc)
+
     def encode_many(self, datas: Sequence, profile: ErasureProfile
                     ) -> Tuple[List[Optional[List[memoryview]]], List[Optional[Exception]]]:
         """Codec.encode for many objects of one profile in one native call
@@ -620,6 +659,88 @@ def reconstruct_batch(stripes: List[List], k: int, m: int, verify: bool = True,
                 if (st[i] is None or len(st[i]) == 0) and lens[b * n + i]:
                     st[i] = bufs[b][i]
     return out
+
+
+def _per_stripe(rc: int, status: Sequence[int], what: str) -> None:
+    """Raises for a call-level error of a batch call: a code no stripe reports."""
+    if rc < 0 and rc not in status:
+        N.check(rc, what)
+
+
+def locate(shards: List, k: int, m: int, context: Optional[N.Context] = None) -> np.ndarray:
+    """rs_locate: which shard of a stripe is corrupt. shards: an n-list
+    (None / empty = missing); nothing is written. Returns k+m+1 uint64 counts: [i] = byte
+    columns blamed on shard i, [k+m] = columns that mismatch but that no single shard
+    explains. All zero for a clean stripe (and for one with exactly k shards present)."""
+    ctx = context or N.default_context()
+    n = k + m
+    if len(shards) != n:
+        raise ErrTooFewShards()
+    lens = (ctypes.c_size_t * n)(*[0 if s is None else len(s) for s in shards])
+    counts = np.zeros(n + 1, dtype=np.uint64)
+    rc = N.lib.rs_locate(ctx.handle, k, m, _shard_ptrs(shards), lens,
+                         counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+    if rc not in (N.RS_OK, N.RS_E_CORRUPT):
+        raise _wrapped(rc, "locate")
+    return counts
+
+
+def locate_batch(stripes: Sequence[Sequence], k: int, m: int,
+                 context: Optional[N.Context] = None) -> Tuple[np.ndarray, List[int]]:
+    """rs_locate_batch: locate() for many stripes of any sizes and erasures in one call.
+    Returns (counts, a (batch, k+m+1) uint64 array; status[b]: RS_OK, RS_E_CORRUPT where a
+    column mismatched, or the stripe's own error as reconstruct_batch reports it)."""
+    ctx = context or N.default_context()
+    n = k + m
+    B = len(stripes)
+    if any(len(st) != n for st in stripes):
+        raise ErrTooFewShards()
+    lens = (ctypes.c_size_t * max(B * n, 1))(*[0 if s is None else len(s) for st in stripes for s in st])
+    counts = np.zeros((B, n + 1), dtype=np.uint64)
+    status = (ctypes.c_int * max(B, 1))()
+    rc = N.lib.rs_locate_batch(ctx.handle, k, m, B, _shard_ptrs([s for st in stripes for s in st] or [None]),
+                               lens, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), status)
+    out = list(status)[:B]
+    _per_stripe(rc, out, "rs_locate_batch")
+    return counts, out
+
+
+def heal_batch(stripes: List[List], k: int, m: int,
+               context: Optional[N.Context] = None) -> Tuple[List[int], List[List[int]]]:
+    """rs_heal_batch: reconstruct_batch(verify=True) that repairs what it can. A stripe whose
+    compared shards mismatch is located; when the blamed shards explain every mismatching
+    column and a compared shard is left to confirm with, they are rebuilt in place (writable
+    buffers) together with the missing ones and the stripe verified again. Returns
+    (status[b], healed[b] = indices of the shards rebuilt because they were corrupt)."""
+    ctx = context or N.default_context()
+    n = k + m
+    B = len(stripes)
+    if any(len(st) != n for st in stripes):
+        raise ErrTooFewShards()
+    flat, lens, bufs = [], (ctypes.c_size_t * max(B * n, 1))(), []
+    for b, st in enumerate(stripes):
+        ln = [0 if s is None else len(s) for s in st]
+        S = next((x for x in ln if x), 0)
+        cp = list(st)
+        for i in range(n):
+            lens[b * n + i] = ln[i]
+            if ln[i] == 0 and S:
+                cp[i] = bytearray(S)
+            elif ln[i] and not _writable(cp[i]):
+                raise TypeError("heal_batch rebuilds corrupt shards in place: writable buffers")
+        bufs.append(cp)
+        flat += cp
+    status = (ctypes.c_int * max(B, 1))()
+    healed = (ctypes.c_uint8 * max(B * n, 1))()
+    rc = N.lib.rs_heal_batch(ctx.handle, k, m, B, _shard_ptrs(flat or [None]), lens, healed, status)
+    out = list(status)[:B]
+    _per_stripe(rc, out, "rs_heal_batch")
+    for b, st in enumerate(stripes):
+        if out[b] in (N.RS_OK, N.RS_E_CORRUPT):
+            for i in range(n):
+                if (st[i] is None or len(st[i]) == 0) and lens[b * n + i]:
+                    st[i] = bufs[b][i]
+    return out, [[i for i in range(n) if healed[b * n + i]] for b in range(B)]
 
 
 def host_counters(context: Optional[N.Context] = None) -> dict:

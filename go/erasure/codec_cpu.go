@@ -2,7 +2,10 @@
 
 package erasure
 
-import "fmt"
+import (
+	"errors"
+	"fmt"
+)
 
 // Builds without the GPU codec (the default CGO_ENABLED=0 release builds,
 // Dockerfile:20-22, builds.sh:8-20) keep the reference codec: after codec.go.diff its
@@ -128,6 +131,30 @@ func (c *Codec) UpdateBatch(shards, newData [][][]byte, profile ErasureProfile) 
 		errs[b] = c.UpdateParity(shards[b], newData[b], profile)
 	}
 	return errs
+}
+
+// ErrLocateUnavailable is what Locate reports on builds without the GPU codec: the CPU codec
+// has no locator (the reference finds a bad shard by its checksum, manager.go:250-320).
+var ErrLocateUnavailable = errors.New("erasure: locating corrupt shards needs the GPU codec")
+
+// Locate reports ErrLocateUnavailable on builds without the GPU codec.
+func (c *Codec) Locate(shards [][]byte, profile ErasureProfile) ([]uint64, error) {
+	if profile.DataShards < 1 || profile.ParityShards < 1 {
+		return nil, ErrInvalidProfile
+	}
+	return nil, ErrLocateUnavailable
+}
+
+// HealBatch is RepairSome of every missing shard on builds without the GPU codec: nothing is
+// healed, and an object whose present shards mismatch reports ErrShardCorrupted as before.
+func (c *Codec) HealBatch(objs [][][]byte, profile ErasureProfile) ([][]int, []error) {
+	return make([][]int, len(objs)), c.RepairSome(objs, nil, profile)
+}
+
+// DecodeHeal is Decode on builds without the GPU codec: nothing is healed.
+func (c *Codec) DecodeHeal(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, []int, error) {
+	out, err := c.cpuDecode(shards, profile, originalSize)
+	return out, nil, err
 }
 
 // Overwrite replaces object bytes [offset, offset+len(data)) in the data shards and updates

@@ -519,6 +519,74 @@ int rs_plan_create_update(rs_ctx* ctx, int device, int k, int m, int batch, cons
                           const uint8_t* changed, const uint8_t* const* old_data,
                           const uint8_t* const* new_data, uint8_t* const* parity, rs_plan** out);
 
+/* ---- locate plans: which shard is corrupt --------------------------
+ * Not in the reference API. Every other plan tells that a stripe's compared shards mismatch; a
+ * locate plan tells where. sizes, present and shards as for rs_plan_create_ragged, but present
+ * == NULL means every shard of every stripe is present. Nothing is written: a launch reads, per
+ * stripe, the first k present shards and the next r' = min(present - k, 16) present shards,
+ * recomputes the latter from the former and, for every byte column in which they differ,
+ * decides from the r' differences (the syndromes) which one shard explains them:
+ *   - one compared shard differs alone: that shard is blamed;
+ *   - every compared shard differs, consistently with one error in one of the k read shards:
+ *     that shard is blamed;
+ *   - anything else, and every mismatch of a stripe with r' = 1: the column is unexplained.
+ * Over the k + r' examined shards a column with one corrupt byte is blamed on exactly that
+ * shard, and a column with 2..r'-1 corrupt bytes is never blamed on anybody; with r' or more
+ * corrupt bytes a column can be misattributed or look clean. Present shards past the 16th
+ * compared one are neither read nor blamed. A stripe with exactly k present shards has no row
+ * and is in no launch; its counts and flag stay 0.
+ * rs_plan_blame synchronises `stream` and copies out batch * (k+m+1) counts: counts[b*(k+m+1) +
+ * i] is the number of byte columns of stripe b blamed on shard i, and entry k+m of a stripe
+ * its unexplained columns. It then clears them, as rs_plan_stripe_status clears the flags.
+ * LAUNCHES ACCUMULATE until the next read: a plan launched twice before a read reports every
+ * count doubled. RS_E_ARG for NULL or for a plan that is not a locate plan.
+ * It is an ordinary plan otherwise: rs_plan_launch / _launch_timed only enqueue (no allocation,
+ * no sync; graph-capturable); _status and _stripe_status report a flag for every stripe with a
+ * nonzero syndrome; _destroy as for any plan, and
+ *   rs_plan_groups  returns 1, or 0 when no stripe has a row;
+ *   rs_plan_bytes   returns the sum over the stripes with a row of sizes[b] * (k + r'_b);
+ *   rs_plan_forms   reports RS_ORDER_LOCATE + RS_ORDER_CONSECUTIVE;
+ *   rs_plan_tune, rs_plan_set_orders and rs_plan_launch_ceiling behave as for a ragged plan;
+ *   no bit-sliced kernel, no hiprtc compile, no tune-table entry.
+ * Errors are those of rs_plan_create_ragged. */
+#define RS_ORDER_LOCATE 8192
+int rs_plan_create_locate(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                          const uint8_t* present, uint8_t* const* shards, rs_plan** out);
+int rs_plan_blame(rs_plan* plan, void* stream, uint64_t* counts);
+
+/* ---- locate and heal, host memory -----------------------------------
+ * rs_locate / rs_locate_batch: the locate plan's counts for stripes in host memory; shards and
+ * lens as for rs_verify / rs_reconstruct_batch (lens 0 = missing; nothing is written), counts
+ * as for rs_plan_blame (k+m+1 words per stripe, written for every stripe, zero where nothing ran).
+ * Argument and shard checks and status[b] follow rs_reconstruct_batch with verify != 0:
+ * RS_E_NO_DATA, RS_E_SHARD_SIZE, RS_E_TOO_FEW_SHARDS, RS_E_ARG (a NULL present shard), and
+ * RS_E_CORRUPT for a stripe with any mismatching column -- its counts say where. rs_locate
+ * returns that status; rs_locate_batch RS_OK or the first nonzero status in stripe order, and
+ * call-level errors as rs_reconstruct_batch. A stripe with exactly k present shards has zero
+ * counts and is RS_OK without device work; a call of such stripes alone reaches no device. The
+ * calls take the staged ragged pipeline (a chunk: one H2D, one launch, one D2H of status words
+ * and counts) whatever memory the buffers are in; a stripe above CALLFS_RS_CHUNK_BYTES is cut
+ * into column parts whose counts are added up. rs_host_counters counts them like the others.
+ * rs_heal_batch: rs_reconstruct_batch with verify that repairs what it can. (a) Reconstruct and
+ * verify; stripes that come back RS_OK are done, healed all 0. (b) Each RS_E_CORRUPT stripe is
+ * located over its original presence; B = the shards with a nonzero count. It is healed only
+ * if no column is unexplained, B is not empty and present - |B| >= k + 1, so that a compared
+ * shard is left to confirm with. (c) B and the originally missing shards are rebuilt from the
+ * others and the rest verified again: clean -> status[b] = RS_OK, healed[b*(k+m) + i] = 1 for
+ * i in B, every lens entry S; otherwise RS_E_CORRUPT. Present shards outside B are never
+ * written; on RS_E_CORRUPT the bytes of the originally missing shards and of B are
+ * unspecified. Other status values and the return value as rs_reconstruct_batch.
+ * rs_codec_decode_heal: rs_codec_decode with that heal in place of the bare Verify failure;
+ * healed receives k+m flags. Error precedence, join and trim are rs_codec_decode's. */
+int rs_locate(rs_ctx* ctx, int k, int m, const uint8_t* const* shards, const size_t* lens,
+              uint64_t* counts);
+int rs_locate_batch(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* shards,
+                    const size_t* lens, uint64_t* counts, int* status);
+int rs_heal_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards, size_t* lens,
+                  uint8_t* healed, int* status);
+int rs_codec_decode_heal(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                         uint8_t* out, int64_t original_size, uint8_t* healed);
+
 /* ---- ShardChecksum on device-resident shards (codec.go:81-84; §8(f) of SURVEY.md) ----
  * SHA-256 of `count` messages already in HBM, one digest per message written to
  * `digests` (device memory, 32*count bytes, FIPS 180-4 byte order — hex-encode it for
