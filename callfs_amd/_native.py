@@ -132,6 +132,16 @@ SIGNATURES = {
                              ctypes.POINTER(_int)]),
     "rs_codec_decode_heal": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _vp,
                                     _i64, _u8p]),
+    "rs_plan_create_locate_ex": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
+                                        ctypes.POINTER(_vp), _int, ctypes.POINTER(_vp)]),
+    "rs_locate_ex": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+                            ctypes.POINTER(ctypes.c_uint64), _int]),
+    "rs_locate_batch_ex": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_int), _int]),
+    "rs_heal_batch_ex": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _u8p,
+                                ctypes.POINTER(_int), _int]),
+    "rs_codec_decode_heal_ex": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _vp,
+                                       _i64, _u8p, _int]),
     "rs_update": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                          ctypes.POINTER(_vp)]),
     "rs_encode_idx": (_int, [_vp, _int, _int, _sz, _vp, _int, ctypes.POINTER(_vp)]),

@@ -41,7 +41,8 @@ int upload_locate_tables(const LocateRun& r, Lane& L, LocateDevTables& dt) {
   dt.arena_off = pk.take(g.arena.size());
   dt.gf_off = pk.take(r.t.gf.size());
   dt.loc_off = pk.take(r.t.loc.size());
-  std::string key = "L" + std::to_string(r.k) + "," + std::to_string(r.m) + ":";
+  // ("L": single plans' tables, "M": pair plans')
+  std::string key = (r.t.max_errors > 1 ? "M" : "L") + std::to_string(r.k) + "," + std::to_string(r.m) + ":";
   for (const MixedPattern& p : r.mt().patterns) key.append(reinterpret_cast<const char*>(p.mask.data()), p.mask.size());
   if (L.rag_tabs.p && L.rag_key == key) return RS_OK;
   L.rag_key.clear();
@@ -157,7 +158,7 @@ int run_locate_chunks(const LocateRun& r, Lane& L, const std::vector<RaggedItem>
     x.counts = reinterpret_cast<uint64_t*>(d + locate_counts_off(C));
     x.loc_stride = static_cast<uint32_t>(r.t.stride);
     x.nbins = static_cast<uint32_t>(nb);
-    HIPCHK(launch_locate(a, x, C.any_tail, sl.stream));
+    HIPCHK(launch_locate(a, x, C.any_tail, sl.stream, {}, r.t.max_errors));
     HIPCHK(hipMemcpyAsync(h + C.status_off, d + C.status_off, total - C.status_off, hipMemcpyDeviceToHost,
                           sl.stream));
     HIPCHK(hipEventRecord(sl.done, sl.stream));
@@ -174,9 +175,10 @@ int run_locate_chunks(const LocateRun& r, Lane& L, const std::vector<RaggedItem>
 
 // The call's runnable stripes `ids` (each has more than k present shards, a nonzero size and
 // its pointers) on one device and lane. sizes and present (0 / 1 flags, batch * (k + m)) are
-// the whole call's; counts too, zeroed by the caller.
+// the whole call's; counts too, zeroed by the caller. max_errors 1 or 2 (2: pair tables and the
+// pair kernel).
 template <class ShardF>
-int run_locate(rs_ctx* ctx, int k, int m, const std::vector<int>& ids, const size_t* sizes,
+int run_locate(rs_ctx* ctx, int k, int m, int max_errors, const std::vector<int>& ids, const size_t* sizes,
                const uint8_t* present, ShardF shard_of, uint64_t* counts, int* flags) {
   if (ids.empty()) return RS_OK;
   if (ctx->devs.empty()) return RS_E_HIP;
@@ -186,7 +188,7 @@ int run_locate(rs_ctx* ctx, int k, int m, const std::vector<int>& ids, const siz
   const size_t n = static_cast<size_t>(k + m);
   return with_lane(ctx, dev, [&](Lane& L) -> int {
     HIPCHK(hipSetDevice(dev->id));
-    const size_t per = pattern_arena_bytes(k, kLocateRows) + locate_stride(k);
+    const size_t per = pattern_arena_bytes(k, kLocateRows) + locate_stride(k, max_errors);
     const size_t max_patterns = std::max<size_t>(1, kRaggedArenaBudget / per);
     size_t begin = 0;
     while (begin < ids.size()) {
@@ -206,7 +208,7 @@ int run_locate(rs_ctx* ctx, int k, int m, const std::vector<int>& ids, const siz
         sz[s] = sizes[r.ids[s]];
         std::memcpy(&pres[s * n], present + static_cast<size_t>(r.ids[s]) * n, n);
       }
-      const TableError te = build_locate_tables(k, m, count, sz.data(), pres.data(), r.t);
+      const TableError te = build_locate_tables(k, m, count, sz.data(), pres.data(), r.t, max_errors);
       if (te == TableError::kSingular) return RS_E_SINGULAR;
       if (te != TableError::kOk || r.mt().groups.size() != 1) return RS_E_ARG;
       r.sh.k = k;

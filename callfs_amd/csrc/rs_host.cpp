@@ -255,8 +255,9 @@ int codec_decode(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens
 // verify that wants nothing (so a stripe of exactly k present shards is RS_OK with zero counts
 // and no device work), then the locate pipeline over the stripes with a compared shard.
 // counts: batch * (k + m + 1), written for every stripe; status[b] = RS_E_CORRUPT where a
-// syndrome of stripe b was nonzero.
-int locate_batch_host(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* shards,
+// syndrome of stripe b was nonzero. max_errors 1 or 2 (checked by the exported calls): 2 locates
+// with pair tables, and a column blamed on two shards counts in both.
+int locate_batch_host(rs_ctx* ctx, int k, int m, int max_errors, int batch, const uint8_t* const* shards,
                       const size_t* lens, uint64_t* counts, int* status) {
   const size_t n = static_cast<size_t>(k + m), B = static_cast<size_t>(batch);
   std::fill(counts, counts + B * (n + 1), 0);
@@ -272,7 +273,7 @@ int locate_batch_host(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const
     ids.push_back(static_cast<int>(b));
   }
   std::vector<int> flags(B, 0);
-  const int rc = run_locate(ctx, k, m, ids, S.data(), present.data(),
+  const int rc = run_locate(ctx, k, m, max_errors, ids, S.data(), present.data(),
                             [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; }, counts,
                             flags.data());
   if (rc) return rc;
@@ -286,8 +287,8 @@ int locate_batch_host(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const
 // is explained by a set B of shards and a compared row is left without them, B and the
 // originally missing shards (rebuilt from corrupt inputs the first time) are rebuilt and the
 // rest verified again. Present shards outside B are never written.
-int heal_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards, size_t* lens,
-                    uint8_t* healed, int* status) {
+int heal_batch_host(rs_ctx* ctx, int k, int m, int max_errors, int batch, uint8_t* const* shards,
+                    size_t* lens, uint8_t* healed, int* status) {
   const size_t n = static_cast<size_t>(k + m), B = static_cast<size_t>(batch);
   std::fill(healed, healed + B * n, 0);
   const std::vector<size_t> lens0(lens, lens + B * n);
@@ -308,7 +309,8 @@ int heal_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards
     }
   std::vector<uint64_t> counts(nb * (n + 1));
   std::vector<int> st1(nb, RS_OK);
-  if ((rc = locate_batch_host(ctx, k, m, static_cast<int>(nb), sh1.data(), ln1.data(), counts.data(), st1.data())))
+  if ((rc = locate_batch_host(ctx, k, m, max_errors, static_cast<int>(nb), sh1.data(), ln1.data(), counts.data(),
+                              st1.data())))
     return rc;
   // (c) the stripes whose blamed set leaves a row to confirm with
   std::vector<int> cand;  // indices into bad
@@ -440,43 +442,67 @@ int rs_codec_decode_data(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size
 
 // ---- exported: locate and heal ----------------------------------------
 
-int rs_locate_batch(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* shards,
-                    const size_t* lens, uint64_t* counts, int* status) {
+// max_errors of the _ex calls: below 1 is an argument error (with the NULL and count checks),
+// above 2 is not built; both before any device work.
+static int check_max_errors(int max_errors) { return max_errors > 2 ? RS_E_UNSUPPORTED : RS_OK; }
+
+int rs_locate_batch_ex(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* shards,
+                       const size_t* lens, uint64_t* counts, int* status, int max_errors) {
   DeviceGuard dg;
   int rc = check_profile(k, m);
   if (rc) return rc;
-  if (!ctx || batch < 0 || (batch && (!shards || !lens || !counts || !status))) return RS_E_ARG;
-  if ((rc = locate_batch_host(ctx, k, m, batch, shards, lens, counts, status))) return rc;
+  if (!ctx || batch < 0 || max_errors < 1 || (batch && (!shards || !lens || !counts || !status))) return RS_E_ARG;
+  if ((rc = check_max_errors(max_errors))) return rc;
+  if ((rc = locate_batch_host(ctx, k, m, max_errors, batch, shards, lens, counts, status))) return rc;
   return first_error(status, batch);
+}
+
+int rs_locate_batch(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* shards,
+                    const size_t* lens, uint64_t* counts, int* status) {
+  return rs_locate_batch_ex(ctx, k, m, batch, shards, lens, counts, status, 1);
+}
+
+int rs_locate_ex(rs_ctx* ctx, int k, int m, const uint8_t* const* shards, const size_t* lens,
+                 uint64_t* counts, int max_errors) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shards || !lens || !counts || max_errors < 1) return RS_E_ARG;
+  if ((rc = check_max_errors(max_errors))) return rc;
+  int status = RS_OK;
+  if ((rc = locate_batch_host(ctx, k, m, max_errors, 1, shards, lens, counts, &status))) return rc;
+  return status;
 }
 
 int rs_locate(rs_ctx* ctx, int k, int m, const uint8_t* const* shards, const size_t* lens,
               uint64_t* counts) {
+  return rs_locate_ex(ctx, k, m, shards, lens, counts, 1);
+}
+
+int rs_heal_batch_ex(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards, size_t* lens,
+                     uint8_t* healed, int* status, int max_errors) {
   DeviceGuard dg;
   int rc = check_profile(k, m);
   if (rc) return rc;
-  if (!ctx || !shards || !lens || !counts) return RS_E_ARG;
-  int status = RS_OK;
-  if ((rc = locate_batch_host(ctx, k, m, 1, shards, lens, counts, &status))) return rc;
-  return status;
+  if (!ctx || batch < 0 || max_errors < 1 || (batch && (!shards || !lens || !healed || !status))) return RS_E_ARG;
+  if ((rc = check_max_errors(max_errors))) return rc;
+  if (batch == 0) return RS_OK;
+  return heal_batch_host(ctx, k, m, max_errors, batch, shards, lens, healed, status);
 }
 
 int rs_heal_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards, size_t* lens,
                   uint8_t* healed, int* status) {
-  DeviceGuard dg;
-  int rc = check_profile(k, m);
-  if (rc) return rc;
-  if (!ctx || batch < 0 || (batch && (!shards || !lens || !healed || !status))) return RS_E_ARG;
-  if (batch == 0) return RS_OK;
-  return heal_batch_host(ctx, k, m, batch, shards, lens, healed, status);
+  return rs_heal_batch_ex(ctx, k, m, batch, shards, lens, healed, status, 1);
 }
 
-int rs_codec_decode_heal(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
-                         uint8_t* out, int64_t original_size, uint8_t* healed) {
+int rs_codec_decode_heal_ex(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                            uint8_t* out, int64_t original_size, uint8_t* healed, int max_errors) {
   DeviceGuard dg;
   int rc = check_profile(k, m);
   if (rc) return rc;
-  if (!ctx || !shards || !lens || !healed || original_size < 0 || (original_size && !out)) return RS_E_ARG;
+  if (!ctx || !shards || !lens || !healed || original_size < 0 || (original_size && !out) || max_errors < 1)
+    return RS_E_ARG;
+  if ((rc = check_max_errors(max_errors))) return rc;
   const size_t n = static_cast<size_t>(k + m);
   std::fill(healed, healed + n, 0);
   const std::vector<size_t> lens0(lens, lens + n);
@@ -485,7 +511,7 @@ int rs_codec_decode_heal(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size
   // Verify failed: heal from the original presence, then join as rs_codec_decode does
   std::copy(lens0.begin(), lens0.end(), lens);
   int status = RS_OK;
-  rc = heal_batch_host(ctx, k, m, 1, shards, lens, healed, &status);
+  rc = heal_batch_host(ctx, k, m, max_errors, 1, shards, lens, healed, &status);
   if (rc) return rc;
   const size_t S = lens[0];
   if (static_cast<uint64_t>(S) * k < static_cast<uint64_t>(original_size)) return RS_E_INSUFFICIENT;
@@ -498,6 +524,11 @@ int rs_codec_decode_heal(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size
   }
   ctx->pool.run(segs);
   return RS_OK;
+}
+
+int rs_codec_decode_heal(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                         uint8_t* out, int64_t original_size, uint8_t* healed) {
+  return rs_codec_decode_heal_ex(ctx, k, m, shards, lens, out, original_size, healed, 1);
 }
 
 // ---- exported: batched host-memory calls ------------------------------------------------

@@ -314,9 +314,11 @@ constexpr int kOrderLocate = 8192;
 // Enqueues the launch group: rs_apply_locate over every mapped stripe's [0, size), tails and
 // misaligned shards as launch_ragged. Consecutive tile order, sliced like launch_ragged;
 // x.r.ntiles == 0 enqueues nothing. Counts accumulate from launch to launch. ev as for
-// launch_apply.
+// launch_apply. max_errors 2 (a pair plan, §5.12.1): rs_apply_locate2, with x.gf the
+// kLoc2GfBytes block, x.loc blocks of locate_stride(K, 2) bytes, and a column blamed on two
+// shards added into both shards' counts.
 hipError_t launch_locate(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
-                         LaunchEvents ev = {});
+                         LaunchEvents ev = {}, int max_errors = 1);
 
 // Tiles per slice of a sliced launch (launch_apply's rule) for `streams` shard streams.
 uint32_t launch_slice_tiles(int streams);

@@ -10,7 +10,8 @@
 // different shard sizes. Required launches (§5.10) are ragged launches that also read each
 // pattern's row count; one host function, launch_ragged, enqueues both. Locate launches
 // (§5.12) are required launches that compare every row and classify the mismatching byte
-// columns into per-stripe, per-shard counts.
+// columns into per-stripe, per-shard counts; the pair instances (§5.12.1) classify with
+// locate_classify2 and add a column blamed on two shards into both shards' counts.
 #include <algorithm>
 #include <array>
 
@@ -46,11 +47,9 @@ __device__ __forceinline__ void lds_xor_byte(typename LdsAcc<RT>::T& t, int r, u
   else t ^= b << (8 * r);
 }
 
-// One byte column's verdict from its syndromes, one per row in the accumulator element.
+// An accumulator element's syndromes, one per row, as the words the rule reads.
 template <int RT>
-__device__ __forceinline__ uint32_t locate_column(const typename LdsAcc<RT>::T& t, int rows, int K,
-                                                  const uint8_t* gf, const uint8_t* pt) {
-  uint32_t s[RT / 4];
+__device__ __forceinline__ void locate_words(const typename LdsAcc<RT>::T& t, uint32_t (&s)[RT / 4]) {
   if constexpr (RT > 8) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) s[i] = t.v[i];
@@ -60,13 +59,25 @@ __device__ __forceinline__ uint32_t locate_column(const typename LdsAcc<RT>::T& 
   } else {
     s[0] = t;
   }
-  return locate_classify(s, rows, K, gf, pt);
+}
+
+// One byte column's verdict from its syndromes, one per row in the accumulator element.
+// PAIR: by a pair plan's rule.
+template <int RT, bool PAIR>
+__device__ __forceinline__ uint32_t locate_column(const typename LdsAcc<RT>::T& t, int rows, int K,
+                                                  const uint8_t* gf, const uint8_t* pt) {
+  uint32_t s[RT / 4];
+  locate_words<RT>(t, s);
+  if constexpr (PAIR) return locate_classify2(s, rows, K, gf, pt);
+  else return locate_classify(s, rows, K, gf, pt);
 }
 
 // Adds every lane's n (0..16) columns of verdict v (kLocateClean: none) into the stripe's
 // bins: one 64-bit atomic per distinct verdict in the wave, issued by one lane. Sums are
 // formed from ballots alone, so lanes that have left the kernel count as nothing; every lane
-// still in the wave must arrive together (no barrier, no LDS).
+// still in the wave must arrive together (no barrier, no LDS). PAIR: a pair verdict's sum goes
+// into both shards' bins, by the same lane.
+template <bool PAIR>
 __device__ __forceinline__ void locate_wave_add(uint64_t* bins, uint32_t nbins, uint32_t v, uint32_t n) {
   uint64_t live = __ballot(v != kLocateClean);
   while (live) {  // wave-uniform
@@ -76,16 +87,24 @@ __device__ __forceinline__ void locate_wave_add(uint64_t* bins, uint32_t nbins, 
     uint32_t sum = 0;
 #pragma unroll
     for (int b = 0; b < 5; ++b) sum += static_cast<uint32_t>(__popcll(__ballot(mine && ((n >> b) & 1u)))) << b;
-    if ((threadIdx.x & 63u) == static_cast<uint32_t>(lead) && sum)
-      atomicAdd(reinterpret_cast<unsigned long long*>(bins + (lv == kLocateUnexplained ? nbins - 1 : lv)),
-                static_cast<unsigned long long>(sum));
+    if ((threadIdx.x & 63u) == static_cast<uint32_t>(lead) && sum) {
+      if (PAIR && locate_is_pair(lv)) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(bins + ((lv >> 8) & 0xffu)),
+                  static_cast<unsigned long long>(sum));
+        atomicAdd(reinterpret_cast<unsigned long long*>(bins + (lv & 0xffu)),
+                  static_cast<unsigned long long>(sum));
+      } else {
+        atomicAdd(reinterpret_cast<unsigned long long*>(bins + (lv == kLocateUnexplained ? nbins - 1 : lv)),
+                  static_cast<unsigned long long>(sum));
+      }
+    }
     live &= ~__ballot(mine);
   }
 }
 
 // The S % 16 tail of a locate launch: lds_tail with every row compared, and a mismatching
 // byte classified and counted. Every thread of the waves that call it reaches the ballots.
-template <int RT>
+template <int RT, bool PAIR>
 __device__ __forceinline__ void locate_tail(const ApplyArgs& a, const LocateArgs& x, cptr<const uint8_t*> in,
                                             cptr<uint8_t*> out, uint32_t stripe, uint32_t p,
                                             uint32_t lds0, uint32_t j) {
@@ -107,11 +126,11 @@ __device__ __forceinline__ void locate_tail(const ApplyArgs& a, const LocateArgs
 #pragma unroll
     for (int r = 0; r < RT; ++r)
       if (r < a.R) lds_xor_byte<RT>(t, r, out[r][b]);
-    v = locate_column<RT>(t, a.R, a.K, x.gf, x.loc + static_cast<size_t>(p) * x.loc_stride);
+    v = locate_column<RT, PAIR>(t, a.R, a.K, x.gf, x.loc + static_cast<size_t>(p) * x.loc_stride);
   }
   if (__ballot(v != kLocateClean) == 0) return;  // wave-uniform
   if (v != kLocateClean) atomicOr(a.status + static_cast<size_t>(stripe) * a.status_stride, 1);
-  locate_wave_add(x.counts + static_cast<size_t>(stripe) * x.nbins, x.nbins, v, v != kLocateClean ? 1u : 0u);
+  locate_wave_add<PAIR>(x.counts + static_cast<size_t>(stripe) * x.nbins, x.nbins, v, v != kLocateClean ? 1u : 0u);
 }
 
 // One tile of one stripe: the body every mixed and ragged block runs once it knows its
@@ -126,12 +145,15 @@ __device__ __forceinline__ void locate_tail(const ApplyArgs& a, const LocateArgs
 // that lane's accumulators into the rows' syndromes (the stored bytes XORed in, read again),
 // classifies its 16 byte columns with locate_classify and adds the columns per verdict into
 // lx->counts, one atomic per verdict and wave (locate_wave_add); nothing block-wide follows the
-// table prologue's barrier.
-template <int RT, class P, bool SOME = false, bool LOCATE = false>
+// table prologue's barrier. LOCATE 2 (the pair plans' kernel, §5.12.1): the same with
+// locate_classify2, in a loop over the 16 columns that is not unrolled, so that the kernel
+// holds one copy of the rule (unrolled 16 times the 16-row instance spilled its accumulators).
+// A lane that matches in every row runs none of it.
+template <int RT, class P, bool SOME = false, int LOCATE = 0>
 __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t stripe, uint32_t tile,
                                            uint32_t p, uint32_t tab_stride, uint32_t out_stride = 0,
                                            const LocateArgs* lx = nullptr) {
-  static_assert(!LOCATE || SOME, "a locate launch reads the patterns' row counts");
+  static_assert(LOCATE == 0 || SOME, "a locate launch reads the patterns' row counts");
   constexpr int BS = P::BS;
   constexpr int W = LdsAcc<RT>::W;
   static_assert(P::REALIGN == 0 && P::WIX == 0 && P::DMA == 0 && !P::NOMATH && !P::PERSIST && P::ORD == 0,
@@ -165,8 +187,8 @@ __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t
       reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*)smem));
   if (a.tail_in_vec) {
     const uint32_t j = tail_lane<BS>(a.tail_in_vec, tile);
-    if constexpr (LOCATE) {
-      if (j != ~0u) locate_tail<RT>(a, *lx, in, out, stripe, p, lds0, j);
+    if constexpr (LOCATE != 0) {
+      if (j != ~0u) locate_tail<RT, LOCATE == 2>(a, *lx, in, out, stripe, p, lds0, j);
     } else {
       if (j != ~0u) lds_tail<RT>(a, in, out, stripe, lds0, j);
     }
@@ -234,7 +256,7 @@ __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t
     }
   }
   if (bad) atomicOr(a.status + static_cast<size_t>(stripe) * a.status_stride, 1);
-  if constexpr (LOCATE) {
+  if constexpr (LOCATE != 0) {
     if (__ballot(bad) == 0) return;  // wave-uniform: the lanes still here stay together below
     if (bad) {
       // acc's byte r holds row r's computed byte: XORing the stored one in leaves the syndrome
@@ -256,21 +278,44 @@ __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t
     // a lane's columns almost always share one verdict: it keeps (verdict, columns) and the
     // wave adds a lane's run when its verdict changes, and every run at the end
     uint32_t run_v = kLocateClean, run_n = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t v = kLocateClean;
-        if (bad) v = locate_column<RT>(acc[w][j], R, K, lx->gf, pt);
-        const bool flush = v != kLocateClean && run_n != 0 && v != run_v;
-        if (__ballot(flush) != 0) locate_wave_add(bins, lx->nbins, flush ? run_v : kLocateClean, run_n);
-        if (flush) run_n = 0;
-        if (v != kLocateClean) {
-          run_v = v;
-          ++run_n;
-        }
+    auto note = [&](uint32_t v) {
+      const bool flush = v != kLocateClean && run_n != 0 && v != run_v;
+      if (__ballot(flush) != 0)
+        locate_wave_add<LOCATE == 2>(bins, lx->nbins, flush ? run_v : kLocateClean, run_n);
+      if (flush) run_n = 0;
+      if (v != kLocateClean) {
+        run_v = v;
+        ++run_n;
       }
-    locate_wave_add(bins, lx->nbins, run_n ? run_v : kLocateClean, run_n);
+    };
+    if constexpr (LOCATE == 2) {
+      // one copy of the rule: the column index is wave-uniform and the column's syndromes are
+      // picked out of the accumulators with selects, so the accumulators stay in registers
+#pragma unroll 1
+      for (int c = 0; c < 16; ++c) {
+        uint32_t v = kLocateClean;
+        if (bad) {
+          AccT t = acc[0][0];
+#pragma unroll
+          for (int w = 0; w < 4; ++w)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (c == w * 4 + j) t = acc[w][j];
+          v = locate_column<RT, true>(t, R, K, lx->gf, pt);
+        }
+        note(v);
+      }
+    } else {
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          uint32_t v = kLocateClean;
+          if (bad) v = locate_column<RT, false>(acc[w][j], R, K, lx->gf, pt);
+          note(v);
+        }
+    }
+    locate_wave_add<LOCATE == 2>(bins, lx->nbins, run_n ? run_v : kLocateClean, run_n);
   }
 }
 
@@ -359,7 +404,28 @@ void rs_apply_locate(ApplyArgs a, LocateArgs xl) {
   a.verify_mask = as_const(x.vmask)[p];
   const uint32_t stride = static_cast<uint32_t>(a.R);
   a.R = static_cast<int>(as_const(xl.nrows)[p]);
-  mixed_tile<RT, P, true, true>(a, smem, stripe, tile, p, x.tab_stride, stride, &xl);
+  mixed_tile<RT, P, true, 1>(a, smem, stripe, tile, p, x.tab_stride, stride, &xl);
+}
+
+// Pair locate launches: rs_apply_locate with locate_classify2 on the slow
+// path. xl.gf and xl.loc are a pair plan's blocks (kLoc2GfBytes, locate_stride(K, 2)).
+template <int RT, class P>
+__global__ __launch_bounds__(P::BS) __attribute__((amdgpu_waves_per_eu(P::WPE, lds_max_waves<RT>())))
+void rs_apply_locate2(ApplyArgs a, LocateArgs xl) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  static_assert(P::TILE_VECS == P::BS, "one vector per thread: the tile map counts 512-vector tiles");
+  const RaggedArgs& x = xl.r;
+  const uint32_t t = a.t_base + blockIdx.x;
+  if (t >= x.ntiles) return;  // block-uniform
+  const uint32_t stripe = as_const(x.tile_stripe)[t];
+  const uint32_t tile = t - as_const(x.tile0)[stripe];
+  const uint32_t p = as_const(x.pat)[stripe];
+  a.S = as_const(x.size)[stripe];
+  a.nvec = a.S / 16;
+  a.verify_mask = as_const(x.vmask)[p];
+  const uint32_t stride = static_cast<uint32_t>(a.R);
+  a.R = static_cast<int>(as_const(xl.nrows)[p]);
+  mixed_tile<RT, P, true, 2>(a, smem, stripe, tile, p, x.tab_stride, stride, &xl);
 }
 
 // S < 16: one byte position per thread, 16 threads per stripe; the nibble tables are read
@@ -417,6 +483,9 @@ using LocateFn = void (*)(ApplyArgs, LocateArgs);
 const std::array<LocateFn, 3> kLocate = {&dev::rs_apply_locate<4, dev::MixedPolicy<4>>,
                                          &dev::rs_apply_locate<8, dev::MixedPolicy<8>>,
                                          &dev::rs_apply_locate<16, dev::MixedPolicy<16>>};
+const std::array<LocateFn, 3> kLocate2 = {&dev::rs_apply_locate2<4, dev::MixedPolicy<4>>,
+                                          &dev::rs_apply_locate2<8, dev::MixedPolicy<8>>,
+                                          &dev::rs_apply_locate2<16, dev::MixedPolicy<16>>};
 static_assert(dev::MixedPolicy<4>::BS == 512 && dev::MixedPolicy<8>::BS == 512 &&
                   dev::MixedPolicy<16>::BS == 512 && dev::MixedPolicy<4>::TILE_VECS == 512 &&
                   dev::MixedPolicy<8>::TILE_VECS == 512 && dev::MixedPolicy<16>::TILE_VECS == 512,
@@ -434,11 +503,12 @@ const std::array<std::array<UpdateFn, 3>, 2> kUpdate = {{
 
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
 // per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one, 2 the
-// required one, 3 the single-source update instance, 4 the pair one, 5 the locate one)
+// required one, 3 the single-source update instance, 4 the pair one, 5 the locate one, 6 the
+// pair locate one)
 DeviceOnce g_mixed_wide_lds;
 
 // The vector launch every kind shares: the dynamic-LDS opt-in (`once_key`: 0 the mixed
-// instance, 1 the ragged one, 2 the required one, 3 and 4 the update ones, 5 the locate one),
+// instance, 1 the ragged one, 2 the required one, 3 and 4 the update ones, 5 and 6 the locate ones),
 // then `grid` tiles
 // in equal consecutive slices of `streams` shard streams, as launch_apply cuts them. A slice
 // boundary may fall inside a stripe (tiles are numbered over the whole grid).
@@ -503,18 +573,21 @@ hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, const uint32_t* nrows
 }
 
 hipError_t launch_locate(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
-                         LaunchEvents ev) {
+                         LaunchEvents ev, int max_errors) {
   const RaggedArgs& r = x.r;
   if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
       !r.pat || !r.vmask || !r.size || !r.tile0 || !a.in_tab || !a.out_tab || !a.status ||
       r.ntiles > 0x7fffffffu || (r.ntiles && !r.tile_stripe) || !x.nrows || !x.gf || !x.loc ||
-      !x.counts || x.loc_stride != locate_stride(a.K) || x.nbins < 2)
+      !x.counts || max_errors < 1 || max_errors > 2 || x.loc_stride != locate_stride(a.K, max_errors) ||
+      x.nbins < 2)
     return hipErrorInvalidValue;
   if (r.ntiles == 0) return hipSuccess;  // no stripe has a row
   a.t_base = 0;
   a.S = a.nvec = 0;  // per stripe, read by the kernel
   a.tail_in_vec = any_tail ? 1u : 0u;  // wave 0 of each stripe's first tile
-  return launch_tiles(kLocate[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 5, r.ntiles, a, x, a.K + a.R, stream, ev);
+  const int inst = a.R > 8 ? 2 : a.R > 4 ? 1 : 0;
+  return max_errors == 2 ? launch_tiles(kLocate2[inst], 6, r.ntiles, a, x, a.K + a.R, stream, ev)
+                         : launch_tiles(kLocate[inst], 5, r.ntiles, a, x, a.K + a.R, stream, ev);
 }
 
 hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_tail,

@@ -43,6 +43,7 @@ struct MixedPlan {
   std::vector<Group> groups;  // per launch group of `t`
   // a locate plan's pieces: locate_tables.hpp's blocks and the batch * (k + m + 1) counts
   size_t gf_off = 0, loc_off = 0, loc_stride = 0, counts_off = 0;
+  int max_errors = 1;  // 2: a pair plan (rs_plan_create_locate_ex)
 };
 
 // An update plan (rs_plan_create_update): where the pieces of
@@ -191,7 +192,7 @@ hipError_t plan_launch(const rs_plan& plan, hipStream_t s, const std::vector<int
       const LocateArgs x{r, nrows, d + mp.gf_off, d + mp.loc_off,
                          reinterpret_cast<uint64_t*>(d + mp.counts_off),
                          static_cast<uint32_t>(mp.loc_stride), static_cast<uint32_t>(mp.t.k + mp.t.m + 1)};
-      e = launch_locate(a, x, mp.groups[gi].any_tail, s, g);
+      e = launch_locate(a, x, mp.groups[gi].any_tail, s, g, mp.max_errors);
     } else {
       e = launch_ragged(a, r, nrows, mp.groups[gi].any_tail, s, g);
     }
@@ -331,6 +332,7 @@ int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rt,
   if (lt) {
     mp.gf_off = pk.take(lt->gf.size());
     mp.loc_stride = lt->stride;
+    mp.max_errors = lt->max_errors;
     mp.loc_off = pk.take(std::max<size_t>(1, lt->loc.size()));
     mp.counts_off = pk.take(sizeof(uint64_t) * static_cast<size_t>(batch) * (n + 1));
   }
@@ -388,12 +390,12 @@ int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rt,
 // required count for ragged and required plans, S for a mixed one.
 int create_tabled(rs_ctx* ctx, int device, int k, int m, PlanKind kind, size_t S, int batch,
                   const size_t* sizes, const uint8_t* present, const uint8_t* required,
-                  uint8_t* const* shards, rs_plan** out) {
+                  uint8_t* const* shards, rs_plan** out, int max_errors = 1) {
   if (!ctx->device(device)) return RS_E_ARG;
   const bool sized = kind != PlanKind::kMixed;
   LocateTables lt;
   RaggedTables& rt = lt.ragged;
-  if (const int rc = table_status(kind == PlanKind::kLocate ? build_locate_tables(k, m, batch, sizes, present, lt)
+  if (const int rc = table_status(kind == PlanKind::kLocate ? build_locate_tables(k, m, batch, sizes, present, lt, max_errors)
                                   : sized ? build_ragged_tables(k, m, batch, sizes, present, required, rt)
                                           : build_mixed_tables(k, m, batch, present, nullptr, rt.mixed)))
     return rc;
@@ -528,8 +530,15 @@ int rs_plan_create_required(rs_ctx* ctx, int device, int k, int m, int batch, co
 
 int rs_plan_create_locate(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
                           const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
+  return rs_plan_create_locate_ex(ctx, device, k, m, batch, sizes, present, shards, 1, out);
+}
+
+int rs_plan_create_locate_ex(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                             const uint8_t* present, uint8_t* const* shards, int max_errors,
+                             rs_plan** out) {
   DeviceGuard dg;
-  int rc = check_plan_args(ctx, k, m, batch, sizes && shards, out);
+  int rc = check_plan_args(ctx, k, m, batch, sizes && shards && max_errors >= 1, out);
+  if (!rc && max_errors > 2) rc = RS_E_UNSUPPORTED;
   if (!rc) rc = check_stripes(k, k + m, batch, sizes, nullptr);
   if (rc) return rc;
   // no masks: every shard of every stripe is present
@@ -539,7 +548,8 @@ int rs_plan_create_locate(rs_ctx* ctx, int device, int k, int m, int batch, cons
     present = all.data();
   }
   // (no route to a simpler plan: only this kind counts)
-  return create_tabled(ctx, device, k, m, PlanKind::kLocate, 0, batch, sizes, present, nullptr, shards, out);
+  return create_tabled(ctx, device, k, m, PlanKind::kLocate, 0, batch, sizes, present, nullptr, shards, out,
+                       max_errors);
 }
 
 int rs_plan_create_update(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,

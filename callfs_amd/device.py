@@ -304,21 +304,26 @@ class Plan:
 
     @classmethod
     def for_ragged(cls, rb: "RaggedBatch", present=None, context=None, required=None,
-                   locate: bool = False) -> "Plan":
+                   locate: bool = False, max_errors: int = 1) -> "Plan":
         dev = rb.device.index if rb.device.index is not None else 0
         if locate:
             if required is not None:
                 raise ValueError("a locate plan writes nothing: no required set")
-            return cls.locate(rb.k, rb.m, rb.sizes, rb.pointers(), present, dev, context)
+            return cls.locate(rb.k, rb.m, rb.sizes, rb.pointers(), present, dev, context, max_errors)
+        if max_errors != 1:
+            raise ValueError("max_errors belongs to a locate plan")
         return cls.ragged(rb.k, rb.m, rb.sizes, rb.pointers(), present, dev, context, required)
 
     @classmethod
     def locate(cls, k: int, m: int, sizes: Sequence[int], pointers: Sequence[int],
-               present=None, device: int = 0, context: Optional[N.Context] = None) -> "Plan":
-        """rs_plan_create_locate: a plan that writes nothing and tells which
-        shard of a stripe is corrupt. present: None (every shard present) or batch rows of k+m
-        flags. A launch compares each stripe's present shards beyond the first k (16 at the
-        most) and classifies every mismatching byte column; `blame()` reads the counts."""
+               present=None, device: int = 0, context: Optional[N.Context] = None,
+               max_errors: int = 1) -> "Plan":
+        """rs_plan_create_locate(_ex): a plan that writes nothing and tells
+        which shard of a stripe is corrupt. present: None (every shard present) or batch rows of
+        k+m flags. A launch compares each stripe's present shards beyond the first k (16 at the
+        most) and classifies every mismatching byte column; `blame()` reads the counts.
+        max_errors=2 (§5.12.1): a stripe that compares four or more shards also names the two
+        shards of a column in which two are corrupt; such a column counts once for each."""
         n, batch = k + m, len(sizes)
         if len(pointers) != batch * n:
             raise ValueError("need batch*(k+m) shard pointers")
@@ -336,15 +341,21 @@ class Plan:
         ptrs = (ctypes.c_void_p * max(1, len(pointers)))(*pointers)
         szs = (ctypes.c_size_t * max(1, batch))(*self.sizes)
         h = ctypes.c_void_p()
-        N.check(N.lib.rs_plan_create_locate(self.ctx.handle, device, k, m, batch, szs, pres, ptrs,
-                                            ctypes.byref(h)), "rs_plan_create_locate")
+        if max_errors == 1:
+            N.check(N.lib.rs_plan_create_locate(self.ctx.handle, device, k, m, batch, szs, pres, ptrs,
+                                                ctypes.byref(h)), "rs_plan_create_locate")
+        else:
+            N.check(N.lib.rs_plan_create_locate_ex(self.ctx.handle, device, k, m, batch, szs, pres, ptrs,
+                                                   int(max_errors), ctypes.byref(h)),
+                    "rs_plan_create_locate_ex")
         self.handle = h
         return self
 
     def blame(self, stream: Optional[torch.cuda.Stream] = None):
         """rs_plan_blame of a locate plan: synchronises the stream and returns a
         (batch, k+m+1) uint64 array: [b, i] = byte columns of stripe b blamed on shard i,
-        [b, k+m] = its unexplained columns. Clears the counts; launches accumulate until the
+        [b, k+m] = its unexplained columns (a pair plan counts a column blamed on two shards
+        once for each). Clears the counts; launches accumulate until the
         next read, so two launches before one read give every count doubled."""
         import numpy as np
         s = stream if stream is not None else torch.cuda.current_stream(self.device)

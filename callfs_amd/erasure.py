@@ -115,6 +115,15 @@ def _wrapped(rc: int, prefix: str) -> Exception:
     return cls(f"{prefix}: {cls.text}")
 
 
+def _check_max_errors(max_errors: int, call: str) -> None:
+    """The _ex calls' own argument, with their codes: below 1 RS_E_ARG,
+    above 2 RS_E_UNSUPPORTED."""
+    if max_errors < 1:
+        raise N.NativeError(N.RS_E_ARG, call)
+    if max_errors > 2:
+        raise N.NativeError(N.RS_E_UNSUPPORTED, call)
+
+
 def _decode_error(rc: int) -> Exception:
     """What Codec.decode raises for a nonzero code of rs_codec_decode (codec.go:45-78)."""
     if rc == N.RS_E_CORRUPT:
@@ -253,18 +262,21 @@ class Codec:
         raise _decode_error(rc)
 
     def decode_heal(self, shards: List, profile: ErasureProfile,
-                    original_size: int) -> Tuple[bytearray, List[int]]:
+                    original_size: int, max_errors: int = 1) -> Tuple[bytearray, List[int]]:
         """rs_codec_decode_heal: decode() that repairs what it can where
         decode() raises ErrShardCorrupted. The corrupt shards are located from the parity
         syndromes; when they explain every mismatching column and a compared shard is left
         to confirm with, they are rebuilt in place (writable buffers) with the missing ones.
-        Returns (data, healed shard indices); every other error is decode()'s."""
+        Returns (data, healed shard indices); every other error is decode()'s.
+        max_errors=2 (rs_codec_decode_heal_ex, §5.12.1) also heals two shards that are
+        corrupt in the same byte columns, where four or more shards are compared."""
         k, m = profile.data_shards, profile.parity_shards
         if k < 1 or m < 1:
             raise ErrInvalidProfile()
         n = k + m
         if k + m > 256:
             raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create decoder")
+        _check_max_errors(max_errors, "rs_codec_decode_heal_ex")
         if len(shards) != n:
             raise ErrTooFewShards(f"erasure: reconstruction failed: {ErrTooFewShards.text}")
         lens = (ctypes.c_size_t * n)()
@@ -281,8 +293,9 @@ class Codec:
                                       for b in bufs])
         out = bytearray(max(int(original_size), 0))
         healed = (ctypes.c_uint8 * n)()
-        rc = N.lib.rs_codec_decode_heal(self.context.handle, k, m, ptrs, lens,
-                                        _addr(out) if out else None, int(original_size), healed)
+        rc = N.lib.rs_codec_decode_heal_ex(self.context.handle, k, m, ptrs, lens,
+                                           _addr(out) if out else None, int(original_size), healed,
+                                           int(max_errors))
         if rc in (N.RS_OK, N.RS_E_CORRUPT, N.RS_E_INSUFFICIENT):
             for i in range(n):
                 if (shards[i] is None or len(shards[i]) == 0) and lens[i]:
@@ -667,29 +680,36 @@ def _per_stripe(rc: int, status: Sequence[int], what: str) -> None:
         N.check(rc, what)
 
 
-def locate(shards: List, k: int, m: int, context: Optional[N.Context] = None) -> np.ndarray:
+def locate(shards: List, k: int, m: int, context: Optional[N.Context] = None,
+           max_errors: int = 1) -> np.ndarray:
     """rs_locate: which shard of a stripe is corrupt. shards: an n-list
     (None / empty = missing); nothing is written. Returns k+m+1 uint64 counts: [i] = byte
     columns blamed on shard i, [k+m] = columns that mismatch but that no single shard
-    explains. All zero for a clean stripe (and for one with exactly k shards present)."""
+    explains. All zero for a clean stripe (and for one with exactly k shards present).
+    max_errors=2 (rs_locate_ex, §5.12.1): a column in which two shards are corrupt counts once
+    for each of the two, where the stripe compares four or more shards."""
+    _check_max_errors(max_errors, "rs_locate_ex")
     ctx = context or N.default_context()
     n = k + m
     if len(shards) != n:
         raise ErrTooFewShards()
     lens = (ctypes.c_size_t * n)(*[0 if s is None else len(s) for s in shards])
     counts = np.zeros(n + 1, dtype=np.uint64)
-    rc = N.lib.rs_locate(ctx.handle, k, m, _shard_ptrs(shards), lens,
-                         counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+    rc = N.lib.rs_locate_ex(ctx.handle, k, m, _shard_ptrs(shards), lens,
+                            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(max_errors))
     if rc not in (N.RS_OK, N.RS_E_CORRUPT):
         raise _wrapped(rc, "locate")
     return counts
 
 
 def locate_batch(stripes: Sequence[Sequence], k: int, m: int,
-                 context: Optional[N.Context] = None) -> Tuple[np.ndarray, List[int]]:
+                 context: Optional[N.Context] = None,
+                 max_errors: int = 1) -> Tuple[np.ndarray, List[int]]:
     """rs_locate_batch: locate() for many stripes of any sizes and erasures in one call.
     Returns (counts, a (batch, k+m+1) uint64 array; status[b]: RS_OK, RS_E_CORRUPT where a
-    column mismatched, or the stripe's own error as reconstruct_batch reports it)."""
+    column mismatched, or the stripe's own error as reconstruct_batch reports it).
+    max_errors as for locate() (rs_locate_batch_ex)."""
+    _check_max_errors(max_errors, "rs_locate_batch_ex")
     ctx = context or N.default_context()
     n = k + m
     B = len(stripes)
@@ -698,20 +718,25 @@ def locate_batch(stripes: Sequence[Sequence], k: int, m: int,
     lens = (ctypes.c_size_t * max(B * n, 1))(*[0 if s is None else len(s) for st in stripes for s in st])
     counts = np.zeros((B, n + 1), dtype=np.uint64)
     status = (ctypes.c_int * max(B, 1))()
-    rc = N.lib.rs_locate_batch(ctx.handle, k, m, B, _shard_ptrs([s for st in stripes for s in st] or [None]),
-                               lens, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), status)
+    rc = N.lib.rs_locate_batch_ex(ctx.handle, k, m, B, _shard_ptrs([s for st in stripes for s in st] or [None]),
+                                  lens, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), status,
+                                  int(max_errors))
     out = list(status)[:B]
     _per_stripe(rc, out, "rs_locate_batch")
     return counts, out
 
 
 def heal_batch(stripes: List[List], k: int, m: int,
-               context: Optional[N.Context] = None) -> Tuple[List[int], List[List[int]]]:
+               context: Optional[N.Context] = None,
+               max_errors: int = 1) -> Tuple[List[int], List[List[int]]]:
     """rs_heal_batch: reconstruct_batch(verify=True) that repairs what it can. A stripe whose
     compared shards mismatch is located; when the blamed shards explain every mismatching
     column and a compared shard is left to confirm with, they are rebuilt in place (writable
     buffers) together with the missing ones and the stripe verified again. Returns
-    (status[b], healed[b] = indices of the shards rebuilt because they were corrupt)."""
+    (status[b], healed[b] = indices of the shards rebuilt because they were corrupt).
+    max_errors=2 (rs_heal_batch_ex, §5.12.1) also heals shards that are corrupt in the same
+    byte columns, two per column, where four or more shards are compared."""
+    _check_max_errors(max_errors, "rs_heal_batch_ex")
     ctx = context or N.default_context()
     n = k + m
     B = len(stripes)
@@ -732,7 +757,8 @@ def heal_batch(stripes: List[List], k: int, m: int,
         flat += cp
     status = (ctypes.c_int * max(B, 1))()
     healed = (ctypes.c_uint8 * max(B * n, 1))()
-    rc = N.lib.rs_heal_batch(ctx.handle, k, m, B, _shard_ptrs(flat or [None]), lens, healed, status)
+    rc = N.lib.rs_heal_batch_ex(ctx.handle, k, m, B, _shard_ptrs(flat or [None]), lens, healed, status,
+                                int(max_errors))
     out = list(status)[:B]
     _per_stripe(rc, out, "rs_heal_batch")
     for b, st in enumerate(stripes):

@@ -157,6 +157,36 @@ func (c *Codec) DecodeHeal(shards [][]byte, profile ErasureProfile, originalSize
 	return out, nil, err
 }
 
+// ErrMaxErrors is what the ...Max calls report for maxErrors outside 1..2.
+var ErrMaxErrors = errors.New("erasure: maxErrors must be 1 or 2")
+
+// LocateMax, HealBatchMax and DecodeHealMax are Locate, HealBatch and DecodeHeal on builds
+// without the GPU codec, whatever the maximum: nothing is located or healed.
+func (c *Codec) LocateMax(shards [][]byte, profile ErasureProfile, maxErrors int) ([]uint64, error) {
+	if maxErrors < 1 || maxErrors > 2 {
+		return nil, ErrMaxErrors
+	}
+	return c.Locate(shards, profile)
+}
+
+func (c *Codec) HealBatchMax(objs [][][]byte, profile ErasureProfile, maxErrors int) ([][]int, []error) {
+	if maxErrors < 1 || maxErrors > 2 {
+		errs := make([]error, len(objs))
+		for b := range errs {
+			errs[b] = ErrMaxErrors
+		}
+		return make([][]int, len(objs)), errs
+	}
+	return c.HealBatch(objs, profile)
+}
+
+func (c *Codec) DecodeHealMax(shards [][]byte, profile ErasureProfile, originalSize int64, maxErrors int) ([]byte, []int, error) {
+	if maxErrors < 1 || maxErrors > 2 {
+		return nil, nil, ErrMaxErrors
+	}
+	return c.DecodeHeal(shards, profile, originalSize)
+}
+
 // Overwrite replaces object bytes [offset, offset+len(data)) in the data shards and updates
 // the affected parity columns with upstream Update, on builds without the GPU codec.
 func (c *Codec) Overwrite(shards [][]byte, profile ErasureProfile, offset int64, data []byte) error {

@@ -4,6 +4,9 @@
 // syndromes alone, and a Decode that repairs what they name. Not in the reference API: the
 // reference finds a bad shard by hashing every shard against the metadata
 // (manager.go:250-320); these calls need no checksum and cost one more pass over the shards.
+// The ...Max variants (§5.12.1) take the number of corrupt shards a byte column may be blamed
+// on: 1 is the plain call, 2 also names two shards that are corrupt in the same columns where
+// four or more shards are compared.
 package erasure
 
 /*
@@ -42,6 +45,19 @@ func pinShards(pin *runtime.Pinner, ptrs cArray, lens []C.size_t, at int, shards
 // present has nothing to compare and reports zeros. A scrub calls it (or HealBatch) per
 // object instead of hashing every shard.
 func (c *Codec) Locate(shards [][]byte, profile ErasureProfile) ([]uint64, error) {
+	return c.LocateMax(shards, profile, 1)
+}
+
+// ErrMaxErrors is what the ...Max calls report for maxErrors outside 1..2.
+var ErrMaxErrors = errors.New("erasure: maxErrors must be 1 or 2")
+
+// LocateMax is Locate with maxErrors corrupt shards per byte column (rs_locate_ex). With 2, a
+// column in which two shards are corrupt counts once for each of the two, so the counts may add
+// up to more than the shard size.
+func (c *Codec) LocateMax(shards [][]byte, profile ErasureProfile, maxErrors int) ([]uint64, error) {
+	if maxErrors < 1 || maxErrors > 2 {
+		return nil, ErrMaxErrors
+	}
 	k, m := profile.DataShards, profile.ParityShards
 	if k < 1 || m < 1 {
 		return nil, ErrInvalidProfile
@@ -60,7 +76,7 @@ func (c *Codec) Locate(shards [][]byte, profile ErasureProfile) ([]uint64, error
 	var pin runtime.Pinner
 	defer pin.Unpin()
 	pinShards(&pin, ptrs, lens, 0, shards)
-	rc := C.rs_locate(gpuCtx, C.int(k), C.int(m), ptrs.at(0), &lens[0], &counts[0])
+	rc := C.rs_locate_ex(gpuCtx, C.int(k), C.int(m), ptrs.at(0), &lens[0], &counts[0], C.int(maxErrors))
 	if rc != C.RS_OK && rc != C.RS_E_CORRUPT { // RS_E_CORRUPT: the counts say where
 		return nil, decodeErr(rc)
 	}
@@ -79,9 +95,22 @@ func (c *Codec) Locate(shards [][]byte, profile ErasureProfile) ([]uint64, error
 // shard indices of object b that were corrupt and have been rewritten (the caller stores them
 // back). Present shards that nobody blamed are never written.
 func (c *Codec) HealBatch(objs [][][]byte, profile ErasureProfile) (healed [][]int, errs []error) {
+	return c.HealBatchMax(objs, profile, 1)
+}
+
+// HealBatchMax is HealBatch with maxErrors corrupt shards per byte column (rs_heal_batch_ex):
+// with 2 it also heals shards that are corrupt in the same columns, two per column, as long as
+// a compared shard is left to confirm with.
+func (c *Codec) HealBatchMax(objs [][][]byte, profile ErasureProfile, maxErrors int) (healed [][]int, errs []error) {
 	k, m := profile.DataShards, profile.ParityShards
 	errs = make([]error, len(objs))
 	healed = make([][]int, len(objs))
+	if maxErrors < 1 || maxErrors > 2 {
+		for b := range errs {
+			errs[b] = ErrMaxErrors
+		}
+		return healed, errs
+	}
 	if k < 1 || m < 1 {
 		for b := range errs {
 			errs[b] = ErrInvalidProfile
@@ -129,8 +158,8 @@ func (c *Codec) HealBatch(objs [][][]byte, profile ErasureProfile) (healed [][]i
 			}
 		}
 	}
-	rc := C.rs_heal_batch(gpuCtx, C.int(k), C.int(m), C.int(len(objs)), ptrs.at(0), &lens[0],
-		&flags[0], &status[0])
+	rc := C.rs_heal_batch_ex(gpuCtx, C.int(k), C.int(m), C.int(len(objs)), ptrs.at(0), &lens[0],
+		&flags[0], &status[0], C.int(maxErrors))
 	if rc != C.RS_OK && !hasStatus(status, rc) { // a call-level error
 		for b := range errs {
 			if errs[b] == nil {
@@ -167,6 +196,15 @@ func (c *Codec) HealBatch(objs [][][]byte, profile ErasureProfile) (healed [][]i
 // CALLFS_ERASURE__GPU_MIN_BYTES, k+m > 256, no device) are decoded by the CPU codec, which
 // heals nothing.
 func (c *Codec) DecodeHeal(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, []int, error) {
+	return c.DecodeHealMax(shards, profile, originalSize, 1)
+}
+
+// DecodeHealMax is DecodeHeal with maxErrors corrupt shards per byte column
+// (rs_codec_decode_heal_ex).
+func (c *Codec) DecodeHealMax(shards [][]byte, profile ErasureProfile, originalSize int64, maxErrors int) ([]byte, []int, error) {
+	if maxErrors < 1 || maxErrors > 2 {
+		return nil, nil, ErrMaxErrors
+	}
 	k, m := profile.DataShards, profile.ParityShards
 	if k < 1 || m < 1 {
 		return nil, nil, ErrInvalidProfile
@@ -218,8 +256,8 @@ func (c *Codec) DecodeHeal(shards [][]byte, profile ErasureProfile, originalSize
 		pin.Pin(&buf[0])
 		out = (*C.uint8_t)(unsafe.Pointer(&buf[0]))
 	}
-	rc := C.rs_codec_decode_heal(gpuCtx, C.int(k), C.int(m), ptrs.at(0), &lens[0], out,
-		C.int64_t(originalSize), &flags[0])
+	rc := C.rs_codec_decode_heal_ex(gpuCtx, C.int(k), C.int(m), ptrs.at(0), &lens[0], out,
+		C.int64_t(originalSize), &flags[0], C.int(maxErrors))
 	switch rc {
 	case C.RS_OK, C.RS_E_CORRUPT, C.RS_E_INSUFFICIENT: // Reconstruct ran: the nil entries are filled
 		for i := range shards {

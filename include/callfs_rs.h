@@ -587,6 +587,37 @@ int rs_heal_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards, 
 int rs_codec_decode_heal(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
                          uint8_t* out, int64_t original_size, uint8_t* healed);
 
+/* ---- two corrupt shards per byte column ----------------------------
+ * The _ex calls are their siblings above with one more argument, max_errors: how many corrupt
+ * shards a byte column may be blamed on.
+ *   max_errors == 1: exactly the sibling (which is this call with 1);
+ *   max_errors == 2: a pair plan. A pattern that compares r' >= 4 shards also explains a column
+ *     in which two of the k + r' examined shards are corrupt: the column counts once for EACH of
+ *     the two shards, so a stripe's counts may add up to more than its columns. Columns with one
+ *     corrupt byte get exactly the verdict of max_errors == 1. For e corrupt examined bytes in a
+ *     column: e = 2 is blamed on exactly those two shards; 3 <= e <= r'-2 is unexplained (an
+ *     empty range at r' = 4); e >= r'-1 may be misattributed or look clean -- at r' = 4 that
+ *     starts at three errors, which max_errors == 1 still reports as unexplained. Patterns
+ *     with r' < 4 behave as with max_errors == 1.
+ *   max_errors < 1 returns RS_E_ARG (with the NULL and count checks), max_errors > 2
+ *   RS_E_UNSUPPORTED (after them); both before any device work.
+ * rs_plan_blame, the counts layout (k+m+1 words per stripe), rs_plan_forms (RS_ORDER_LOCATE +
+ * RS_ORDER_CONSECUTIVE) and every other plan call are unchanged. The heal rule is unchanged
+ * too: B = the shards with a nonzero count, and a stripe is healed when nothing is unexplained,
+ * B is not empty and present - |B| >= k + 1; the second verify stays the backstop against a
+ * misattributed column. */
+int rs_plan_create_locate_ex(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                             const uint8_t* present, uint8_t* const* shards, int max_errors,
+                             rs_plan** out);
+int rs_locate_ex(rs_ctx* ctx, int k, int m, const uint8_t* const* shards, const size_t* lens,
+                 uint64_t* counts, int max_errors);
+int rs_locate_batch_ex(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* shards,
+                       const size_t* lens, uint64_t* counts, int* status, int max_errors);
+int rs_heal_batch_ex(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards, size_t* lens,
+                     uint8_t* healed, int* status, int max_errors);
+int rs_codec_decode_heal_ex(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                            uint8_t* out, int64_t original_size, uint8_t* healed, int max_errors);
+
 /* ---- ShardChecksum on device-resident shards (codec.go:81-84; §8(f) of SURVEY.md) ----
  * SHA-256 of `count` messages already in HBM, one digest per message written to
  * `digests` (device memory, 32*count bytes, FIPS 180-4 byte order — hex-encode it for

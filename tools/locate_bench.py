@@ -10,14 +10,21 @@ stripe fully present and consistent:
                stripe is classified);
   (d) sha256   what finding the shard costs without locate: rs_sha256_dev's kernel over all
                shards of the batch (a hash plan's launch between two stream events).
+Pair plans (max_errors = 2), same batch, same process, same rounds:
+  (b2) clean2  the pair plan on clean data;
+  (c2) pair_valid   two of the k read shards of every stripe wholly corrupt (the same columns);
+  (c3) pair_mixed   one read shard and one compared shard of every stripe wholly corrupt;
+  (c4) single2      the pair plan over (c) valid's batch: every column has a single error.
 Workloads: `rs10_4` RS(10,4), 256 stripes, sizes log-uniform in 64 KiB..4 MiB; `rs16_4`
 RS(16,4), 4,096 stripes, sizes uniform in 1..16 KiB (the §5.9 workloads).
 (a)-(c) are timed with rs_plan_launch_timed events over `--reps` launches, the median counts;
-the variants are interleaved over `--rounds` rounds, (a) and (b) in alternating order. Which
-of the two runs first in a round (right after the previous round's SHA-256 pass) matters more
-than which it is, so b/a is also reported per position: first against first, second against
-second. Prints one JSON line per workload: median microseconds, GB/s of algorithmic bytes,
-the ratios b/a, c/a and d/c, and the counts check of (c).
+the variants are interleaved over `--rounds` rounds, (a), (b) and (b2) in rotating order. Which
+of them runs first in a round (right after the previous round's SHA-256 pass) matters more
+than which it is, so b/a, b2/a and b2/b are also reported per position: first against first
+and so on (use a multiple of 3 rounds). (c2)-(c4) follow (c) in every round and are reported
+against (c) valid of the same round, the median of the per-round ratios. Prints one JSON line
+per workload: median microseconds, GB/s of algorithmic bytes, the ratios b/a, c/a and d/c, the
+pair plan's ratios, and the counts checks of (c) and of (c2)-(c4).
 usage: python tools/locate_bench.py [--workload rs10_4] [--workload rs16_4]
 """
 import argparse
@@ -68,11 +75,15 @@ def main():
         every = [[True] * n] * B
         verify = Plan.ragged(k, m, sizes, ptrs, present=every, required=[[False] * n] * B)
         locate = Plan.locate(k, m, sizes, ptrs)
+        locate2 = Plan.locate(k, m, sizes, ptrs, max_errors=2)
         hashes = HashPlan(ptrs, [S for S in sizes for _ in range(n)])
         digests = torch.empty(32 * B * n, dtype=torch.uint8, device=dev)
         rng = np.random.default_rng(a.seed)
         which = {"valid": [int(x) for x in rng.integers(0, k, B)],
                  "compared": [int(x) for x in rng.integers(k, n, B)]}
+        # a second read shard, never the first one (k = 1 has none: its pair is read + compared)
+        which["valid_b"] = [(i + 1 + int(x)) % k if k > 1 else k
+                            for i, x in zip(which["valid"], rng.integers(0, max(k - 1, 1), B))]
 
         def flip(shards):
             for b, i in enumerate(shards):
@@ -85,20 +96,28 @@ def main():
             hashes.launch(digests, stream)
             e1.record(stream)
 
-        plans = {"verify": verify, "clean": locate, "valid": locate, "compared": locate}
+        plans = {"verify": verify, "clean": locate, "valid": locate, "compared": locate,
+                 "clean2": locate2, "pair_valid": locate2, "pair_mixed": locate2, "single2": locate2}
         fns = {v: (lambda e0, e1, p=p: p.launch(stream, events=(e0, e1))) for v, p in plans.items()}
         fns["sha256"] = sha
-        for v in ("verify", "clean", "sha256"):  # warm-up by time
+        for v in ("verify", "clean", "clean2", "sha256"):  # warm-up by time
             w0 = time.perf_counter()
             while (time.perf_counter() - w0) * 1e3 < a.warm_ms:
                 timed(fns[v], 2)
         assert not locate.blame(stream).any() and not verify.corrupt(stream)
+        assert not locate2.blame(stream).any()
         ms = {v: [] for v in fns}
-        counts_ok = True
+        counts_ok = counts2_ok = True
+        trio = ("verify", "clean", "clean2")
+        pos = {v: {0: [], 1: [], 2: []} for v in trio}
+        # what (c2)-(c4) corrupt, and on which plan's bins the columns land
+        pairs = {"pair_valid": ("valid", "valid_b"), "pair_mixed": ("valid", "compared"),
+                 "single2": ("valid",)}
         for r in range(a.rounds):
-            for v in (("verify", "clean") if r % 2 == 0 else ("clean", "verify")):
+            for at, v in enumerate(trio[r % 3:] + trio[:r % 3]):
                 ms[v].append(timed(fns[v], a.reps))
-            assert not locate.blame(stream).any()
+                pos[v][at].append(ms[v][-1])
+            assert not locate.blame(stream).any() and not locate2.blame(stream).any()
             for v in ("valid", "compared"):
                 flip(which[v])
                 timed(fns[v], 2)
@@ -110,19 +129,38 @@ def main():
                     want[b, i] = a.reps * sizes[b]
                 counts_ok = counts_ok and bool(np.array_equal(got, want))
                 flip(which[v])
+            for v, sets in pairs.items():
+                for w in sets:
+                    flip(which[w])
+                timed(fns[v], 2)
+                locate2.blame(stream)
+                ms[v].append(timed(fns[v], a.reps))
+                got = locate2.blame(stream)
+                want = np.zeros_like(got)
+                for w in sets:
+                    for b, i in enumerate(which[w]):
+                        want[b, i] = a.reps * sizes[b]
+                counts2_ok = counts2_ok and bool(np.array_equal(got, want))
+                for w in sets:
+                    flip(which[w])
             ms["sha256"].append(timed(fns["sha256"], a.reps))
         med = {v: statistics.median(x) for v, x in ms.items()}
-        # verify runs first in even rounds, clean in odd ones
-        at = {"first": (ms["clean"][1::2], ms["verify"][0::2]), "second": (ms["clean"][0::2], ms["verify"][1::2])}
-        by_pos = {pos: round(statistics.median(c) / statistics.median(v), 4) if c and v else None
-                  for pos, (c, v) in at.items()}
-        nb = {"verify": verify.bytes, "clean": locate.bytes, "valid": locate.bytes,
-              "compared": locate.bytes, "sha256": n * total}
-        assert nb["verify"] == nb["clean"] == n * total
+        # round r runs verify, clean, clean2 rotated by r: each is first in every third round
+        def by_position(x, y):
+            return {name: round(statistics.median(pos[x][at]) / statistics.median(pos[y][at]), 4)
+                    if pos[x][at] and pos[y][at] else None
+                    for at, name in enumerate(("first", "second", "third"))}
+
+        def per_round(x, y):
+            return round(statistics.median([p / q for p, q in zip(ms[x], ms[y])]), 3)
+
+        by_pos = by_position("clean", "verify")
+        nb = {v: (verify.bytes if v == "verify" else n * total if v == "sha256" else plans[v].bytes) for v in fns}
+        assert nb["verify"] == nb["clean"] == nb["clean2"] == n * total
         print(json.dumps({
             "workload": name, "k": k, "m": m, "stripes": B, "sizes": kind, "size_min": min(sizes),
             "size_max": max(sizes), "layout": "planar, 256-B aligned shards", "bytes": nb["clean"],
-            "forms": {"verify": verify.forms(), "locate": locate.forms()},
+            "forms": {"verify": verify.forms(), "locate": locate.forms(), "locate2": locate2.forms()},
             "us": {v: round(x * 1e3, 2) for v, x in med.items()},
             "us_rounds": {v: [round(y * 1e3, 2) for y in x] for v, x in ms.items()},
             "GBps": {v: round(nb[v] / (x * 1e-3) / 1e9, 1) for v, x in med.items()},
@@ -132,9 +170,19 @@ def main():
             "compared_over_verify": round(med["compared"] / med["verify"], 3),
             "sha256_over_valid": round(med["sha256"] / med["valid"], 3),
             "sha256_over_compared": round(med["sha256"] / med["compared"], 3),
-            "counts_exact": counts_ok, "reps": a.reps, "rounds": a.rounds}), flush=True)
+            "counts_exact": counts_ok,
+            "clean2_over_verify": round(med["clean2"] / med["verify"], 4),
+            "clean2_over_verify_by_position": by_position("clean2", "verify"),
+            "clean2_over_clean_by_position": by_position("clean2", "clean"),
+            "pair_valid_over_valid": per_round("pair_valid", "valid"),
+            "pair_mixed_over_valid": per_round("pair_mixed", "valid"),
+            "single2_over_valid": per_round("single2", "valid"),
+            "pair_valid_over_verify": round(med["pair_valid"] / med["verify"], 3),
+            "pair_mixed_over_verify": round(med["pair_mixed"] / med["verify"], 3),
+            "pair_counts_exact": counts2_ok, "reps": a.reps, "rounds": a.rounds}), flush=True)
         verify.close()
         locate.close()
+        locate2.close()
         hashes.close()
         del raw, digests
         torch.cuda.empty_cache()
