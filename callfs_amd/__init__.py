@@ -23,6 +23,8 @@ from .erasure import (  # noqa: F401
     encode_matrix,
     encode_shards,
     heal_batch,
+    correct,
+    correct_batch,
     locate,
     locate_batch,
     reconstruct,
@@ -37,6 +39,6 @@ __all__ = [
     "ErrShardCorrupted", "ErrShardNotFound", "ErrShortData", "ErrTooFewShards",
     "ErrShardNoData", "ErrShardSize", "ErrSingular", "ErrUnsupportedProfile",
     "decode_rows", "encode_matrix", "encode_shards", "reconstruct", "reconstruct_some", "verify",
-    "locate", "locate_batch", "heal_batch",
+    "locate", "locate_batch", "heal_batch", "correct", "correct_batch",
     "shard_checksum", "shard_layout",
 ]

@@ -142,6 +142,14 @@ SIGNATURES = {
                                 ctypes.POINTER(_int), _int]),
     "rs_codec_decode_heal_ex": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _vp,
                                        _i64, _u8p, _int]),
+    "rs_plan_create_correct": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
+                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rs_correct": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+                          ctypes.POINTER(ctypes.c_uint64)]),
+    "rs_correct_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_int)]),
+    "rs_codec_decode_correct": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _vp,
+                                       _i64, _u8p]),
     "rs_update": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                          ctypes.POINTER(_vp)]),
     "rs_encode_idx": (_int, [_vp, _int, _int, _sz, _vp, _int, ctypes.POINTER(_vp)]),

@@ -23,6 +23,7 @@ struct LocateRun {
   LocateTables t;
   RaggedShape sh;  // nin = k + r', nout = 0
   std::vector<int> ids;
+  bool correct = false;  // launch_correct in launch_locate's place (host_correct.hpp)
   const MixedTables& mt() const { return t.ragged.mixed; }
   size_t bins() const { return static_cast<size_t>(k + m) + 1; }
 };
@@ -67,11 +68,18 @@ inline size_t locate_chunk_bytes(const LocateRun& r, const ChunkLayout& C) {
 
 // The chunk loop, in the style of run_update_chunks. shard_of takes a stripe of the call and a
 // shard index; counts (the call's, batch * (k + m + 1)) are added into and flags[b] set where a
-// compared row of stripe b mismatched.
-template <class ShardF>
+// compared row of stripe b mismatched. back(r, C, items, d, cn) runs once a chunk's counts `cn`
+// are on the host and its device rows at `d` still stand (LocateNoBack: nothing to do).
+struct LocateNoBack {
+  int operator()(const LocateRun&, const ChunkLayout&, const std::vector<RaggedItem>&, const uint8_t*,
+                 const uint64_t*) const {
+    return RS_OK;
+  }
+};
+template <class ShardF, class BackF>
 int run_locate_chunks(const LocateRun& r, Lane& L, const std::vector<RaggedItem>& items,
                       const std::vector<ChunkLayout>& chunks, ShardF& shard_of, uint64_t* counts,
-                      int* flags) {
+                      int* flags, BackF& back) {
   int rc;
   LocateDevTables dt;
   if ((rc = upload_locate_tables(r, L, dt))) return rc;
@@ -100,7 +108,7 @@ int run_locate_chunks(const LocateRun& r, Lane& L, const std::vector<RaggedItem>
       for (size_t q = 0; q < nb; ++q) counts[static_cast<size_t>(id) * nb + q] += cn[j * nb + q];
     }
     sl.pending = false;
-    return RS_OK;
+    return back(r, C, items, static_cast<const uint8_t*>(sl.dev.p), cn);
   };
   std::vector<CopyPool::Seg> segs;
   for (size_t c = 0; c < nchunks; ++c) {
@@ -158,7 +166,8 @@ int run_locate_chunks(const LocateRun& r, Lane& L, const std::vector<RaggedItem>
     x.counts = reinterpret_cast<uint64_t*>(d + locate_counts_off(C));
     x.loc_stride = static_cast<uint32_t>(r.t.stride);
     x.nbins = static_cast<uint32_t>(nb);
-    HIPCHK(launch_locate(a, x, C.any_tail, sl.stream, {}, r.t.max_errors));
+    HIPCHK(r.correct ? launch_correct(a, x, C.any_tail, sl.stream)
+                     : launch_locate(a, x, C.any_tail, sl.stream, {}, r.t.max_errors));
     HIPCHK(hipMemcpyAsync(h + C.status_off, d + C.status_off, total - C.status_off, hipMemcpyDeviceToHost,
                           sl.stream));
     HIPCHK(hipEventRecord(sl.done, sl.stream));
@@ -176,10 +185,12 @@ int run_locate_chunks(const LocateRun& r, Lane& L, const std::vector<RaggedItem>
 // The call's runnable stripes `ids` (each has more than k present shards, a nonzero size and
 // its pointers) on one device and lane. sizes and present (0 / 1 flags, batch * (k + m)) are
 // the whole call's; counts too, zeroed by the caller. max_errors 1 or 2 (2: pair tables and the
-// pair kernel).
-template <class ShardF>
+// pair kernel). correct (with max_errors 1): launch_correct, and `back`
+// after every chunk (host_correct.hpp).
+template <class ShardF, class BackF = LocateNoBack>
 int run_locate(rs_ctx* ctx, int k, int m, int max_errors, const std::vector<int>& ids, const size_t* sizes,
-               const uint8_t* present, ShardF shard_of, uint64_t* counts, int* flags) {
+               const uint8_t* present, ShardF shard_of, uint64_t* counts, int* flags, bool correct = false,
+               BackF back = BackF()) {
   if (ids.empty()) return RS_OK;
   if (ctx->devs.empty()) return RS_E_HIP;
   ctx->n_calls.fetch_add(1, std::memory_order_relaxed);
@@ -199,7 +210,7 @@ int run_locate(rs_ctx* ctx, int k, int m, int max_errors, const std::vector<int>
         if (!seen.count(key) && seen.size() == max_patterns) break;
         seen.insert(std::move(key));
       }
-      LocateRun r{ctx, k, m, {}, {}, {}};
+      LocateRun r{ctx, k, m, {}, {}, {}, correct};
       r.ids.assign(ids.begin() + static_cast<ptrdiff_t>(begin), ids.begin() + static_cast<ptrdiff_t>(end));
       const int count = static_cast<int>(r.ids.size());
       std::vector<size_t> sz(r.ids.size());
@@ -222,7 +233,7 @@ int run_locate(rs_ctx* ctx, int k, int m, int max_errors, const std::vector<int>
       const std::vector<ChunkLayout> chunks = ragged_chunks(r.sh, items, chunk_bytes());
       for (const ChunkLayout& C : chunks)
         if (C.ntiles > kRaggedMaxTiles) return RS_E_ARG;
-      if (const int rc = run_locate_chunks(r, L, items, chunks, shard_of, counts, flags)) return rc;
+      if (const int rc = run_locate_chunks(r, L, items, chunks, shard_of, counts, flags, back)) return rc;
       begin = end;
     }
     return RS_OK;

@@ -11,9 +11,11 @@
 // A pair plan (max_errors = 2) appends what locate_classify2 reads to name
 // two corrupt shards per column: the power-syndrome matrix H_cmp, the point -> position table
 // and, in the shared block, the roots of z^2 + z = c.
-// Plain C++ with no HIP dependence (tests/native/locate_host_test.cpp and locate2_host_test.cpp
-// build it with g++ on the CPU); locate_classify and locate_classify2 are the functions the
-// kernels and the CPU tests both run.
+// A correct plan has a locate plan's tables (max_errors = 1) and runs
+// locate_correct, which also says where and what to XOR to repair a single error.
+// Plain C++ with no HIP dependence (tests/native/locate_host_test.cpp, locate2_host_test.cpp and
+// correct_host_test.cpp build it with g++ on the CPU); locate_classify, locate_classify2 and
+// locate_correct are the functions the kernels and the CPU tests both run.
 #pragma once
 
 #include <cstddef>
@@ -114,6 +116,56 @@ CALLFS_HD inline uint32_t locate_classify(const uint32_t (&s)[NW], int rows, int
   for (int x = 2; x < NW * 4; ++x)
     if (x < rows) ok &= ex[lg[g[x]] + le] == locate_byte(s, x);
   return ok ? pt[kLocMap + j] : kLocateUnexplained;
+}
+
+// The correction of one byte column (correct plans): locate_classify's
+// decision for a single error, and with a shard verdict where and what to XOR: `pos`, the
+// shard's position in T = valid then cmp (j for valid[j], k + x for cmp[x]), and `value`, the
+// error e = s_0 / G[0][j] (or s_x). A column is corrected only when rows >= 3: the verdict
+// takes two syndromes and at least one further row must confirm it -- a corrected column is a
+// codeword by construction, so nothing after the write could catch a miscorrection. With
+// rows < 3 every mismatching column is unexplained. For rows >= 3 the verdict is
+// locate_classify's: one corrupt byte is restored exactly, 2..rows-1 are left alone.
+// (The decision is written out again, not shared with locate_classify: the locate kernels'
+// code stays what it was, instruction for instruction.)
+template <int NW>
+CALLFS_HD inline uint32_t locate_correct(const uint32_t (&s)[NW], int rows, int k, const uint8_t* gf,
+                                         const uint8_t* pt, uint32_t& pos, uint32_t& value) {
+  int nz = 0, first = 0;
+  CALLFS_UNROLL
+  for (int x = NW * 4 - 1; x >= 0; --x) {
+    if (x < rows && locate_byte(s, x) != 0) {
+      ++nz;
+      first = x;
+    }
+  }
+  if (nz == 0) return kLocateClean;
+  if (rows < 3) return kLocateUnexplained;
+  if (nz == 1) {
+    uint32_t sx = 0;
+    CALLFS_UNROLL
+    for (int x = 0; x < NW * 4; ++x) sx |= x < rows ? locate_byte(s, x) : 0u;  // the others are zero
+    pos = static_cast<uint32_t>(k + first);
+    value = sx;
+    return pt[kLocMap + static_cast<size_t>(k) + first];
+  }
+  if (nz != rows) return kLocateUnexplained;
+  const uint8_t* lg = gf;
+  const uint8_t* ex = gf + 256;
+  const uint32_t s0 = locate_byte(s, 0), s1 = locate_byte(s, 1);
+  const uint32_t q = ex[lg[s1] + 255u - lg[s0]];
+  const uint32_t j = pt[kLocRatio + q];
+  if (j == 0xffu) return kLocateUnexplained;
+  const uint8_t* g = pt + kLocG + static_cast<size_t>(j) * kLocateRows;
+  const uint32_t le = (lg[s0] + 255u - lg[g[0]]) % 255u;  // log of e = s_0 / G[0][j]
+  bool ok = true;
+  CALLFS_UNROLL
+  for (int x = 2; x < NW * 4; ++x)
+    if (x < rows) ok &= ex[lg[g[x]] + le] == locate_byte(s, x);
+  if (!ok) return kLocateUnexplained;
+  pos = j;
+  value = ex[le];
+  return pt[kLocMap + j];
 }
 
 // a . b and a / b (b != 0) from the shared log / exp block

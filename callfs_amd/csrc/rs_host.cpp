@@ -9,8 +9,10 @@
 // Split's shape are the HIP-free host_path.hpp and codec_batch.hpp. Every reconstruct, with a
 // wanted set (ReconstructSome / ReconstructData) or without, is admitted into the same kShard*
 // flag rows and takes the same path from there. Locate (which shard is corrupt, DESIGN.md
-// §5.12) runs through host_locate.hpp, and the heal calls compose it with the reconstructs.
+// §5.12) runs through host_locate.hpp, and the heal calls compose it with the reconstructs;
+// correct (repair in place from the syndromes, §5.13) through host_correct.hpp.
 #include "codec_batch.hpp"
+#include "host_correct.hpp"
 #include "host_locate.hpp"
 #include "host_ragged.hpp"
 #include "host_uniform.hpp"
@@ -529,6 +531,45 @@ int rs_codec_decode_heal_ex(rs_ctx* ctx, int k, int m, uint8_t* const* shards, s
 int rs_codec_decode_heal(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
                          uint8_t* out, int64_t original_size, uint8_t* healed) {
   return rs_codec_decode_heal_ex(ctx, k, m, shards, lens, out, original_size, healed, 1);
+}
+
+// ---- exported: correct --------------------------------------------------
+
+int rs_correct_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards, const size_t* lens,
+                     uint64_t* counts, int* status) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!shards || !lens || !counts || !status))) return RS_E_ARG;
+  if ((rc = correct_batch_host(ctx, k, m, batch, shards, lens, counts, status))) return rc;
+  return first_error(status, batch);
+}
+
+int rs_correct(rs_ctx* ctx, int k, int m, uint8_t* const* shards, const size_t* lens, uint64_t* counts) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shards || !lens || !counts) return RS_E_ARG;
+  int status = RS_OK;
+  if ((rc = correct_batch_host(ctx, k, m, 1, shards, lens, counts, &status))) return rc;
+  return status;
+}
+
+int rs_codec_decode_correct(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                            uint8_t* out, int64_t original_size, uint8_t* corrected) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || !shards || !lens || !corrected || original_size < 0 || (original_size && !out)) return RS_E_ARG;
+  const size_t n = static_cast<size_t>(k + m);
+  std::fill(corrected, corrected + n, 0);
+  // the present shards are corrected where they can be; what the stripe's admission or a column
+  // left over has to say is the decode's to say, with its own precedence
+  std::vector<uint64_t> counts(n + 1, 0);
+  int status = RS_OK;
+  if ((rc = correct_batch_host(ctx, k, m, 1, shards, lens, counts.data(), &status))) return rc;
+  for (size_t i = 0; i < n; ++i) corrected[i] = counts[i] != 0;
+  return codec_decode(ctx, k, m, shards, lens, out, original_size, false);
 }
 
 // ---- exported: batched host-memory calls ------------------------------------------------

@@ -320,6 +320,18 @@ constexpr int kOrderLocate = 8192;
 hipError_t launch_locate(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
                          LaunchEvents ev = {}, int max_errors = 1);
 
+// ---- correct launches (rs_mixed.hip) -------------------------------------
+// A locate launch that repairs what it blames: rs_apply_correct classifies a mismatching column
+// with locate_correct and XORs the error value into the blamed shard's byte, through a.in_tab
+// (whose shards must be writable) or a.out_tab. x as for launch_locate with max_errors 1;
+// counts[stripe * nbins + shard] is the number of bytes of that shard the launch changed, bin
+// nbins - 1 the columns left mismatching (with fewer than 3 compared rows: every mismatching
+// column, and nothing is written).
+// (kOrderCorrect + consecutive: rs_plan_forms of a correct plan)
+constexpr int kOrderCorrect = 16384;
+hipError_t launch_correct(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
+                          LaunchEvents ev = {});
+
 // Tiles per slice of a sliced launch (launch_apply's rule) for `streams` shard streams.
 uint32_t launch_slice_tiles(int streams);
 

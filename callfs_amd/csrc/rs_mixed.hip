@@ -11,7 +11,8 @@
 // pattern's row count; one host function, launch_ragged, enqueues both. Locate launches
 // (§5.12) are required launches that compare every row and classify the mismatching byte
 // columns into per-stripe, per-shard counts; the pair instances (§5.12.1) classify with
-// locate_classify2 and add a column blamed on two shards into both shards' counts.
+// locate_classify2 and add a column blamed on two shards into both shards' counts. Correct
+// launches (§5.13) are locate launches that XOR the error value into the blamed shard's byte.
 #include <algorithm>
 #include <array>
 
@@ -72,6 +73,27 @@ __device__ __forceinline__ uint32_t locate_column(const typename LdsAcc<RT>::T& 
   else return locate_classify(s, rows, K, gf, pt);
 }
 
+// A correct plan's column: locate_correct's verdict, and for a shard verdict
+// the position in T = valid then cmp and the error value to XOR into that shard's byte.
+template <int RT>
+__device__ __forceinline__ uint32_t correct_column(const typename LdsAcc<RT>::T& t, int rows, int K,
+                                                   const uint8_t* gf, const uint8_t* pt, uint32_t& pos,
+                                                   uint32_t& value) {
+  uint32_t s[RT / 4];
+  locate_words<RT>(t, s);
+  return locate_correct(s, rows, K, gf, pt, pos, value);
+}
+
+// The shard at position pos of a stripe's T: in_tab's slot pos, or out_tab's slot pos - K. The
+// index differs from lane to lane, so these are plain global loads of the pointer tables (only
+// lanes with something to repair come here). A correct plan's in_tab names writable shards.
+__device__ __forceinline__ uint8_t* correct_shard(const ApplyArgs& a, uint32_t stripe, uint32_t out_stride,
+                                                  uint32_t pos) {
+  const uint32_t K = static_cast<uint32_t>(a.K);
+  return pos < K ? const_cast<uint8_t*>(a.in_tab[static_cast<size_t>(stripe) * K + pos])
+                 : a.out_tab[static_cast<size_t>(stripe) * out_stride + (pos - K)];
+}
+
 // Adds every lane's n (0..16) columns of verdict v (kLocateClean: none) into the stripe's
 // bins: one 64-bit atomic per distinct verdict in the wave, issued by one lane. Sums are
 // formed from ballots alone, so lanes that have left the kernel count as nothing; every lane
@@ -104,10 +126,12 @@ __device__ __forceinline__ void locate_wave_add(uint64_t* bins, uint32_t nbins, 
 
 // The S % 16 tail of a locate launch: lds_tail with every row compared, and a mismatching
 // byte classified and counted. Every thread of the waves that call it reaches the ballots.
-template <int RT, bool PAIR>
+// LOCATE 3 (a correct plan): a byte blamed on a shard is repaired there, with a byte store.
+template <int RT, int LOCATE>
 __device__ __forceinline__ void locate_tail(const ApplyArgs& a, const LocateArgs& x, cptr<const uint8_t*> in,
                                             cptr<uint8_t*> out, uint32_t stripe, uint32_t p,
-                                            uint32_t lds0, uint32_t j) {
+                                            uint32_t lds0, uint32_t j, uint32_t out_stride) {
+  constexpr bool PAIR = LOCATE == 2;
   constexpr int W = LdsAcc<RT>::W;
   const uint32_t nt = static_cast<uint32_t>(a.S - a.nvec * 16);
   uint32_t v = kLocateClean;
@@ -126,7 +150,14 @@ __device__ __forceinline__ void locate_tail(const ApplyArgs& a, const LocateArgs
 #pragma unroll
     for (int r = 0; r < RT; ++r)
       if (r < a.R) lds_xor_byte<RT>(t, r, out[r][b]);
-    v = locate_column<RT, PAIR>(t, a.R, a.K, x.gf, x.loc + static_cast<size_t>(p) * x.loc_stride);
+    const uint8_t* pt = x.loc + static_cast<size_t>(p) * x.loc_stride;
+    if constexpr (LOCATE == 3) {
+      uint32_t pos = 0, val = 0;
+      v = correct_column<RT>(t, a.R, a.K, x.gf, pt, pos, val);
+      if (v < 256u) correct_shard(a, stripe, out_stride, pos)[b] ^= static_cast<uint8_t>(val);
+    } else {
+      v = locate_column<RT, PAIR>(t, a.R, a.K, x.gf, pt);
+    }
   }
   if (__ballot(v != kLocateClean) == 0) return;  // wave-uniform
   if (v != kLocateClean) atomicOr(a.status + static_cast<size_t>(stripe) * a.status_stride, 1);
@@ -148,7 +179,10 @@ __device__ __forceinline__ void locate_tail(const ApplyArgs& a, const LocateArgs
 // table prologue's barrier. LOCATE 2 (the pair plans' kernel, §5.12.1): the same with
 // locate_classify2, in a loop over the 16 columns that is not unrolled, so that the kernel
 // holds one copy of the rule (unrolled 16 times the 16-row instance spilled its accumulators).
-// A lane that matches in every row runs none of it.
+// A lane that matches in every row runs none of it. LOCATE 3 (the correct plans' kernel, §5.13):
+// the columns are classified with locate_correct, and a column blamed on a shard is repaired in
+// that shard: the lane gathers its run's error values into one 16-byte vector and XORs it into
+// the shard's vector. Counts and status words are a locate launch's.
 template <int RT, class P, bool SOME = false, int LOCATE = 0>
 __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t stripe, uint32_t tile,
                                            uint32_t p, uint32_t tab_stride, uint32_t out_stride = 0,
@@ -188,7 +222,7 @@ __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t
   if (a.tail_in_vec) {
     const uint32_t j = tail_lane<BS>(a.tail_in_vec, tile);
     if constexpr (LOCATE != 0) {
-      if (j != ~0u) locate_tail<RT, LOCATE == 2>(a, *lx, in, out, stripe, p, lds0, j);
+      if (j != ~0u) locate_tail<RT, LOCATE>(a, *lx, in, out, stripe, p, lds0, j, out_stride);
     } else {
       if (j != ~0u) lds_tail<RT>(a, in, out, stripe, lds0, j);
     }
@@ -288,7 +322,37 @@ __device__ __forceinline__ void mixed_tile(ApplyArgs& a, uint8_t* smem, uint32_t
         ++run_n;
       }
     };
-    if constexpr (LOCATE == 2) {
+    if constexpr (LOCATE == 3) {
+      // the lane's correction of the shard its run blames, as the 16 bytes of its own vector:
+      // XORed into the shard with one load and one store when the verdict changes and at the
+      // end. No other lane touches these bytes.
+      uint32_t cw[4] = {0, 0, 0, 0}, run_pos = 0;
+      auto apply = [&]() {
+        uint4* q = reinterpret_cast<uint4*>(correct_shard(a, stripe, out_stride, run_pos)) + v0;
+        uint4 y = *q;
+        y.x ^= cw[0];
+        y.y ^= cw[1];
+        y.z ^= cw[2];
+        y.w ^= cw[3];
+        *q = y;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) cw[w] = 0;
+      };
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          uint32_t v = kLocateClean, pos = 0, val = 0;
+          if (bad) v = correct_column<RT>(acc[w][j], R, K, lx->gf, pt, pos, val);
+          if (v != kLocateClean && run_n != 0 && v != run_v && run_v < 256u) apply();
+          note(v);
+          if (v < 256u) {
+            cw[w] |= val << (8 * j);
+            run_pos = pos;
+          }
+        }
+      if (run_n != 0 && run_v < 256u) apply();
+    } else if constexpr (LOCATE == 2) {
       // one copy of the rule: the column index is wave-uniform and the column's syndromes are
       // picked out of the accumulators with selects, so the accumulators stay in registers
 #pragma unroll 1
@@ -428,6 +492,27 @@ void rs_apply_locate2(ApplyArgs a, LocateArgs xl) {
   mixed_tile<RT, P, true, 2>(a, smem, stripe, tile, p, x.tab_stride, stride, &xl);
 }
 
+// Correct launches: rs_apply_locate that repairs what it blames. The shards
+// in_tab and out_tab name are written through.
+template <int RT, class P>
+__global__ __launch_bounds__(P::BS) __attribute__((amdgpu_waves_per_eu(P::WPE, lds_max_waves<RT>())))
+void rs_apply_correct(ApplyArgs a, LocateArgs xl) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  static_assert(P::TILE_VECS == P::BS, "one vector per thread: the tile map counts 512-vector tiles");
+  const RaggedArgs& x = xl.r;
+  const uint32_t t = a.t_base + blockIdx.x;
+  if (t >= x.ntiles) return;  // block-uniform
+  const uint32_t stripe = as_const(x.tile_stripe)[t];
+  const uint32_t tile = t - as_const(x.tile0)[stripe];
+  const uint32_t p = as_const(x.pat)[stripe];
+  a.S = as_const(x.size)[stripe];
+  a.nvec = a.S / 16;
+  a.verify_mask = as_const(x.vmask)[p];
+  const uint32_t stride = static_cast<uint32_t>(a.R);
+  a.R = static_cast<int>(as_const(xl.nrows)[p]);
+  mixed_tile<RT, P, true, 3>(a, smem, stripe, tile, p, x.tab_stride, stride, &xl);
+}
+
 // S < 16: one byte position per thread, 16 threads per stripe; the nibble tables are read
 // from the arena in global memory (a launch of batch * S bytes has nothing to amortise an
 // LDS prologue over). An RT instance (8 or 16: the entry width) serves every R <= RT.
@@ -486,6 +571,9 @@ const std::array<LocateFn, 3> kLocate = {&dev::rs_apply_locate<4, dev::MixedPoli
 const std::array<LocateFn, 3> kLocate2 = {&dev::rs_apply_locate2<4, dev::MixedPolicy<4>>,
                                           &dev::rs_apply_locate2<8, dev::MixedPolicy<8>>,
                                           &dev::rs_apply_locate2<16, dev::MixedPolicy<16>>};
+const std::array<LocateFn, 3> kCorrect = {&dev::rs_apply_correct<4, dev::MixedPolicy<4>>,
+                                          &dev::rs_apply_correct<8, dev::MixedPolicy<8>>,
+                                          &dev::rs_apply_correct<16, dev::MixedPolicy<16>>};
 static_assert(dev::MixedPolicy<4>::BS == 512 && dev::MixedPolicy<8>::BS == 512 &&
                   dev::MixedPolicy<16>::BS == 512 && dev::MixedPolicy<4>::TILE_VECS == 512 &&
                   dev::MixedPolicy<8>::TILE_VECS == 512 && dev::MixedPolicy<16>::TILE_VECS == 512,
@@ -504,11 +592,11 @@ const std::array<std::array<UpdateFn, 3>, 2> kUpdate = {{
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
 // per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one, 2 the
 // required one, 3 the single-source update instance, 4 the pair one, 5 the locate one, 6 the
-// pair locate one)
+// pair locate one, 7 the correct one)
 DeviceOnce g_mixed_wide_lds;
 
 // The vector launch every kind shares: the dynamic-LDS opt-in (`once_key`: 0 the mixed
-// instance, 1 the ragged one, 2 the required one, 3 and 4 the update ones, 5 and 6 the locate ones),
+// instance, 1 the ragged one, 2 the required one, 3 and 4 the update ones, 5 and 6 the locate ones, 7 the correct one),
 // then `grid` tiles
 // in equal consecutive slices of `streams` shard streams, as launch_apply cuts them. A slice
 // boundary may fall inside a stripe (tiles are numbered over the whole grid).
@@ -572,8 +660,11 @@ hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, const uint32_t* nrows
                : launch_tiles(kRagged[inst], 1, x.ntiles, a, x, a.K + a.R, stream, ev);
 }
 
-hipError_t launch_locate(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
-                         LaunchEvents ev, int max_errors) {
+namespace {
+
+// launch_locate and launch_correct: `fns` with the dynamic-LDS key `once_key`
+hipError_t launch_locate_kind(const std::array<LocateFn, 3>& fns, int once_key, ApplyArgs a, const LocateArgs& x,
+                              bool any_tail, hipStream_t stream, LaunchEvents ev, int max_errors) {
   const RaggedArgs& r = x.r;
   if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
       !r.pat || !r.vmask || !r.size || !r.tile0 || !a.in_tab || !a.out_tab || !a.status ||
@@ -585,9 +676,20 @@ hipError_t launch_locate(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStr
   a.t_base = 0;
   a.S = a.nvec = 0;  // per stripe, read by the kernel
   a.tail_in_vec = any_tail ? 1u : 0u;  // wave 0 of each stripe's first tile
-  const int inst = a.R > 8 ? 2 : a.R > 4 ? 1 : 0;
-  return max_errors == 2 ? launch_tiles(kLocate2[inst], 6, r.ntiles, a, x, a.K + a.R, stream, ev)
-                         : launch_tiles(kLocate[inst], 5, r.ntiles, a, x, a.K + a.R, stream, ev);
+  return launch_tiles(fns[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], once_key, r.ntiles, a, x, a.K + a.R, stream, ev);
+}
+
+}  // namespace
+
+hipError_t launch_locate(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
+                         LaunchEvents ev, int max_errors) {
+  return max_errors == 2 ? launch_locate_kind(kLocate2, 6, a, x, any_tail, stream, ev, 2)
+                         : launch_locate_kind(kLocate, 5, a, x, any_tail, stream, ev, max_errors);
+}
+
+hipError_t launch_correct(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
+                          LaunchEvents ev) {
+  return launch_locate_kind(kCorrect, 7, a, x, any_tail, stream, ev, 1);
 }
 
 hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_tail,

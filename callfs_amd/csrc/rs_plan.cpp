@@ -24,7 +24,8 @@ static_assert(kRaggedTileVecs == kRaggedLaunchTileVecs, "the tile map counts the
 // (ragged_tables.hpp) that every launch group names; the plan's S is the largest shard size
 // (never 0). A required plan (rs_plan_create_required) is a ragged plan whose patterns have their
 // own row counts: every launch group has its own tile map and launches with the patterns' row
-// counts inside it. A locate plan (rs_plan_create_locate) is a required plan with nothing
+// counts inside it. A locate plan (rs_plan_create_locate; rs_plan_create_correct's correct plan
+// is one too, with `correct` set) is a required plan with nothing
 // wanted, cut to its first launch group, plus what the classification reads (the shared log / exp
 // block and a block per pattern) and the per-stripe, per-shard counts it adds into.
 enum class PlanKind { kMixed, kRagged, kRequired, kLocate };
@@ -44,6 +45,9 @@ struct MixedPlan {
   // a locate plan's pieces: locate_tables.hpp's blocks and the batch * (k + m + 1) counts
   size_t gf_off = 0, loc_off = 0, loc_stride = 0, counts_off = 0;
   int max_errors = 1;  // 2: a pair plan (rs_plan_create_locate_ex)
+  // a correct plan (rs_plan_create_correct): a locate plan in every piece, whose
+  // launches repair what they blame
+  bool correct = false;
 };
 
 // An update plan (rs_plan_create_update): where the pieces of
@@ -192,7 +196,8 @@ hipError_t plan_launch(const rs_plan& plan, hipStream_t s, const std::vector<int
       const LocateArgs x{r, nrows, d + mp.gf_off, d + mp.loc_off,
                          reinterpret_cast<uint64_t*>(d + mp.counts_off),
                          static_cast<uint32_t>(mp.loc_stride), static_cast<uint32_t>(mp.t.k + mp.t.m + 1)};
-      e = launch_locate(a, x, mp.groups[gi].any_tail, s, g, mp.max_errors);
+      e = mp.correct ? launch_correct(a, x, mp.groups[gi].any_tail, s, g)
+                     : launch_locate(a, x, mp.groups[gi].any_tail, s, g, mp.max_errors);
     } else {
       e = launch_ragged(a, r, nrows, mp.groups[gi].any_tail, s, g);
     }
@@ -390,7 +395,7 @@ int upload_mixed(rs_plan& plan, uint8_t* const* shards, const RaggedTables* rt,
 // required count for ragged and required plans, S for a mixed one.
 int create_tabled(rs_ctx* ctx, int device, int k, int m, PlanKind kind, size_t S, int batch,
                   const size_t* sizes, const uint8_t* present, const uint8_t* required,
-                  uint8_t* const* shards, rs_plan** out, int max_errors = 1) {
+                  uint8_t* const* shards, rs_plan** out, int max_errors = 1, bool correct = false) {
   if (!ctx->device(device)) return RS_E_ARG;
   const bool sized = kind != PlanKind::kMixed;
   LocateTables lt;
@@ -402,10 +407,12 @@ int create_tabled(rs_ctx* ctx, int device, int k, int m, PlanKind kind, size_t S
   auto plan = new_plan(device, sized ? *std::max_element(sizes, sizes + batch) : S, batch);
   plan->mixed = std::make_unique<MixedPlan>();
   plan->mixed->kind = kind;
+  plan->mixed->correct = correct;
   plan->mixed->t = std::move(rt.mixed);
   plan->fixed_form = RS_ORDER_CONSECUTIVE + (kind == PlanKind::kMixed      ? kOrderMixed
                                              : kind == PlanKind::kRagged   ? kOrderRagged
                                              : kind == PlanKind::kRequired ? kOrderRequired
+                                             : correct                     ? kOrderCorrect
                                                                            : kOrderLocate);
   // per stripe with a row: the k shards read, the rows written and the rows compared. Every
   // stripe of a mixed plan has m rows: n shards of S bytes each.
@@ -550,6 +557,23 @@ int rs_plan_create_locate_ex(rs_ctx* ctx, int device, int k, int m, int batch, c
   // (no route to a simpler plan: only this kind counts)
   return create_tabled(ctx, device, k, m, PlanKind::kLocate, 0, batch, sizes, present, nullptr, shards, out,
                        max_errors);
+}
+
+// A locate plan (max_errors 1: the same checks in the same order, the same tables) that
+// launches rs_apply_correct.
+int rs_plan_create_correct(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                           const uint8_t* present, uint8_t* const* shards, rs_plan** out) {
+  DeviceGuard dg;
+  int rc = check_plan_args(ctx, k, m, batch, sizes && shards, out);
+  if (!rc) rc = check_stripes(k, k + m, batch, sizes, nullptr);
+  if (rc) return rc;
+  std::vector<uint8_t> all;
+  if (!present) {
+    all.assign(static_cast<size_t>(batch) * (k + m), 1);
+    present = all.data();
+  }
+  return create_tabled(ctx, device, k, m, PlanKind::kLocate, 0, batch, sizes, present, nullptr, shards, out, 1,
+                       /*correct=*/true);
 }
 
 int rs_plan_create_update(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,

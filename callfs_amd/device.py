@@ -219,7 +219,8 @@ class Plan:
     mask for the whole batch; a batch x (k+m) sequence or array gives every stripe its own
     mask (a mixed plan, DESIGN.md §5.8: one launch repairs stripes with different erasures).
     `Plan.ragged` builds a plan over stripes of different shard sizes,
-    `Plan.locate` one that tells which shard of a stripe is corrupt (§5.12).
+    `Plan.locate` one that tells which shard of a stripe is corrupt (§5.12), `Plan.correct` one
+    that repairs single corrupt bytes in place (§5.13).
     """
 
     def __init__(self, k: int, m: int, S: int, batch: int, pointers: Sequence[int],
@@ -324,6 +325,22 @@ class Plan:
         most) and classifies every mismatching byte column; `blame()` reads the counts.
         max_errors=2 (§5.12.1): a stripe that compares four or more shards also names the two
         shards of a column in which two are corrupt; such a column counts once for each."""
+        return cls._locate_like(k, m, sizes, pointers, present, device, context, max_errors, False)
+
+    @classmethod
+    def correct(cls, k: int, m: int, sizes: Sequence[int], pointers: Sequence[int],
+                present=None, device: int = 0, context: Optional[N.Context] = None) -> "Plan":
+        """rs_plan_create_correct: a locate plan whose launch repairs what it
+        blames. In a stripe that compares three or more shards, a byte column in which one
+        examined shard is corrupt gets that byte restored IN PLACE (the shard pointers are
+        written through, the k read shards included); columns with more errors, and every
+        mismatching column of a stripe that compares fewer than three shards, are left as they
+        are. `blame()` reads the counts: [b, i] = bytes of shard i of stripe b the launches
+        changed, [b, k+m] = columns left mismatching."""
+        return cls._locate_like(k, m, sizes, pointers, present, device, context, 1, True)
+
+    @classmethod
+    def _locate_like(cls, k, m, sizes, pointers, present, device, context, max_errors, correct) -> "Plan":
         n, batch = k + m, len(sizes)
         if len(pointers) != batch * n:
             raise ValueError("need batch*(k+m) shard pointers")
@@ -341,7 +358,10 @@ class Plan:
         ptrs = (ctypes.c_void_p * max(1, len(pointers)))(*pointers)
         szs = (ctypes.c_size_t * max(1, batch))(*self.sizes)
         h = ctypes.c_void_p()
-        if max_errors == 1:
+        if correct:
+            N.check(N.lib.rs_plan_create_correct(self.ctx.handle, device, k, m, batch, szs, pres, ptrs,
+                                                 ctypes.byref(h)), "rs_plan_create_correct")
+        elif max_errors == 1:
             N.check(N.lib.rs_plan_create_locate(self.ctx.handle, device, k, m, batch, szs, pres, ptrs,
                                                 ctypes.byref(h)), "rs_plan_create_locate")
         else:
@@ -352,7 +372,8 @@ class Plan:
         return self
 
     def blame(self, stream: Optional[torch.cuda.Stream] = None):
-        """rs_plan_blame of a locate plan: synchronises the stream and returns a
+        """rs_plan_blame of a locate plan (or a correct plan: bytes changed per shard, and the
+        columns left mismatching): synchronises the stream and returns a
         (batch, k+m+1) uint64 array: [b, i] = byte columns of stripe b blamed on shard i,
         [b, k+m] = its unexplained columns (a pair plan counts a column blamed on two shards
         once for each). Clears the counts; launches accumulate until the
@@ -451,7 +472,7 @@ class Plan:
                    198: "dma-x32", 224: "tridb-g4", 225: "tridb-g8", 256: "bs", 257: "bs-g8",
                    258: "bs-g2", 259: "bs-q8", 260: "bs-q16", 261: "bs-x8", 262: "bs-x32",
                    512: "mixed", 1024: "ragged", 2048: "required", 4096: "update",
-                   8192: "locate"}
+                   8192: "locate", 16384: "correct"}
 
     def tune(self, reps: int = 5, stream: Optional[torch.cuda.Stream] = None) -> list:
         """rs_plan_tune: time each launch group in every tile order its kernel offers

@@ -304,6 +304,46 @@ class Codec:
             return out, [i for i in range(n) if healed[i]]
         raise _decode_error(rc)
 
+    def decode_correct(self, shards: List, profile: ErasureProfile,
+                       original_size: int) -> Tuple[bytearray, List[int]]:
+        """rs_codec_decode_correct: decode() after one correct() over the
+        present shards (writable buffers): in a stripe that compares three or more shards, every
+        byte column with one corrupt byte is repaired in place, however many shards the damage
+        is spread over. Returns (data, indices of the shards that had bytes corrected); raises
+        ErrShardCorrupted exactly when decode() still does after the correction. Every other
+        error is decode()'s."""
+        k, m = profile.data_shards, profile.parity_shards
+        if k < 1 or m < 1:
+            raise ErrInvalidProfile()
+        n = k + m
+        if k + m > 256:
+            raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create decoder")
+        if len(shards) != n:
+            raise ErrTooFewShards(f"erasure: reconstruction failed: {ErrTooFewShards.text}")
+        lens = (ctypes.c_size_t * n)()
+        for i, s in enumerate(shards):
+            lens[i] = 0 if s is None else len(s)
+        S = next((lens[i] for i in range(n) if lens[i]), 0)
+        bufs = list(shards)
+        for i in range(n):
+            if lens[i] == 0 and S:
+                bufs[i] = bytearray(S)
+            elif lens[i] and not _writable(bufs[i]):
+                raise TypeError("decode_correct repairs corrupt bytes in place: writable buffers")
+        ptrs = (ctypes.c_void_p * n)(*[_addr(b) if b is not None and len(b) else 0
+                                      for b in bufs])
+        out = bytearray(max(int(original_size), 0))
+        corrected = (ctypes.c_uint8 * n)()
+        rc = N.lib.rs_codec_decode_correct(self.context.handle, k, m, ptrs, lens,
+                                           _addr(out) if out else None, int(original_size), corrected)
+        if rc in (N.RS_OK, N.RS_E_CORRUPT, N.RS_E_INSUFFICIENT):
+            for i in range(n):
+                if (shards[i] is None or len(shards[i]) == 0) and lens[i]:
+                    shards[i] = bufs[i]
+        if rc == N.RS_OK:
+            return out, [i for i in range(n) if corrected[i]]
+        raise _decode_error(rc)
+
     def encode_many(self, datas: Sequence, profile: ErasureProfile
                     ) -> Tuple[List[Optional[List[memoryview]]], List[Optional[Exception]]]:
         """Codec.encode for many objects of one profile in one native call
@@ -767,6 +807,56 @@ def heal_batch(stripes: List[List], k: int, m: int,
                 if (st[i] is None or len(st[i]) == 0) and lens[b * n + i]:
                     st[i] = bufs[b][i]
     return out, [[i for i in range(n) if healed[b * n + i]] for b in range(B)]
+
+
+def _need_writable(stripes: Sequence[Sequence], call: str) -> None:
+    for st in stripes:
+        for s in st:
+            if s is not None and len(s) and not _writable(s):
+                raise TypeError(f"{call} repairs corrupt bytes in place: writable buffers")
+
+
+def correct(shards: List, k: int, m: int, context: Optional[N.Context] = None) -> np.ndarray:
+    """rs_correct: repairs, in place, every byte column of a stripe in which
+    one examined shard is corrupt, where the stripe compares three or more shards. shards: an
+    n-list of writable buffers (None / empty = missing: neither read nor rebuilt). Returns
+    k+m+1 uint64 counts: [i] = bytes of shard i that were changed, [k+m] = columns that still
+    mismatch (more than one error, or fewer than three compared shards)."""
+    ctx = context or N.default_context()
+    n = k + m
+    if len(shards) != n:
+        raise ErrTooFewShards()
+    _need_writable([shards], "correct")
+    lens = (ctypes.c_size_t * n)(*[0 if s is None else len(s) for s in shards])
+    counts = np.zeros(n + 1, dtype=np.uint64)
+    rc = N.lib.rs_correct(ctx.handle, k, m, _shard_ptrs(shards), lens,
+                          counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+    if rc not in (N.RS_OK, N.RS_E_CORRUPT):
+        raise _wrapped(rc, "correct")
+    return counts
+
+
+def correct_batch(stripes: Sequence[Sequence], k: int, m: int,
+                  context: Optional[N.Context] = None) -> Tuple[np.ndarray, List[int]]:
+    """rs_correct_batch: correct() for many stripes of any sizes and erasures in one call.
+    Returns (counts, a (batch, k+m+1) uint64 array; status[b]: RS_OK where nothing mismatched
+    or every mismatching column was corrected, RS_E_CORRUPT where a column is left, or the
+    stripe's own error as reconstruct_batch reports it). Only shards with corrected bytes are
+    copied back from the device."""
+    ctx = context or N.default_context()
+    n = k + m
+    B = len(stripes)
+    if any(len(st) != n for st in stripes):
+        raise ErrTooFewShards()
+    _need_writable(stripes, "correct_batch")
+    lens = (ctypes.c_size_t * max(B * n, 1))(*[0 if s is None else len(s) for st in stripes for s in st])
+    counts = np.zeros((B, n + 1), dtype=np.uint64)
+    status = (ctypes.c_int * max(B, 1))()
+    rc = N.lib.rs_correct_batch(ctx.handle, k, m, B, _shard_ptrs([s for st in stripes for s in st] or [None]),
+                                lens, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), status)
+    out = list(status)[:B]
+    _per_stripe(rc, out, "rs_correct_batch")
+    return counts, out
 
 
 def host_counters(context: Optional[N.Context] = None) -> dict:

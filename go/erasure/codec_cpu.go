@@ -187,6 +187,32 @@ func (c *Codec) DecodeHealMax(shards [][]byte, profile ErasureProfile, originalS
 	return c.DecodeHeal(shards, profile, originalSize)
 }
 
+// Correct and CorrectBatch report ErrLocateUnavailable on builds without the GPU codec: the CPU
+// codec has no syndrome decoder. Nothing is written.
+func (c *Codec) Correct(shards [][]byte, profile ErasureProfile) ([]uint64, error) {
+	if profile.DataShards < 1 || profile.ParityShards < 1 {
+		return nil, ErrInvalidProfile
+	}
+	return nil, ErrLocateUnavailable
+}
+
+func (c *Codec) CorrectBatch(objs [][][]byte, profile ErasureProfile) ([][]uint64, []error) {
+	errs := make([]error, len(objs))
+	for b := range errs {
+		errs[b] = ErrLocateUnavailable
+		if profile.DataShards < 1 || profile.ParityShards < 1 {
+			errs[b] = ErrInvalidProfile
+		}
+	}
+	return make([][]uint64, len(objs)), errs
+}
+
+// DecodeCorrect is Decode on builds without the GPU codec: nothing is corrected.
+func (c *Codec) DecodeCorrect(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, []int, error) {
+	out, err := c.cpuDecode(shards, profile, originalSize)
+	return out, nil, err
+}
+
 // Overwrite replaces object bytes [offset, offset+len(data)) in the data shards and updates
 // the affected parity columns with upstream Update, on builds without the GPU codec.
 func (c *Codec) Overwrite(shards [][]byte, profile ErasureProfile, offset int64, data []byte) error {

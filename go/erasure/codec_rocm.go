@@ -951,3 +951,178 @@ func (c *Codec) Overwrite(shards [][]byte, profile ErasureProfile, offset int64,
 	return updateErr(C.rs_codec_overwrite(gpuCtx, C.int(k), C.int(m), C.size_t(S), ptrs.at(0),
 		C.int64_t(offset), (*C.uint8_t)(unsafe.Pointer(&data[0])), C.size_t(len(data))))
 }
+
+// Correct repairs one object's present shards in place from the parity syndromes (rs_correct,
+// DESIGN.md §5.13): in every byte column in which exactly one examined shard is corrupt, that
+// byte is restored, however many shards the damage is spread over -- as long as the object
+// compares three or more shards (present shards beyond the first k). counts[i] is the number
+// of bytes of shard i that were changed, counts[k+m] the columns that still mismatch (more than
+// one error in the column, or fewer than three compared shards: nothing is written there).
+// Missing shards (nil or empty) are neither read nor rebuilt. Shards with a nonzero count are
+// the ones to store back.
+func (c *Codec) Correct(shards [][]byte, profile ErasureProfile) ([]uint64, error) {
+	k, m := profile.DataShards, profile.ParityShards
+	if k < 1 || m < 1 {
+		return nil, ErrInvalidProfile
+	}
+	n := k + m
+	if n > 256 || device() == nil {
+		return nil, ErrLocateUnavailable
+	}
+	if len(shards) != n {
+		return nil, fmt.Errorf("erasure: reconstruction failed: %w", reedsolomon.ErrTooFewShards)
+	}
+	ptrs := newCArray(n)
+	defer ptrs.free()
+	lens := make([]C.size_t, n)
+	counts := make([]C.uint64_t, n+1)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pinShards(&pin, ptrs, lens, 0, shards)
+	rc := C.rs_correct(gpuCtx, C.int(k), C.int(m), ptrs.at(0), &lens[0], &counts[0])
+	if rc != C.RS_OK && rc != C.RS_E_CORRUPT { // RS_E_CORRUPT: counts[k+m] says how much is left
+		return nil, decodeErr(rc)
+	}
+	out := make([]uint64, n+1)
+	for i := range out {
+		out[i] = uint64(counts[i])
+	}
+	return out, nil
+}
+
+// CorrectBatch is Correct for many objects of any sizes and erasures in one call
+// (rs_correct_batch): a scrub over objs[b] = the n shards of object b as stored. counts[b] is
+// Correct's; errs[b] is nil when nothing mismatched or every mismatching column was corrected,
+// ErrShardCorrupted when a column is left (bytes already corrected stay corrected), and the
+// object's own error otherwise. Only shards with corrected bytes are copied back from the
+// device. On builds or hosts without the GPU codec every object reports ErrLocateUnavailable.
+func (c *Codec) CorrectBatch(objs [][][]byte, profile ErasureProfile) (counts [][]uint64, errs []error) {
+	k, m := profile.DataShards, profile.ParityShards
+	errs = make([]error, len(objs))
+	counts = make([][]uint64, len(objs))
+	fail := func(err error) ([][]uint64, []error) {
+		for b := range errs {
+			if errs[b] == nil {
+				errs[b] = err
+			}
+		}
+		return counts, errs
+	}
+	if k < 1 || m < 1 {
+		return fail(ErrInvalidProfile)
+	}
+	n := k + m
+	if len(objs) == 0 {
+		return counts, errs
+	}
+	if n > 256 || device() == nil {
+		return fail(ErrLocateUnavailable)
+	}
+	ptrs := newCArray(len(objs) * n)
+	defer ptrs.free()
+	lens := make([]C.size_t, len(objs)*n)
+	cn := make([]C.uint64_t, len(objs)*(n+1))
+	status := make([]C.int, len(objs))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for b, shards := range objs {
+		if len(shards) != n {
+			errs[b] = fmt.Errorf("erasure: reconstruction failed: %w", reedsolomon.ErrTooFewShards)
+			continue // all lens 0 and no pointers: the stripe reports RS_E_NO_DATA, ignored
+		}
+		pinShards(&pin, ptrs, lens, b*n, shards)
+	}
+	rc := C.rs_correct_batch(gpuCtx, C.int(k), C.int(m), C.int(len(objs)), ptrs.at(0), &lens[0],
+		&cn[0], &status[0])
+	if rc != C.RS_OK && !hasStatus(status, rc) { // a call-level error
+		return fail(decodeErr(rc))
+	}
+	for b := range objs {
+		if errs[b] != nil {
+			continue
+		}
+		counts[b] = make([]uint64, n+1)
+		for i := range counts[b] {
+			counts[b][i] = uint64(cn[b*(n+1)+i])
+		}
+		errs[b] = decodeErr(status[b])
+	}
+	return counts, errs
+}
+
+// DecodeCorrect is Decode after one Correct over the present shards
+// (rs_codec_decode_correct): an object whose fetched shards hold scattered bad sectors -- one
+// corrupt byte per column, on any number of shards -- is served where Decode and DecodeHeal end
+// in ErrShardCorrupted. It returns the object and the indices of the shards that had bytes
+// corrected in `shards`, for the caller to store back; it fails with ErrShardCorrupted exactly
+// when Decode still does after the correction. Every other error, the join and the trim are
+// Decode's. Objects the GPU does not take are decoded by the CPU codec, which corrects nothing.
+func (c *Codec) DecodeCorrect(shards [][]byte, profile ErasureProfile, originalSize int64) ([]byte, []int, error) {
+	k, m := profile.DataShards, profile.ParityShards
+	if k < 1 || m < 1 {
+		return nil, nil, ErrInvalidProfile
+	}
+	n := k + m
+	if n > 256 || originalSize < int64(gpuMinBytes) || device() == nil {
+		out, err := c.cpuDecode(shards, profile, originalSize)
+		return out, nil, err
+	}
+	if len(shards) != n {
+		return nil, nil, fmt.Errorf("erasure: reconstruction failed: %w", reedsolomon.ErrTooFewShards)
+	}
+	S := 0
+	for _, s := range shards {
+		if len(s) != 0 {
+			S = len(s)
+			break
+		}
+	}
+	bufs := make([][]byte, n)
+	copy(bufs, shards)
+	ptrs := newCArray(n)
+	defer ptrs.free()
+	lens := make([]C.size_t, n)
+	flags := make([]C.uint8_t, n)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for i := range bufs {
+		lens[i] = C.size_t(len(bufs[i]))
+		if len(bufs[i]) == 0 && S > 0 { // upstream Reconstruct allocates missing shards
+			if cap(bufs[i]) >= S {
+				bufs[i] = bufs[i][:S]
+			} else {
+				bufs[i] = make([]byte, S)
+			}
+		}
+		if len(bufs[i]) > 0 {
+			pin.Pin(&bufs[i][0])
+			ptrs.set(i, unsafe.Pointer(&bufs[i][0]))
+		}
+	}
+	buf := make([]byte, int(originalSize))
+	var out *C.uint8_t
+	if originalSize > 0 {
+		pin.Pin(&buf[0])
+		out = (*C.uint8_t)(unsafe.Pointer(&buf[0]))
+	}
+	rc := C.rs_codec_decode_correct(gpuCtx, C.int(k), C.int(m), ptrs.at(0), &lens[0], out,
+		C.int64_t(originalSize), &flags[0])
+	switch rc {
+	case C.RS_OK, C.RS_E_CORRUPT, C.RS_E_INSUFFICIENT: // Reconstruct ran: the nil entries are filled
+		for i := range shards {
+			if len(shards[i]) == 0 && lens[i] != 0 {
+				shards[i] = bufs[i]
+			}
+		}
+	}
+	if rc != C.RS_OK {
+		return nil, nil, decodeErr(rc)
+	}
+	var corrected []int
+	for i := range flags {
+		if flags[i] != 0 {
+			corrected = append(corrected, i)
+		}
+	}
+	return buf, corrected, nil
+}

@@ -618,6 +618,48 @@ int rs_heal_batch_ex(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shard
 int rs_codec_decode_heal_ex(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
                             uint8_t* out, int64_t original_size, uint8_t* healed, int max_errors);
 
+/* ---- correct plans: repair corrupt bytes in place --------------------
+ * A correct plan is a locate plan (max_errors 1: the same arguments, errors in the same order,
+ * the same tables byte for byte) whose launch repairs what it blames: in a mismatching byte
+ * column that one shard explains, the error value is XORed into that shard's byte. THE SHARD
+ * POINTERS ARE WRITTEN THROUGH, the k read shards included, so `shards` must name writable
+ * memory. A column is corrected only in a stripe that compares r' >= 3 shards: two syndromes
+ * make the verdict and at least one more must confirm it (a corrected column is a codeword, so
+ * no later verify could catch a miscorrection). With r' < 3 nothing is written and every
+ * mismatching column is unexplained. For r' >= 3 and e corrupt examined bytes in a column:
+ *   e = 0: clean; e = 1: that byte is restored exactly; 2 <= e <= r'-1: untouched and
+ *   unexplained; e >= r': may be miscorrected.
+ * rs_plan_blame reads (and clears) batch * (k+m+1) counts: counts[b*(k+m+1) + i] is the number
+ * of bytes of shard i of stripe b the launches changed, entry k+m the columns left mismatching.
+ * A second launch over repaired data changes nothing and adds only to that last entry.
+ * _status and _stripe_status flag every stripe that HAD a mismatch, corrected or not.
+ * rs_plan_launch / _launch_timed only enqueue (no allocation, no sync; graph-capturable);
+ * rs_plan_groups and rs_plan_bytes are the locate plan's (the few bytes written are not
+ * counted); rs_plan_forms reports RS_ORDER_CORRECT + RS_ORDER_CONSECUTIVE; rs_plan_tune,
+ * rs_plan_set_orders and rs_plan_launch_ceiling behave as for a locate plan. Missing shards are
+ * neither read nor rebuilt. Pair correction (max_errors 2) is not built.
+ * rs_correct / rs_correct_batch: the same for stripes in host memory, on the staged ragged
+ * pipeline like rs_locate_batch (checks, their order and the column parts of large stripes are
+ * that call's). After a chunk's launch the counts come back first and only the (stripe, shard)
+ * rows with a nonzero count are copied back into the caller's shards: a call over clean stripes
+ * copies no shard byte back. counts as for rs_plan_blame. status[b] is RS_OK when nothing
+ * mismatched or every mismatching column was corrected, RS_E_CORRUPT when a column is left
+ * (bytes already corrected stay corrected). A stripe with exactly k present shards is RS_OK
+ * with zero counts and reaches no device.
+ * rs_codec_decode_correct: rs_codec_decode's checks, then one rs_correct over the present
+ * shards, then the ordinary decode (reconstruct, verify, join, trim), whose result it returns:
+ * RS_E_CORRUPT exactly when the decode still fails after the correction. corrected receives
+ * k+m flags: 1 for a shard with a nonzero count. */
+#define RS_ORDER_CORRECT 16384
+int rs_plan_create_correct(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                           const uint8_t* present, uint8_t* const* shards, rs_plan** out);
+int rs_correct(rs_ctx* ctx, int k, int m, uint8_t* const* shards, const size_t* lens,
+               uint64_t* counts);
+int rs_correct_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
+                     const size_t* lens, uint64_t* counts, int* status);
+int rs_codec_decode_correct(rs_ctx* ctx, int k, int m, uint8_t* const* shards, size_t* lens,
+                            uint8_t* out, int64_t original_size, uint8_t* corrected);
+
 /* ---- ShardChecksum on device-resident shards (codec.go:81-84; §8(f) of SURVEY.md) ----
  * SHA-256 of `count` messages already in HBM, one digest per message written to
  * `digests` (device memory, 32*count bytes, FIPS 180-4 byte order — hex-encode it for

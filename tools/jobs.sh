@@ -493,8 +493,11 @@ timeout -k 10 400 python3 -u tools/update_bench.py "$@" | tee $O/update_bench.js
 # every shard (tools/locate_bench.py): RS(10,4) x 256 stripes of 64 KiB..4 MiB
 # and RS(16,4) x 4,096 stripes of 1..16 KiB, clean and with one shard of every stripe wholly
 # corrupt; and the pair plans of §5.12.1 over the same batch (clean, two shards of every stripe
-# wholly corrupt, and the single-error batch). One JSON line per workload on stdout and in <out dir>/locate_bench.jsonl (the lines
-# kept in profiles/r16/locate/). Usage: bash tools/jobs.sh locate_bench <out dir> [locate_bench.py args]
+# wholly corrupt, and the single-error batch); with --correct also the correct plans of §5.13 (a
+# second line per workload: clean, a shard wholly corrupt and repaired, rs_heal_batch against
+# rs_correct_batch on host stripes; the lines kept in profiles/r18/correct/). One JSON line per
+# workload and section on stdout and in <out dir>/locate_bench.jsonl (the lines kept in
+# profiles/r16/locate/). Usage: bash tools/jobs.sh locate_bench <out dir> [locate_bench.py args]
 job_locate_bench() {
 cd "$(dirname "$JOBS")/.." || exit $?
 O=${1:-locate_out}; mkdir -p "$O" || exit $?

@@ -25,7 +25,20 @@ and so on (use a multiple of 3 rounds). (c2)-(c4) follow (c) in every round and 
 against (c) valid of the same round, the median of the per-round ratios. Prints one JSON line
 per workload: median microseconds, GB/s of algorithmic bytes, the ratios b/a, c/a and d/c, the
 pair plan's ratios, and the counts checks of (c) and of (c2)-(c4).
-usage: python tools/locate_bench.py [--workload rs10_4] [--workload rs16_4]
+Correct plans (`--correct` adds a second JSON line per workload, "section":
+"correct"), same batch, same process:
+  (e1) clean_correct   the correct plan on clean data, against (b) clean timed beside it: the
+               two alternate, and are compared first against first and second against second;
+  (e2) fix_valid       one of the k read shards of every stripe wholly corrupt, against (c) valid
+               of the same round. A launch repairs the damage, so it is re-injected before
+               every timed launch (the same XOR kernels that inject it for (c), then a
+               synchronise); the time is the launch's own events', so the injection is not in
+               it, but the launch finds the cache as the injection left it;
+  (e3) fix_compared    the same with a compared shard, against (c) compared;
+  (e4) heal_host / correct_host   rs_heal_batch against rs_correct_batch, wall clock, on
+               `--host-stripes` host stripes of `--host-shard` bytes with one bad 4 KiB sector each
+               (re-injected before every call; RS of the workload).
+usage: python tools/locate_bench.py [--workload rs10_4] [--workload rs16_4] [--correct]
 """
 import argparse
 import json
@@ -45,6 +58,110 @@ from tools.mixed_bench import timed  # noqa: E402
 from tools.ragged_bench import WORKLOADS, draw_sizes, planar_offsets  # noqa: E402
 
 
+def correct_section(a, name, k, m, sizes, ptrs, flip, which, locate, stream):
+    """(e1)-(e4) of the module docstring: one JSON line."""
+    from callfs_amd import erasure
+    n, B = k + m, len(sizes)
+    correct = Plan.correct(k, m, sizes, ptrs)
+
+    def launch(p):
+        return lambda e0, e1: p.launch(stream, events=(e0, e1))
+
+    def fix(v):
+        def fn(e0, e1):
+            flip(which[v])  # the launch before this one repaired it
+            correct.launch(stream, events=(e0, e1))
+        return fn
+
+    def found(v):
+        def fn(e0, e1):
+            locate.launch(stream, events=(e0, e1))
+        return fn
+
+    w0 = time.perf_counter()
+    while (time.perf_counter() - w0) * 1e3 < a.warm_ms:
+        timed(launch(correct), 2)
+    assert not correct.blame(stream).any() and not locate.blame(stream).any()
+    ms = {v: [] for v in ("clean", "clean_correct", "valid", "fix_valid", "compared", "fix_compared")}
+    pos = {"clean": ([], []), "clean_correct": ([], [])}
+    counts_ok = True
+    for r in range(a.rounds):
+        order = ("clean", "clean_correct") if r % 2 == 0 else ("clean_correct", "clean")
+        for at, v in enumerate(order):
+            ms[v].append(timed(launch(locate if v == "clean" else correct), a.reps))
+            pos[v][at].append(ms[v][-1])
+        assert not correct.blame(stream).any() and not locate.blame(stream).any()
+        for v in ("valid", "compared"):
+            flip(which[v])
+            timed(found(v), 2)
+            ms[v].append(timed(found(v), a.reps))
+            flip(which[v])
+            locate.blame(stream)
+            timed(fix(v), 2)
+            correct.blame(stream)
+            ms["fix_" + v].append(timed(fix(v), a.reps))
+            got = correct.blame(stream)
+            want = np.zeros_like(got)
+            for b, i in enumerate(which[v]):
+                want[b, i] = a.reps * sizes[b]
+            counts_ok = counts_ok and bool(np.array_equal(got, want))
+    assert not locate.blame(stream).any()  # every repair was exact: the batch is clean again
+    med = {v: statistics.median(x) for v, x in ms.items()}
+
+    def per_round(x, y):
+        return round(statistics.median([p / q for p, q in zip(ms[x], ms[y])]), 4)
+
+    by_pos = {nm: round(statistics.median(pos["clean_correct"][at]) / statistics.median(pos["clean"][at]), 4)
+              if pos["clean_correct"][at] and pos["clean"][at] else None
+              for at, nm in enumerate(("first", "second"))}
+    # (e4) host stripes, one bad 4 KiB sector each
+    S, HB = a.host_shard, a.host_stripes
+    rng = np.random.default_rng(a.seed)
+    host = []
+    for _ in range(HB):
+        st = [rng.integers(0, 256, S, dtype=np.uint8) for _ in range(k)] + [np.zeros(S, dtype=np.uint8) for _ in range(m)]
+        erasure.encode_shards(st, k, m)
+        host.append(st)
+    sector = [(int(rng.integers(0, n)), 4096 * int(rng.integers(0, max(1, S // 4096)))) for _ in range(HB)]
+
+    def hurt():
+        for st, (i, o) in zip(host, sector):
+            st[i][o:o + 4096] ^= 0x55
+
+    wall = {"heal_host": [], "correct_host": []}
+    host_ok = True
+    for _ in range(a.host_reps + 1):  # the first pass warms both
+        hurt()
+        t0 = time.perf_counter()
+        status, healed = erasure.heal_batch(host, k, m)
+        wall["heal_host"].append((time.perf_counter() - t0) * 1e3)
+        host_ok = host_ok and status == [0] * HB and healed == [[i] for i, _ in sector]
+        hurt()
+        t0 = time.perf_counter()
+        counts, status = erasure.correct_batch(host, k, m)
+        wall["correct_host"].append((time.perf_counter() - t0) * 1e3)
+        host_ok = host_ok and status == [0] * HB and all(
+            int(counts[b, i]) == min(4096, S - o) and int(counts[b].sum()) == int(counts[b, i])
+            for b, (i, o) in enumerate(sector))
+    hmed = {v: statistics.median(x[1:]) for v, x in wall.items()}
+    print(json.dumps({
+        "workload": name, "section": "correct", "k": k, "m": m, "stripes": B, "bytes": correct.bytes,
+        "forms": {"locate": locate.forms(), "correct": correct.forms()},
+        "us": {v: round(x * 1e3, 2) for v, x in med.items()},
+        "us_rounds": {v: [round(y * 1e3, 2) for y in x] for v, x in ms.items()},
+        "clean_correct_over_clean": round(med["clean_correct"] / med["clean"], 4),
+        "clean_correct_over_clean_by_position": by_pos,
+        "fix_valid_over_valid": per_round("fix_valid", "valid"),
+        "fix_compared_over_compared": per_round("fix_compared", "compared"),
+        "counts_exact": counts_ok,
+        "host": {"stripes": HB, "shard_bytes": S, "sector": 4096,
+                 "ms": {v: round(x, 2) for v, x in hmed.items()},
+                 "ms_calls": {v: [round(y, 2) for y in x[1:]] for v, x in wall.items()},
+                 "heal_over_correct": round(hmed["heal_host"] / hmed["correct_host"], 3), "exact": host_ok},
+        "reps": a.reps, "rounds": a.rounds}), flush=True)
+    correct.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", action="append", choices=sorted(WORKLOADS))
@@ -52,6 +169,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warm-ms", type=float, default=150.0)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--correct", action="store_true", help="also the correct plans' rows (e1)-(e4)")
+    ap.add_argument("--host-stripes", type=int, default=16)
+    ap.add_argument("--host-shard", type=int, default=1 << 20)
+    ap.add_argument("--host-reps", type=int, default=5)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev)
@@ -180,6 +301,8 @@ def main():
             "pair_valid_over_verify": round(med["pair_valid"] / med["verify"], 3),
             "pair_mixed_over_verify": round(med["pair_mixed"] / med["verify"], 3),
             "pair_counts_exact": counts2_ok, "reps": a.reps, "rounds": a.rounds}), flush=True)
+        if a.correct:
+            correct_section(a, name, k, m, sizes, ptrs, flip, which, locate, stream)
         verify.close()
         locate.close()
         locate2.close()
