@@ -81,6 +81,12 @@ SIGNATURES = {
                                      ctypes.POINTER(_int)]),
     "rs_codec_decode_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
                                      ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_int)]),
+    "rs_codec_encode_batch_sums": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+                                          ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_sz),
+                                          _vp, ctypes.POINTER(_int)]),
+    "rs_codec_decode_batch_sums": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+                                          _vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64), _vp,
+                                          ctypes.POINTER(_int)]),
     "rs_reconstruct_some": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _u8p]),
     "rs_reconstruct_some_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_vp),
                                          ctypes.POINTER(_sz), _u8p, _int, ctypes.POINTER(_int)]),

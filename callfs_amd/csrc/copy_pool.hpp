@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -61,6 +62,37 @@ class CopyPool {
                               static_cast<const uint8_t*>(s.src) + o, len,
                               len2 ? static_cast<uint8_t*>(s.dst2) + o : nullptr, len2});
       }
+    job.count = job.pieces.size();
+    share(job);
+  }
+
+  // fn(0) .. fn(count - 1), each once, on the calling thread and the pool's workers: the
+  // tasks that are no copies (the host side of the checksummed batches hashes one shard per
+  // task). fn must not call back into the pool.
+  void each(size_t count, const std::function<void(size_t)>& fn) {
+    if (workers_.empty() || count < 2) {
+      for (size_t i = 0; i < count; ++i) fn(i);
+      return;
+    }
+    Job job;
+    job.fn = &fn;
+    job.count = count;
+    share(job);
+  }
+
+ private:
+  static constexpr size_t kPiece = 1u << 20;
+  static constexpr size_t kInline = 256u << 10;
+  struct Job {
+    std::vector<Seg> pieces;                         // a copy job's work items, or
+    const std::function<void(size_t)>* fn = nullptr;  // the task of each()
+    size_t count = 0;
+    std::atomic<size_t> next{0};
+    int users = 0;  // workers inside work(); guarded by mu_
+  };
+
+  // Queues the job, works on it and returns once every item has been done.
+  void share(Job& job) {
     {
       std::lock_guard<std::mutex> g(mu_);
       queue_.push_back(&job);
@@ -72,22 +104,16 @@ class CopyPool {
     done_.wait(lk, [&] { return job.users == 0; });
   }
 
- private:
-  static constexpr size_t kPiece = 1u << 20;
-  static constexpr size_t kInline = 256u << 10;
-  struct Job {
-    std::vector<Seg> pieces;
-    std::atomic<size_t> next{0};
-    int users = 0;  // workers inside work(); guarded by mu_
-  };
-
   static void copy(const Seg& s) {
     if (s.n) std::memcpy(s.dst, s.src, s.n);
     if (s.dst2 && s.n2) std::memcpy(s.dst2, s.src, std::min(s.n, s.n2));
   }
 
   static void work(Job& j) {
-    for (size_t i; (i = j.next.fetch_add(1)) < j.pieces.size();) copy(j.pieces[i]);
+    for (size_t i; (i = j.next.fetch_add(1)) < j.count;) {
+      if (j.fn) (*j.fn)(i);
+      else copy(j.pieces[i]);
+    }
   }
 
   void unlink(Job* j) {

@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "rs_internal.hpp"
+#include "sums_host.hpp"
 
 namespace callfs {
 namespace {
@@ -60,6 +61,18 @@ bool ragged_batch() {
     return !(e && *e == '0');
   }();
   return on;
+}
+
+// Where a checksummed codec batch hashes its whole-stripe items (sums_table.hpp has the rule):
+// CALLFS_RS_SUMS_DEVICE=0 the copy pool's threads always, =1 the device always, else `auto`.
+SumsKnob sums_device_knob() {
+  static const SumsKnob v = [] {
+    const char* e = std::getenv("CALLFS_RS_SUMS_DEVICE");
+    if (e && e[0] == '0' && !e[1]) return SumsKnob::kHost;
+    if (e && e[0] == '1' && !e[1]) return SumsKnob::kDevice;
+    return SumsKnob::kAuto;
+  }();
+  return v;
 }
 
 // Zero-copy: when every caller buffer lies in rs_host_alloc memory (page-locked and

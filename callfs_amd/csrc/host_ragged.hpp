@@ -10,6 +10,7 @@
 
 #include "host_common.hpp"
 #include "ragged_chunks.hpp"
+#include "sha256.hpp"
 
 namespace callfs {
 namespace {
@@ -24,6 +25,10 @@ struct RaggedRun {
   RaggedShape sh;
   std::vector<int> ids;
   const Join* joins;  // nullable: one per runnable stripe of the call (codec-level batches)
+  // a checksummed codec batch, else null; sums_host[s] = 1: stripe s of the
+  // run hashes on the host (sums_route)
+  const SumsCall* sums = nullptr;
+  std::vector<uint8_t> sums_host;
   const Join* join_of(int id) const { return joins ? joins + id : nullptr; }
   const MixedPattern& pattern(int s) const { return mt.patterns[mt.pat[static_cast<size_t>(s)]]; }
   void count(size_t chunks, size_t copies) const {
@@ -101,8 +106,9 @@ hipError_t launch_ragged_chunk(const RaggedRun& r, const ChunkLayout& C, uint8_t
 }
 
 // Staged: one H2D of the chunk's input region (through the zeroed status words that open the
-// output region), launch_ragged per launch group on the slot's device mirror, one D2H of the
-// output region, then the slot's event.
+// output region), launch_ragged per launch group on the slot's device mirror, the hash launch
+// of a chunk that carries a message table (sha256_rows over the rows where they lie), one D2H
+// of the output region, then the slot's event.
 struct RaggedStaged {
   const RaggedRun& r;
   Lane& L;
@@ -120,6 +126,16 @@ struct RaggedStaged {
     const size_t head = C.status_off + sizeof(int) * C.count;
     HIPCHK(hipMemcpyAsync(d, h, head, hipMemcpyHostToDevice, sl.stream));
     HIPCHK(launch_ragged_chunk(r, C, d, static_cast<const uint8_t*>(L.rag_tabs.p), dt, sl.stream));
+    if (C.sums_count) {
+      Sha256RowsArgs a{};
+      a.base = d;
+      a.table = reinterpret_cast<const uint32_t*>(d + C.sums_tab_off);
+      a.expected = C.sums == SumsMode::kCheck ? reinterpret_cast<const uint32_t*>(d + C.sums_expect_off) : nullptr;
+      a.out = d + C.sums_out_off;
+      a.count = static_cast<uint32_t>(C.sums_count);
+      HIPCHK(launch_sha256_rows(a, sl.stream));
+      r.ctx->n_launches.fetch_add(1, std::memory_order_relaxed);
+    }
     HIPCHK(hipMemcpyAsync(h + C.status_off, d + C.status_off, C.out_end - C.status_off,
                           hipMemcpyDeviceToHost, sl.stream));
     HIPCHK(hipEventRecord(sl.done, sl.stream));
@@ -223,6 +239,13 @@ struct RaggedInplace {
 // before are copied out first. in / out take a stripe of the call's runnable
 // list and a shard index; flags (per runnable stripe) receive 1 where a compared row
 // mismatched.
+// A checksummed codec batch (r.sums): a chunk with a message table gets it and -- a decode --
+// its slots' expected digests written beside the metadata, and its digests or flags are read
+// when it drains. The host-hashed stripes of a decode are hashed before the chunk that holds
+// their first item is staged, those of an encode once the chunk that holds their last item has
+// drained and its rows have landed in the caller's buffers. A decode delivers nothing of a
+// stripe with a mismatch (the caller runs it again): the join of a device-checked item's
+// present data shards therefore waits for the chunk's flags and is copied from its staging.
 template <class Transport, class InF, class OutF>
 int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>& items,
                       const std::vector<ChunkLayout>& chunks, Transport& tr, InF& in, OutF& out,
@@ -239,6 +262,23 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
   }
   const size_t k = static_cast<size_t>(r.k);
   std::vector<CopyPool::Seg> segs;
+  const SumsCall* sums = r.sums;
+  const bool check = sums && sums->mode == SumsMode::kCheck;
+  std::vector<SumsTask> tasks;
+  // the shards of stripe s that are hashed, by the pattern: valid[], the compared rows and
+  // (an encode) the written rows
+  auto hashed_shards = [&](int s, auto&& fn) {
+    const MixedPattern& pt = r.pattern(s);
+    for (int i : pt.valid) fn(i);
+    for (size_t row = 0; row < pt.rows.size(); ++row)
+      if (!check || row >= static_cast<size_t>(pt.missing)) fn(pt.rows[row]);
+  };
+  auto stripe_bad = [&](int s) {
+    bool any = false;
+    hashed_shards(s, [&](int i) { any |= sums->bad[sums->at(r.ids[static_cast<size_t>(s)], i)] != 0; });
+    return any;
+  };
+  auto on_host = [&](int s) { return sums && r.sums_host[static_cast<size_t>(s)]; };
   auto drain = [&](Slot& sl) -> int {
     if (!sl.pending) return RS_OK;
     const int wrc = tr.wait(sl);
@@ -246,11 +286,29 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
     const ChunkLayout& C = chunks[sl.rag_chunk];
     uint8_t* h = tr.staging(sl);
     const int* st = reinterpret_cast<const int*>(h + C.status_off);
+    if (C.sums_count) {
+      const std::vector<SumsSlot> slots = sums_slots(C, r.sh, items, r.mt);
+      for (size_t s = 0; s < slots.size(); ++s) {
+        const size_t at = sums->at(r.ids[static_cast<size_t>(slots[s].stripe)], slots[s].shard);
+        if (check) sums->bad[at] = h[C.sums_out_off + s] != 0;
+        else std::memcpy(sums->digests + 32 * at, h + C.sums_out_off + 32 * s, 32);
+      }
+    }
     for (size_t j = 0; j < C.count; ++j) {
       const RaggedItem& it = items[C.first + j];
       const int id = r.ids[static_cast<size_t>(it.stripe)];
+      if (check && stripe_bad(it.stripe)) continue;  // nothing of it is delivered
       if (st[j]) flags[id] = 1;
       const MixedPattern& pt = r.pattern(it.stripe);
+      if (sums && !check && on_host(it.stripe) && it.off + it.w == r.sh.size[static_cast<size_t>(it.stripe)])
+        hashed_shards(it.stripe, [&](int i) {
+          tasks.push_back(sums_task(*sums, id, i, out(id, i), r.sh.size[static_cast<size_t>(it.stripe)]));
+        });
+      // the join a device-checked item held back: its present data shards, from staging
+      for (size_t i = 0; check && !on_host(it.stripe) && i < k; ++i) {
+        const auto js = join_span(r.join_of(id), pt.valid[i], it.off, it.w);
+        if (js.first) segs.push_back({js.first, h + C.items[j].in_off + C.items[j].pitch * i, js.second});
+      }
       for (int row = 0; row < pt.missing; ++row) {
         const int i = pt.rows[static_cast<size_t>(row)];
         const auto tee = join_span(r.join_of(id), i, it.off, it.w);
@@ -270,9 +328,23 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
     // of one run are laid out differently: its inputs may lie where those outputs were)
     if (!segs.empty()) r.ctx->pool.run(segs);
     segs.clear();
+    run_sums_tasks(r.ctx->pool, tasks);  // an encode's host-hashed stripes that just completed
+    tasks.clear();
     const ChunkLayout& C = chunks[c];
     uint8_t* h = tr.staging(sl);
     uint8_t* b = tr.base(sl);
+    if (check) {
+      for (size_t j = 0; j < C.count; ++j) {
+        const RaggedItem& it = items[C.first + j];
+        if (!on_host(it.stripe) || it.off) continue;
+        const int id = r.ids[static_cast<size_t>(it.stripe)];
+        hashed_shards(it.stripe, [&](int i) {
+          tasks.push_back(sums_task(*sums, id, i, in(id, i), r.sh.size[static_cast<size_t>(it.stripe)]));
+        });
+      }
+      run_sums_tasks(r.ctx->pool, tasks);
+      tasks.clear();
+    }
     // a row's address by the pattern's row number: written rows in the output part, compared
     // ones behind the k inputs
     auto row_at = [&](uint8_t* at, size_t j, int row) {
@@ -288,8 +360,10 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
       const RaggedItem& it = items[C.first + j];
       const int id = r.ids[static_cast<size_t>(it.stripe)];
       const MixedPattern& pt = r.pattern(it.stripe);
+      // a checked decode joins no shard before its stripe's flags are known
+      const bool tee_now = !check || (on_host(it.stripe) && !stripe_bad(it.stripe));
       for (size_t i = 0; i < k; ++i) {
-        const auto tee = join_span(r.join_of(id), pt.valid[i], it.off, it.w);
+        const auto tee = join_span(tee_now ? r.join_of(id) : nullptr, pt.valid[i], it.off, it.w);
         segs.push_back({h + C.items[j].in_off + C.items[j].pitch * i, in(id, pt.valid[i]) + it.off, it.w,
                         tee.first, tee.second});
       }
@@ -297,6 +371,13 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
         segs.push_back({row_at(h, j, static_cast<int>(row)), in(id, pt.rows[row]) + it.off, it.w});
     }
     r.ctx->pool.run(segs);
+    if (C.sums_count) {
+      const std::vector<SumsSlot> slots = sums_slots(C, r.sh, items, r.mt);
+      sums_fill_table(slots, reinterpret_cast<uint32_t*>(h + C.sums_tab_off));
+      for (size_t s = 0; check && s < slots.size(); ++s)
+        std::memcpy(h + C.sums_expect_off + 32 * s,
+                    sums->expected + 32 * sums->at(r.ids[static_cast<size_t>(slots[s].stripe)], slots[s].shard), 32);
+    }
     if ((rc = tr.send(sl, C))) return rc;
     sl.pending = true;
     sl.rag_chunk = c;
@@ -305,6 +386,8 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
     segs.clear();
     if ((rc = drain(L.slot[c % nslots]))) return rc;
     r.ctx->pool.run(segs);
+    run_sums_tasks(r.ctx->pool, tasks);
+    tasks.clear();
   }
   return RS_OK;
 }
@@ -386,14 +469,15 @@ int run_ragged_direct(const RaggedRun& r, Lane& L, InF& in, OutF& out, int* flag
 template <class InF, class OutF>
 int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_missing,
                        const std::vector<size_t>& S, const std::vector<uint8_t>& present, InF& in,
-                       OutF& out, int* flags, const Join* joins) {
+                       OutF& out, int* flags, const Join* joins, const SumsCall* sums) {
   HIPCHK(hipSetDevice(device));
   const int n = k + m, stripes = static_cast<int>(S.size());
   const size_t nn = static_cast<size_t>(n);
   // direct: every buffer pinned, and the call at or above the zero-copy threshold
   unsigned long long total = 0;
   for (size_t s : S) total += static_cast<unsigned long long>(s) * nn;
-  bool direct = !ctx->pinned.empty() && total >= zero_copy_min(nn);
+  // (a checksummed batch takes the staged transport alone)
+  bool direct = !sums && !ctx->pinned.empty() && total >= zero_copy_min(nn);
   for (int j = 0; direct && j < stripes; ++j)
     for (int i = 0; direct && i < n; ++i) {
       const bool written = present[static_cast<size_t>(j) * nn + i] == kShardWanted;
@@ -410,7 +494,7 @@ int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_m
     direct = joins[j].len == 0 || ctx->pinned.contains(joins[j].out, joins[j].len);
   for (const RaggedClass& cls : ragged_classes(n, k, stripes, present.data(), !by_missing)) {
     for (const auto& seg : ragged_segments(k, n, cls.rows, cls.stripes, present.data(), kRaggedArenaBudget)) {
-      RaggedRun r{ctx, k, m, {}, {}, {}, joins};
+      RaggedRun r{ctx, k, m, {}, {}, {}, joins, sums, {}};
       r.ids.assign(cls.stripes.begin() + static_cast<ptrdiff_t>(seg.first),
                    cls.stripes.begin() + static_cast<ptrdiff_t>(seg.second));
       std::vector<uint8_t> pres(r.ids.size() * nn), want(pres.size());
@@ -435,6 +519,19 @@ int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_m
         continue;
       }
       const std::vector<RaggedItem> items = ragged_items(r.sh, chunk_bytes());
+      if (sums) {
+        // packed with the regions of the hash launch; the rule then takes them out of the
+        // chunks that hash on the host
+        const SumsKnob knob = sums_device_knob();
+        std::vector<ChunkLayout> chunks = ragged_chunks(r.sh, items, chunk_bytes(), true,
+                                                        knob == SumsKnob::kHost ? SumsMode::kNone : sums->mode);
+        r.sums_host = sums_route(r.sh, items, chunks, knob);
+        for (const ChunkLayout& C : chunks)
+          if (C.ntiles > kRaggedMaxTiles) return RS_E_ARG;
+        RaggedStaged tr{r, L, {}};
+        if ((rc = run_ragged_chunks(r, L, items, chunks, tr, in, out, flags))) return rc;
+        continue;
+      }
       // the whole run as one in-place chunk on slot 0
       if (items.size() <= kRaggedMaxItems && small_max_bytes() > 0) {
         std::vector<ChunkLayout> one(1, layout_chunk(r.sh, items, 0, items.size()));
@@ -465,14 +562,14 @@ int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_m
 template <class InF, class OutF>
 int run_ragged(rs_ctx* ctx, int k, int m, bool by_missing, const std::vector<size_t>& S,
                const std::vector<uint8_t>& present, InF in, OutF out, int* flags,
-               const Join* joins = nullptr) {
+               const Join* joins = nullptr, const SumsCall* sums = nullptr) {
   if (ctx->devs.empty()) return RS_E_HIP;
   ctx->n_calls.fetch_add(1, std::memory_order_relaxed);
   ctx->n_ragged_calls.fetch_add(1, std::memory_order_relaxed);
   // one device and lane, chosen round-robin like any call (split_ways does not apply)
   Device* dev = ctx->devs[device_slot(ctx->rr.fetch_add(1), 0, ctx->devs.size())].get();
   return with_lane(ctx, dev, [&](Lane& L) {
-    return run_ragged_on_lane(ctx, L, dev->id, k, m, by_missing, S, present, in, out, flags, joins);
+    return run_ragged_on_lane(ctx, L, dev->id, k, m, by_missing, S, present, in, out, flags, joins, sums);
   });
 }
 

@@ -48,6 +48,23 @@ struct RaggedShape {
   int stripes() const { return static_cast<int>(size.size()); }
 };
 
+// What a checksummed codec batch hashes of a chunk on the device: nothing
+// (every other caller), the digest of every shard of an item (an encode: its staged inputs
+// and its written rows), or a check of every staged shard against its expected digest (a
+// decode: the k inputs and the compared rows). Only whole-stripe items are hashed in a chunk.
+enum class SumsMode { kNone, kDigest, kCheck };
+
+inline bool whole_stripe(const RaggedShape& sh, const RaggedItem& it) {
+  return it.off == 0 && it.w == sh.size[static_cast<size_t>(it.stripe)];
+}
+// The rows of a whole-stripe item that are hashed: slots [0, nin) are its staged rows in
+// staging order, [nin, nin + nout) its written rows (digest mode alone).
+inline size_t sums_rows(const RaggedShape& sh, const RaggedItem& it, SumsMode mode) {
+  if (mode == SumsMode::kNone || !whole_stripe(sh, it)) return 0;
+  const size_t s = static_cast<size_t>(it.stripe);
+  return static_cast<size_t>(sh.nin[s]) + (mode == SumsMode::kDigest ? static_cast<size_t>(sh.nout[s]) : 0);
+}
+
 struct ItemLayout {
   size_t in_off = 0;   // input row r at in_off + r * pitch
   size_t out_off = 0;  // output row r at out_off + r * pitch
@@ -69,12 +86,23 @@ struct ChunkLayout {
   uint32_t ntiles = 0;
   bool any_tail = false;
   std::vector<ItemLayout> items;  // [count]
+  // The regions of sha256_rows (sha256.hpp), absent (sums_count == 0) unless the chunk hashes
+  // on the device: the message table in the metadata, the expected digests (check mode) behind
+  // the input rows, the digests or flag bytes behind the status words.
+  SumsMode sums = SumsMode::kNone;
+  size_t sums_count = 0;       // messages = result slots
+  size_t sums_tab_off = 0;     // [sums_count][3] dwords
+  size_t sums_expect_off = 0;  // [sums_count][32] bytes
+  size_t sums_out_off = 0;     // kDigest: [sums_count][32] bytes; kCheck: [sums_count] bytes
+  std::vector<uint32_t> sums_slot0;  // [count]: an item's first slot
 };
 
 // Lays items [first, first + count) out. with_rows = false: the metadata and status words
-// alone (the direct transport, whose rows are the caller's buffers).
+// alone (the direct transport, whose rows are the caller's buffers). sums: the regions of a
+// chunk that hashes on the device; kNone leaves every offset what it was without them.
 inline ChunkLayout layout_chunk(const RaggedShape& sh, const std::vector<RaggedItem>& items,
-                                size_t first, size_t count, bool with_rows = true) {
+                                size_t first, size_t count, bool with_rows = true,
+                                SumsMode sums = SumsMode::kNone) {
   ChunkLayout L;
   L.first = first;
   L.count = count;
@@ -82,6 +110,14 @@ inline ChunkLayout layout_chunk(const RaggedShape& sh, const std::vector<RaggedI
   for (size_t j = 0; j < count; ++j) {
     ntiles += ragged_tiles(items[first + j].w);
     L.any_tail |= (items[first + j].w & 15u) != 0;
+  }
+  if (sums != SumsMode::kNone) {
+    L.sums_slot0.resize(count);
+    for (size_t j = 0; j < count; ++j) {
+      L.sums_slot0[j] = static_cast<uint32_t>(L.sums_count);
+      L.sums_count += sums_rows(sh, items[first + j], sums);
+    }
+    if (L.sums_count) L.sums = sums;
   }
   L.ntiles = static_cast<uint32_t>(ntiles);
   Packer pk;
@@ -92,6 +128,7 @@ inline ChunkLayout layout_chunk(const RaggedShape& sh, const std::vector<RaggedI
   L.tile0_off = pk.take(sizeof(uint32_t) * (count + 1));
   L.tile_stripe_off = pk.take(sizeof(uint32_t) * static_cast<size_t>(ntiles));
   L.item_tab_off = pk.take(4 * sizeof(uint32_t) * count);
+  if (L.sums_count) L.sums_tab_off = pk.take(3 * sizeof(uint32_t) * L.sums_count);
   L.meta_end = pk.off;
   L.items.resize(count);
   for (size_t j = 0; j < count; ++j) {
@@ -99,8 +136,10 @@ inline ChunkLayout layout_chunk(const RaggedShape& sh, const std::vector<RaggedI
     L.items[j].pitch = round_up(it.w, 16);
     if (with_rows) L.items[j].in_off = pk.take(L.items[j].pitch * static_cast<size_t>(sh.nin[it.stripe]));
   }
+  if (L.sums == SumsMode::kCheck) L.sums_expect_off = pk.take(32 * L.sums_count);
   L.in_end = L.status_off = pk.off;
   pk.take(sizeof(int) * count);
+  if (L.sums_count) L.sums_out_off = pk.take((L.sums == SumsMode::kDigest ? 32 : 1) * L.sums_count);
   for (size_t j = 0; j < count; ++j) {
     const RaggedItem& it = items[first + j];
     if (with_rows) L.items[j].out_off = pk.take(L.items[j].pitch * static_cast<size_t>(sh.nout[it.stripe]));
@@ -157,7 +196,8 @@ inline std::vector<RaggedItem> ragged_items(const RaggedShape& sh, size_t budget
 // least one (an item alone may need up to ragged_effective_budget). Returns the chunks'
 // layouts in order.
 inline std::vector<ChunkLayout> ragged_chunks(const RaggedShape& sh, const std::vector<RaggedItem>& items,
-                                              size_t budget, bool with_rows = true) {
+                                              size_t budget, bool with_rows = true,
+                                              SumsMode sums = SumsMode::kNone) {
   std::vector<ChunkLayout> chunks;
   size_t first = 0;
   while (first < items.size()) {
@@ -166,7 +206,7 @@ inline std::vector<ChunkLayout> ragged_chunks(const RaggedShape& sh, const std::
     size_t step = 1;
     while (lo < hi) {
       const size_t probe = std::min(hi, lo + step);
-      if (layout_chunk(sh, items, first, probe, with_rows).out_end <= budget) {
+      if (layout_chunk(sh, items, first, probe, with_rows, sums).out_end <= budget) {
         lo = probe;
         step *= 2;
       } else {
@@ -176,10 +216,10 @@ inline std::vector<ChunkLayout> ragged_chunks(const RaggedShape& sh, const std::
     }
     while (lo < hi) {
       const size_t mid = (lo + hi + 1) / 2;
-      if (layout_chunk(sh, items, first, mid, with_rows).out_end <= budget) lo = mid;
+      if (layout_chunk(sh, items, first, mid, with_rows, sums).out_end <= budget) lo = mid;
       else hi = mid - 1;
     }
-    chunks.push_back(layout_chunk(sh, items, first, lo, with_rows));
+    chunks.push_back(layout_chunk(sh, items, first, lo, with_rows, sums));
     first += lo;
   }
   return chunks;

@@ -10,7 +10,9 @@
 // wanted set (ReconstructSome / ReconstructData) or without, is admitted into the same kShard*
 // flag rows and takes the same path from there. Locate (which shard is corrupt, DESIGN.md
 // §5.12) runs through host_locate.hpp, and the heal calls compose it with the reconstructs;
-// correct (repair in place from the syndromes, §5.13) through host_correct.hpp.
+// correct (repair in place from the syndromes, §5.13) through host_correct.hpp. The checksummed
+// codec batches (§7.7) are the codec batches with a SumsCall handed to the ragged pipeline; what
+// they hash where, and a decode's follow-up run, are the HIP-free sums_table.hpp / sums_host.hpp.
 #include "codec_batch.hpp"
 #include "host_correct.hpp"
 #include "host_locate.hpp"
@@ -75,14 +77,23 @@ struct BatchMode {
 // rows mismatched.
 // One call is counted: by run_ragged, or with the first group that runs (tables without
 // launch groups run nothing). Returns RS_OK or the error that ended the call.
+// sums (nullable): a checksummed codec batch, indexed by the call's stripes
+// like the rest. It takes the ragged pipeline whatever its groups are, and there the staged
+// transport.
 template <class InF, class OutF>
 int run_batch(rs_ctx* ctx, int k, int m, BatchMode mode, const BatchGroups& groups,
               const size_t* S, const uint8_t* present, const Join* joins, InF in, OutF out,
-              int* flags) {
+              int* flags, SumsCall* sums = nullptr) {
   const size_t n = static_cast<size_t>(k + m);
-  const BatchRoute route = batch_route(groups, ragged_batch());
+  BatchRoute route = batch_route(groups, ragged_batch() || sums);
+  if (sums && !route.ragged && !groups.stripes.empty()) {
+    route.ragged = true;
+    route.ids = groups.stripes;
+    std::sort(route.ids.begin(), route.ids.end());
+  }
   if (route.ragged) {
     const std::vector<int>& ids = route.ids;
+    if (sums) sums->obj = ids.data();
     std::vector<size_t> Sj(ids.size());
     std::vector<uint8_t> pres(ids.size() * n);
     std::vector<Join> jj;
@@ -96,7 +107,7 @@ int run_batch(rs_ctx* ctx, int k, int m, BatchMode mode, const BatchGroups& grou
     const int rc = run_ragged(ctx, k, m, mode.by_missing, Sj, pres,
                               [&](int j, int i) { return in(ids[j], i); },
                               [&](int j, int i) { return out(ids[j], i); }, fj.data(),
-                              joins ? jj.data() : nullptr);
+                              joins ? jj.data() : nullptr, sums);
     for (size_t j = 0; j < ids.size(); ++j) flags[ids[j]] = fj[j];
     return rc;
   }
@@ -128,10 +139,15 @@ int run_batch(rs_ctx* ctx, int k, int m, BatchMode mode, const BatchGroups& grou
 // required (nullable, batch * n flags) or data_only (the data shards) name the missing shards
 // to rebuild: the others are neither written nor read, a stripe without a row reaches no
 // device, and decode's join of such a stripe is a plain copy of its data shards.
+// expected and bad (both or neither; batch * n digests and flags): rs_codec_decode_batch_sums.
+// The admitted objects run with every present shard taken as good and their shards hashed on
+// the way; nothing of an object with a mismatch is delivered, and those objects then run
+// again, in one plain call of this function, with their bad shards' lengths zero.
 int reconstruct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
                            size_t* lens, bool verify, uint8_t* const* out,
                            const int64_t* original_sizes, int* status,
-                           const uint8_t* required = nullptr, bool data_only = false) {
+                           const uint8_t* required = nullptr, bool data_only = false,
+                           const uint8_t* expected = nullptr, uint8_t* bad = nullptr) {
   const size_t n = static_cast<size_t>(k + m), B = static_cast<size_t>(batch);
   std::vector<uint8_t> present(B * n, 0);
   std::vector<size_t> S(B, 0);  // nonzero for the stripes that run
@@ -176,9 +192,27 @@ int reconstruct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const*
   std::vector<int> flags(B, 0);
   auto shard = [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; };
   if (!copies.empty()) ctx->pool.run(copies);
-  const int rc = run_batch(ctx, k, m, BatchMode{verify, !verify}, groups, S.data(),
-                           present.data(), out ? joins.data() : nullptr, shard, shard, flags.data());
+  SumsCall sums;
+  sums.mode = SumsMode::kCheck;
+  sums.n = k + m;
+  sums.expected = expected;
+  sums.bad = bad;
+  if (bad) std::memset(bad, 0, B * n);
+  int rc = run_batch(ctx, k, m, BatchMode{verify, !verify}, groups, S.data(), present.data(),
+                     out ? joins.data() : nullptr, shard, shard, flags.data(), bad ? &sums : nullptr);
   if (rc) return rc;
+  if (bad) {
+    SumsRerun again(k + m, batch, S.data(), bad, shards, lens, out, original_sizes);
+    if (again.count()) {
+      rc = reconstruct_batch_host(ctx, k, m, again.count(), again.shards.data(), again.lens.data(),
+                                  verify, again.out.data(), again.sizes.data(), again.status.data());
+      if (rc && rc != first_error(again.status.data(), again.count())) return rc;  // call-level
+      again.finish(k + m, lens, status, [](int st) {
+        return st == RS_OK || st == RS_E_CORRUPT || st == RS_E_INSUFFICIENT;
+      });
+      for (int b : again.objs) S[static_cast<size_t>(b)] = 0;  // done
+    }
+  }
   for (size_t b = 0; b < B; ++b) {
     if (!S[b]) continue;
     for (size_t i = 0; i < n; ++i)
@@ -704,15 +738,17 @@ int rs_codec_overwrite(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* shar
 
 // ---- exported: codec-level batches (objects in, objects out) ----------------------------
 
-int rs_codec_encode_batch(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* data,
-                          const size_t* lens, uint8_t* const* shards_out, const size_t* out_caps,
-                          size_t* shard_sizes, int* status) {
+// rs_codec_encode_batch, and with digests (batch * n * 32 bytes) rs_codec_encode_batch_sums.
+static int codec_encode_batch(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* data,
+                              const size_t* lens, uint8_t* const* shards_out, const size_t* out_caps,
+                              size_t* shard_sizes, int* status, uint8_t* digests, bool with_sums) {
   DeviceGuard dg;
   // per object codec.go:31 Split and :36 Encode; the profile (:22-26) is the call's
   int rc = check_profile(k, m);
   if (rc) return rc;
   if (!ctx || batch < 0 ||
-      (batch && (!data || !lens || !shards_out || !out_caps || !shard_sizes || !status)))
+      (batch && (!data || !lens || !shards_out || !out_caps || !shard_sizes || !status ||
+                 (with_sums && !digests))))
     return RS_E_ARG;
   const int n = k + m;
   const size_t B = static_cast<size_t>(batch);
@@ -739,12 +775,30 @@ int rs_codec_encode_batch(rs_ctx* ctx, int k, int m, int batch, const uint8_t* c
     groups.add(S[b], &present[b * n], n, static_cast<int>(b));
   }
   std::vector<int> flags(B, 0);
+  SumsCall sums;
+  sums.mode = SumsMode::kDigest;
+  sums.n = n;
+  sums.digests = digests;
   rc = run_batch(ctx, k, m, BatchMode{false, false}, groups, S.data(), present.data(), tees.data(),
                  [&](int b, int i) { return split_row(plan[b], data[b], shards_out[b], i); },
                  [&](int b, int i) { return shards_out[b] + S[b] * static_cast<size_t>(i); },
-                 flags.data());
+                 flags.data(), with_sums ? &sums : nullptr);
   if (rc) return rc;
   return first_error(status, batch);
+}
+
+int rs_codec_encode_batch(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* data,
+                          const size_t* lens, uint8_t* const* shards_out, const size_t* out_caps,
+                          size_t* shard_sizes, int* status) {
+  return codec_encode_batch(ctx, k, m, batch, data, lens, shards_out, out_caps, shard_sizes, status,
+                            nullptr, false);
+}
+
+int rs_codec_encode_batch_sums(rs_ctx* ctx, int k, int m, int batch, const uint8_t* const* data,
+                               const size_t* lens, uint8_t* const* shards_out, const size_t* out_caps,
+                               size_t* shard_sizes, uint8_t* digests, int* status) {
+  return codec_encode_batch(ctx, k, m, batch, data, lens, shards_out, out_caps, shard_sizes, status,
+                            digests, true);
 }
 
 int rs_codec_decode_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
@@ -757,6 +811,21 @@ int rs_codec_decode_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* 
   if (!ctx || batch < 0 || (batch && (!shards || !lens || !out || !original_sizes || !status)))
     return RS_E_ARG;
   return reconstruct_batch_host(ctx, k, m, batch, shards, lens, true, out, original_sizes, status);
+}
+
+int rs_codec_decode_batch_sums(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,
+                               size_t* lens, const uint8_t* expected, uint8_t* const* out,
+                               const int64_t* original_sizes, uint8_t* bad, int* status) {
+  DeviceGuard dg;
+  // per object manager.go:283-296 (a shard whose checksum differs counts as missing), then
+  // codec.go:55 Reconstruct, :59-65 Verify, :67-77 join / trim
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 ||
+      (batch && (!shards || !lens || !expected || !out || !original_sizes || !bad || !status)))
+    return RS_E_ARG;
+  return reconstruct_batch_host(ctx, k, m, batch, shards, lens, true, out, original_sizes, status,
+                                nullptr, false, expected, bad);
 }
 
 int rs_codec_decode_data_batch(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* shards,

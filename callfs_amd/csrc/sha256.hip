@@ -8,6 +8,10 @@
 // lane issues the next block's four 16-B loads before the current block's 64 rounds.
 // Messages are read as dwordx4 at any alignment; padding and the big-endian length
 // follow FIPS 180-4 exactly (bit-exact with Go's crypto/sha256).
+//
+// Two entry points over one hash_message: sha256_kernel takes a table of pointers and lengths
+// (rs_sha256_plan_*), sha256_rows the rows of one chunk of the ragged host pipeline from a
+// table inside the chunk, for the checksummed codec batches.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -81,18 +85,15 @@ __device__ __forceinline__ void load_block16(const uint8_t* p, uint4 (&q)[4]) {
   }
 }
 
-template <int MPB>
-__global__ __launch_bounds__(64) void sha256_kernel(Sha256Args a) {
-  if (static_cast<int>(threadIdx.x) >= MPB) return;
-  const int idx = blockIdx.x * MPB + threadIdx.x;
-  if (idx >= a.count) return;
-  const uint8_t* msg = a.msgs[idx];
-  const uint64_t len = a.lens[idx];
-  uint32_t st[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a,
-                    0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+// The digest state of one message: full blocks (the next block's loads issued before the
+// current block's rounds), then the FIPS tail. Shared by both entry points below.
+__device__ __forceinline__ void hash_message(const uint8_t* msg, uint64_t len, uint32_t (&st)[8]) {
+  st[0] = 0x6a09e667; st[1] = 0xbb67ae85; st[2] = 0x3c6ef372; st[3] = 0xa54ff53a;
+  st[4] = 0x510e527f; st[5] = 0x9b05688c; st[6] = 0x1f83d9ab; st[7] = 0x5be0cd19;
   const uint64_t full = len / 64;
   uint32_t w[16];
-  // 16-B loads at any byte address (legal on gfx950, rs_kernels.hpp): no byte path
+  // 16-B loads at any byte address (legal on gfx950, rs_kernels.hpp): no byte path. Only
+  // whole blocks are loaded as vectors, so none reaches past the message's last byte.
   uint4 q[4];
   if (full) load_block16(msg, q);
   for (uint64_t blk = 0; blk < full; ++blk) {
@@ -131,9 +132,45 @@ __global__ __launch_bounds__(64) void sha256_kernel(Sha256Args a) {
     }
     compress(st, w);
   }
+}
+
+template <int MPB>
+__global__ __launch_bounds__(64) void sha256_kernel(Sha256Args a) {
+  if (static_cast<int>(threadIdx.x) >= MPB) return;
+  const int idx = blockIdx.x * MPB + threadIdx.x;
+  if (idx >= a.count) return;
+  uint32_t st[8];
+  hash_message(a.msgs[idx], a.lens[idx], st);
   uint32_t* o = a.digests + static_cast<size_t>(idx) * 8;
 #pragma unroll
   for (int i = 0; i < 8; ++i) o[i] = be32(st[i]);  // digest bytes in order
+}
+
+// The rows of one pipeline chunk (host_ragged.hpp), hashed where they lie in the chunk's device
+// mirror: lane idx takes entry idx of the chunk's message table, which the host wrote in
+// descending order of length so that the lanes of a wave end together. The entry's slot says
+// where the result goes: 32 digest bytes, or (with `expected`) one flag byte, 1 where the
+// digest differs from the slot's expected 32 bytes. A full wave per 64 messages: a wave's
+// time is its longest lane's whatever the lane count, so fewer lanes per wave gain nothing
+// while the chunk's waves number fewer than the chip's SIMDs.
+__global__ __launch_bounds__(64) void sha256_rows(Sha256RowsArgs a) {
+  const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
+  if (idx >= a.count) return;
+  const uint32_t* e = a.table + 3u * idx;
+  const uint32_t len = e[1], slot = e[2];
+  uint32_t st[8];
+  hash_message(a.base + static_cast<size_t>(e[0]) * 16u, len, st);
+  if (a.expected) {
+    const uint32_t* x = a.expected + static_cast<size_t>(slot) * 8;
+    uint32_t diff = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) diff |= be32(st[i]) ^ x[i];
+    static_cast<uint8_t*>(a.out)[slot] = diff != 0;
+  } else {
+    uint32_t* o = static_cast<uint32_t*>(a.out) + static_cast<size_t>(slot) * 8;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = be32(st[i]);
+  }
 }
 
 }  // namespace
@@ -150,6 +187,12 @@ hipError_t launch_sha256(const Sha256Args& a, int msgs_per_wave, hipStream_t str
     default:
       return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_sha256_rows(const Sha256RowsArgs& a, hipStream_t stream) {
+  if (a.count == 0) return hipSuccess;
+  hipLaunchKernelGGL(sha256_rows, dim3((a.count + 63u) / 64u), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -445,6 +445,120 @@ class Codec:
                 errors[b] = _decode_error(st[j])
         return objects, errors
 
+    def encode_many_sums(self, datas: Sequence, profile: ErasureProfile
+                         ) -> Tuple[List[Optional[List[memoryview]]], List[Optional[List[str]]],
+                                    List[Optional[Exception]]]:
+        """encode_many with every shard's checksum taken on the way through the pipeline
+        (rs_codec_encode_batch_sums): what Manager.StoreFile computes with
+        ShardChecksum beside Codec.Encode. Returns (shards_per_object, checksums_per_object,
+        errors): checksums_per_object[b][i] is the 64-character hex string shard_checksum()
+        returns for shard i of object b, or None where errors[b] is set."""
+        k, m = profile.data_shards, profile.parity_shards
+        if k < 1 or m < 1:
+            raise ErrInvalidProfile()
+        if k + m > 256:
+            raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create encoder")
+        n, B = k + m, len(datas)
+        srcs = [memoryview(d).cast("B") for d in datas]
+        outs = [bytearray(n * ((len(s) + k - 1) // k)) for s in srcs]
+        lens = (ctypes.c_size_t * max(B, 1))(*[len(s) for s in srcs])
+        caps = (ctypes.c_size_t * max(B, 1))(*[len(o) for o in outs])
+        sizes = (ctypes.c_size_t * max(B, 1))()
+        status = (ctypes.c_int * max(B, 1))()
+        digests = bytearray(max(B, 1) * n * 32)
+        rc = N.lib.rs_codec_encode_batch_sums(self.context.handle, k, m, B, _shard_ptrs(srcs or [None]),
+                                              lens, _shard_ptrs(outs or [None]), caps, sizes,
+                                              _addr(digests), status)
+        st = list(status)[:B]
+        if rc != N.RS_OK and rc not in st:
+            raise N.NativeError(rc, "rs_codec_encode_batch_sums")  # call-level
+        shards, sums, errors = [], [], []
+        for b in range(B):
+            if st[b] == N.RS_OK:
+                S, mv = sizes[b], memoryview(outs[b])
+                shards.append([mv[i * S:(i + 1) * S] for i in range(n)])
+                sums.append([digests[(b * n + i) * 32:(b * n + i + 1) * 32].hex() for i in range(n)])
+                errors.append(None)
+                continue
+            shards.append(None)
+            sums.append(None)
+            errors.append(_wrapped(st[b], "erasure: failed to split data"
+                                   if st[b] == N.RS_E_SHORT_DATA else "erasure: failed to encode parity"))
+        return shards, sums, errors
+
+    def decode_many_sums(self, shards_per_object: Sequence[List], checksums_per_object: Sequence[Sequence],
+                         profile: ErasureProfile, original_sizes: Sequence[int]
+                         ) -> Tuple[List[Optional[bytearray]], List[List[int]], List[Optional[Exception]]]:
+        """decode_many with every present shard checked against its recorded checksum on the
+        way through the pipeline (rs_codec_decode_batch_sums): what
+        Manager.RetrieveFile does before Codec.Decode (manager.go:283-296). A present shard
+        whose SHA-256 differs from checksums_per_object[b][i] (hex, as shard_checksum() gives
+        it; entries of missing shards are ignored and may be None) counts as missing: it is
+        rebuilt in place (a writable buffer), the rest is verified and the object joined.
+        Returns (objects, bad_indices, errors): bad_indices[b] lists the shards of object b that
+        failed their checksum; errors[b] is what decode() would raise for the object with
+        those shards missing."""
+        k, m = profile.data_shards, profile.parity_shards
+        if k < 1 or m < 1:
+            raise ErrInvalidProfile()
+        n = k + m
+        if n > 256:
+            raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create decoder")
+        if len(original_sizes) != len(shards_per_object) or len(checksums_per_object) != len(shards_per_object):
+            raise ValueError("one original size and one checksum list per object")
+        B = len(shards_per_object)
+        errors: List[Optional[Exception]] = [None] * B
+        run = []  # the objects handed to the native call
+        for b, shards in enumerate(shards_per_object):
+            if len(shards) != n:
+                errors[b] = ErrTooFewShards(f"erasure: reconstruction failed: {ErrTooFewShards.text}")
+            elif int(original_sizes[b]) < 0 or len(checksums_per_object[b]) != n:
+                errors[b] = N.NativeError(N.RS_E_ARG, "erasure: decode")
+            else:
+                run.append(b)
+        R = len(run)
+        lens = (ctypes.c_size_t * max(R * n, 1))()
+        expected = bytearray(max(R, 1) * n * 32)
+        flat, bufs, outs = [], [], []
+        for j, b in enumerate(run):
+            shards = shards_per_object[b]
+            ln = [0 if s is None else len(s) for s in shards]
+            S = next((x for x in ln if x), 0)
+            cp = list(shards)
+            for i in range(n):
+                lens[j * n + i] = ln[i]
+                if ln[i] == 0 and S:
+                    cp[i] = bytearray(S)  # upstream Reconstruct allocates missing shards
+                elif ln[i]:
+                    if not _writable(cp[i]):
+                        raise TypeError("decode_many_sums rebuilds a corrupt shard in place: writable buffers")
+                    expected[(j * n + i) * 32:(j * n + i + 1) * 32] = bytes.fromhex(checksums_per_object[b][i])
+            bufs.append(cp)
+            flat += cp
+            outs.append(bytearray(int(original_sizes[b])))
+        sizes = (ctypes.c_int64 * max(R, 1))(*[int(original_sizes[b]) for b in run])
+        status = (ctypes.c_int * max(R, 1))()
+        bad = bytearray(max(R, 1) * n)
+        rc = N.lib.rs_codec_decode_batch_sums(self.context.handle, k, m, R, _shard_ptrs(flat or [None]), lens,
+                                              _addr(expected), _shard_ptrs(outs or [None]), sizes,
+                                              _addr(bad), status)
+        st = list(status)[:R]
+        if rc != N.RS_OK and rc not in st:
+            raise N.NativeError(rc, "rs_codec_decode_batch_sums")  # call-level
+        objects: List[Optional[bytearray]] = [None] * B
+        bad_indices: List[List[int]] = [[] for _ in range(B)]
+        for j, b in enumerate(run):
+            shards = shards_per_object[b]
+            bad_indices[b] = [i for i in range(n) if bad[j * n + i]]
+            if st[j] in (N.RS_OK, N.RS_E_CORRUPT, N.RS_E_INSUFFICIENT):
+                for i in range(n):
+                    if (shards[i] is None or len(shards[i]) == 0) and lens[j * n + i]:
+                        shards[i] = bufs[j][i]
+            if st[j] == N.RS_OK:
+                objects[b] = outs[j]
+            else:
+                errors[b] = _decode_error(st[j])
+        return objects, bad_indices, errors
 
     def overwrite(self, shards: List, profile: ErasureProfile, offset: int, data) -> None:
         """rs_codec_overwrite: bytes [offset, offset + len(data)) of the object

@@ -192,6 +192,42 @@ int rs_codec_decode_batch(rs_ctx* ctx, int k, int m, int batch,
                           uint8_t* const* shards, size_t* lens,
                           uint8_t* const* out, const int64_t* original_sizes, int* status);
 
+/* ---- Checksummed codec batches -----------------------------------
+ * The batches above with ShardChecksum (SHA-256, codec.go:81-84) of every shard taken on
+ * the way through the pipeline: what Manager.StoreFile computes beside Codec.Encode
+ * (manager.go:185) and what Manager.RetrieveFile checks before Codec.Decode
+ * (manager.go:283-296). They take the ragged pipeline's staged transport whatever the
+ * batch holds. A shard that passes through a chunk whole is hashed in the chunk's device
+ * mirror or by the library's copy threads (CALLFS_RS_SUMS_DEVICE = auto / 0 / 1); a shard
+ * cut over several chunks is hashed by the copy threads. Both give the same bytes.
+ * rs_codec_encode_batch_sums: rs_codec_encode_batch (same bytes in shards_out, same
+ *   shard_sizes, statuses, precedence and overlap rules), and digests[(b*n + i)*32 ..] holds
+ *   the SHA-256 of shard i of object b over all S_b bytes, the zero pad included. digests
+ *   has batch*n*32 bytes; entries are written for objects of status RS_OK alone.
+ * rs_codec_decode_batch_sums: expected has batch*n*32 bytes (entries of missing shards are
+ *   ignored), bad batch*n bytes. Admission is rs_codec_decode_batch's on the shards as given
+ *   (a present shard of the wrong length is RS_E_SHARD_SIZE, where the manager would see a
+ *   checksum mismatch: drop such a shard before the call). For an admitted object every
+ *   entry of bad is written: 1 for a present shard whose SHA-256 differs from its expected
+ *   digest, else 0; it is 0 for objects refused at admission. A bad shard counts as missing:
+ *   from there the object's outcome, status and precedence are rs_codec_decode_batch's with
+ *   that shard's length zero (it is rebuilt into its own buffer, Verify runs over what is
+ *   left, out[b] is joined and trimmed). With fewer than k good shards left status[b] is
+ *   RS_E_TOO_FEW_SHARDS and the object's buffers and lens are left as given. Rebuilt shards
+ *   are not checked against their expected digests.
+ * Both: call-level errors and batch == 0 as above; digests, expected and bad are arrays
+ * like the others (NULL with batch > 0: RS_E_ARG). rs_host_counters: `launches` also counts
+ * one per chunk hashed on the device; a call without a mismatch enqueues the copies of the
+ * plain call on the same transport, and the objects with a mismatch run a second time. */
+int rs_codec_encode_batch_sums(rs_ctx* ctx, int k, int m, int batch,
+                               const uint8_t* const* data, const size_t* lens,
+                               uint8_t* const* shards_out, const size_t* out_caps,
+                               size_t* shard_sizes, uint8_t* digests, int* status);
+int rs_codec_decode_batch_sums(rs_ctx* ctx, int k, int m, int batch,
+                               uint8_t* const* shards, size_t* lens, const uint8_t* expected,
+                               uint8_t* const* out, const int64_t* original_sizes,
+                               uint8_t* bad, int* status);
+
 /* ---- Only the shards a caller asks for --------------------------
  * Upstream ReconstructSome(shards, required) and ReconstructData for host memory. A download
  * keeps the joined data alone and a repair wants the one shard its node lost: these calls

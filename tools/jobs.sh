@@ -432,6 +432,21 @@ cd "$(dirname "$JOBS")/.." || exit $?
 timeout -k 10 400 python3 -u tools/ragged_bench.py "$@" || exit $?
 }
 
+# Checksummed codec batches (tools/sums_bench.py): shard sizes 256 B..256 KiB,
+# RS(10,4) and RS(16,4), 64 MiB of objects per call on the staged transport, the shards hashed
+# by the copy pool's threads (CALLFS_RS_SUMS_DEVICE=0) against sha256_rows in every chunk (=1)
+# and against the plain batch call followed by hashlib on 16 threads; encode and clean decode.
+# One process per (shape, route), two warm-up calls and five timed ones each, the whole list
+# twice. Output: <out dir>/sums.jsonl (the lines kept in profiles/r08/sums/).
+# Usage: bash tools/jobs.sh sums_bench <out dir> [sums_bench.py args]
+job_sums_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+O=${1:-sums_out}; mkdir -p "$O" || exit $?
+shift
+timeout -k 10 1100 python3 -u tools/sums_bench.py --out "$O/sums.jsonl" "$@" > "$O/sums.log" 2>&1; rc=$?
+tail -80 "$O/sums.log"; exit $rc
+}
+
 # The codec-level batch calls against the routes they replace (tools/host_batch_bench.py --codec,
 # DESIGN.md §7.6): workloads W0-W3 as objects, encode and decode, pageable and pinned buffers.
 # PARENT_LIB: the parent commit's libcallfs_rs.so (timed as a loop of single-object calls and as
