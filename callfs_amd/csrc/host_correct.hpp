@@ -1,41 +1,13 @@
 // Correct on host memory: rs_correct, rs_correct_batch and the correction
-// step of rs_codec_decode_correct are the locate route of host_locate.hpp with launch_correct
-// in launch_locate's place. A chunk's counts come back first; then only the (item, shard) rows
-// whose count is nonzero -- the rows the launch changed -- are copied from the slot's device
-// mirror into the caller's shards, one D2H each. A chunk of clean stripes copies no shard byte
-// back. Included by rs_host.cpp only.
+// step of rs_codec_decode_correct are the locate route of host_locate.hpp as a correct run:
+// launch_correct in launch_locate's place, and the rows a launch changed copied back into the
+// caller's shards. Included by rs_host.cpp only.
 #pragma once
 
 #include "host_locate.hpp"
 
 namespace callfs {
 namespace {
-
-// After a chunk: input row i of an item is its pattern's valid[i], row k + x its compared shard
-// x (as staged by run_locate_chunks). shards: the call's, batch * (k + m).
-struct CorrectBack {
-  uint8_t* const* shards;
-  int operator()(const LocateRun& r, const ChunkLayout& C, const std::vector<RaggedItem>& items,
-                 const uint8_t* d, const uint64_t* cn) const {
-    const size_t k = static_cast<size_t>(r.k), n = static_cast<size_t>(r.k + r.m), nb = r.bins();
-    for (size_t j = 0; j < C.count; ++j) {
-      const RaggedItem& it = items[C.first + j];
-      const ItemLayout& il = C.items[j];
-      const size_t id = static_cast<size_t>(r.ids[static_cast<size_t>(it.stripe)]);
-      const uint32_t p = r.mt().pat[static_cast<size_t>(it.stripe)];
-      const MixedPattern& pt = r.mt().patterns[p];
-      const size_t rows = r.t.rows(p);
-      for (size_t row = 0; row < k + rows; ++row) {
-        const size_t shard = static_cast<size_t>(row < k ? pt.valid[row] : pt.rows[row - k]);
-        if (cn[j * nb + shard] == 0) continue;
-        HIPCHK(hipMemcpy(shards[id * n + shard] + it.off, d + il.in_off + il.pitch * row, it.w,
-                         hipMemcpyDeviceToHost));
-        r.ctx->n_copies.fetch_add(1, std::memory_order_relaxed);
-      }
-    }
-    return RS_OK;
-  }
-};
 
 // Shared by rs_correct, rs_correct_batch and rs_codec_decode_correct: locate_batch_host's
 // admission (a stripe of exactly k present shards is RS_OK with zero counts and no device
@@ -60,7 +32,7 @@ int correct_batch_host(rs_ctx* ctx, int k, int m, int batch, uint8_t* const* sha
   std::vector<int> flags(B, 0);
   const int rc = run_locate(ctx, k, m, 1, ids, S.data(), present.data(),
                             [&](int b, int i) { return shards[static_cast<size_t>(b) * n + i]; }, counts,
-                            flags.data(), /*correct=*/true, CorrectBack{shards});
+                            flags.data(), /*repair=*/shards);
   if (rc) return rc;
   for (size_t b = 0; b < B; ++b)
     if (counts[b * (n + 1) + n] != 0) status[b] = RS_E_CORRUPT;

@@ -4,12 +4,12 @@
 // row (host_path.hpp kShard*) says which shards are present, wanted or left alone; a call
 // without a wanted set is the all-wanted case of the same code. It owns the runs of
 // a call (RaggedRun), their pattern tables on a lane, the staged, in-place and direct
-// transports, the chunk loop over a lane's slots (run_ragged_chunks) and run_ragged, which
-// picks the device and the lane. Included by rs_host.cpp only.
+// transports, the ragged job of the one chunk pipeline (RaggedJob; host_chunks.hpp has the
+// slot rotation) and run_ragged, which picks the device and the lane. Included by rs_host.cpp
+// only.
 #pragma once
 
-#include "host_common.hpp"
-#include "ragged_chunks.hpp"
+#include "host_chunks.hpp"
 #include "sha256.hpp"
 
 namespace callfs {
@@ -50,55 +50,25 @@ std::string ragged_key(const RaggedRun& r) {
   return key;
 }
 
-// The run's nibble-table arenas and compare masks in the lane's device buffer, per launch
-// group [vmask][arena]; uploaded when the lane last held another run's.
-struct RaggedDevTables {
-  std::vector<size_t> vmask_off, arena_off;
-};
-int upload_ragged_tables(const RaggedRun& r, Lane& L, RaggedDevTables& dt) {
-  Packer pk;
+// The run's compare masks and nibble-table arenas in the lane's device buffer, per launch group
+// [vmask][arena] (off[2 * gi], off[2 * gi + 1]); uploaded when the lane last held another run's.
+int upload_ragged_tables(const RaggedRun& r, Lane& L, std::vector<size_t>& off) {
+  std::vector<TablePiece> pieces;
   for (const MixedGroup& g : r.mt.groups) {
-    dt.vmask_off.push_back(pk.take(sizeof(uint32_t) * g.vmask.size()));
-    dt.arena_off.push_back(pk.take(g.arena.size()));
+    pieces.push_back({g.vmask.data(), sizeof(uint32_t) * g.vmask.size()});
+    pieces.push_back({g.arena.data(), g.arena.size()});
   }
-  std::string key = ragged_key(r);
-  if (L.rag_tabs.p && L.rag_key == key) return RS_OK;
-  L.rag_key.clear();
-  if (const int rc = L.rag_tabs.ensure(pk.off)) return rc;
-  std::vector<uint8_t> h(pk.off, 0);
-  for (size_t gi = 0; gi < r.mt.groups.size(); ++gi) {
-    const MixedGroup& g = r.mt.groups[gi];
-    std::memcpy(h.data() + dt.vmask_off[gi], g.vmask.data(), sizeof(uint32_t) * g.vmask.size());
-    std::memcpy(h.data() + dt.arena_off[gi], g.arena.data(), g.arena.size());
-  }
-  HIPCHK(hipMemcpy(L.rag_tabs.p, h.data(), h.size(), hipMemcpyHostToDevice));
-  r.ctx->n_copies.fetch_add(1, std::memory_order_relaxed);
-  L.rag_key = std::move(key);
-  return RS_OK;
+  return upload_lane_tables(r.ctx, L.rag_tabs, L.rag_key, ragged_key(r), pieces, off);
 }
 
 // launch_ragged of every launch group over the chunk laid out by C at `base` (device-visible).
 hipError_t launch_ragged_chunk(const RaggedRun& r, const ChunkLayout& C, uint8_t* base,
-                               const uint8_t* tabs, const RaggedDevTables& dt, hipStream_t s) {
+                               const uint8_t* tabs, const std::vector<size_t>& off, hipStream_t s) {
   for (size_t gi = 0; gi < r.mt.groups.size(); ++gi) {
     const MixedGroup& g = r.mt.groups[gi];
-    ApplyArgs a{};
-    a.in_tab = reinterpret_cast<const uint8_t* const*>(base + C.in_tab_off);
-    a.out_tab = reinterpret_cast<uint8_t* const*>(base + C.out_tab_off[gi]);
-    a.ltabs = tabs + dt.arena_off[gi];
-    a.status = reinterpret_cast<int*>(base + C.status_off);
-    a.status_stride = 1;
-    a.K = r.k;
-    a.R = g.R;
-    a.batch = static_cast<int>(C.count);
     RaggedArgs x{};
-    x.pat = reinterpret_cast<const uint32_t*>(base + C.pat_off);
-    x.vmask = reinterpret_cast<const uint32_t*>(tabs + dt.vmask_off[gi]);
-    x.size = reinterpret_cast<const uint64_t*>(base + C.size_off);
-    x.tile0 = reinterpret_cast<const uint32_t*>(base + C.tile0_off);
-    x.tile_stripe = reinterpret_cast<const uint32_t*>(base + C.tile_stripe_off);
-    x.tab_stride = static_cast<uint32_t>(g.tab_stride);
-    x.ntiles = C.ntiles;
+    const ApplyArgs a = chunk_launch_args(C, base, gi, r.k, g.R, tabs + off[2 * gi + 1], g.tab_stride, x);
+    x.vmask = reinterpret_cast<const uint32_t*>(tabs + off[2 * gi]);
     const hipError_t e = launch_ragged(a, x, nullptr, C.any_tail, s);
     if (e != hipSuccess) return e;
   }
@@ -109,23 +79,18 @@ hipError_t launch_ragged_chunk(const RaggedRun& r, const ChunkLayout& C, uint8_t
 // output region), launch_ragged per launch group on the slot's device mirror, the hash launch
 // of a chunk that carries a message table (sha256_rows over the rows where they lie), one D2H
 // of the output region, then the slot's event.
-struct RaggedStaged {
+struct RaggedStaged : StagedSlots {
   const RaggedRun& r;
   Lane& L;
-  RaggedDevTables dt;
-  int prepare_run() { return upload_ragged_tables(r, L, dt); }
-  int prepare(Slot& sl, size_t bytes) {
-    if (const int rc = sl.dev.ensure(bytes)) return rc;
-    return sl.host.ensure(bytes);
-  }
-  uint8_t* staging(Slot& sl) const { return static_cast<uint8_t*>(sl.host.p); }
-  uint8_t* base(Slot& sl) const { return static_cast<uint8_t*>(sl.dev.p); }
+  std::vector<size_t> tab_off;
+  RaggedStaged(const RaggedRun& run, Lane& lane) : r(run), L(lane) {}
+  int prepare_run() { return upload_ragged_tables(r, L, tab_off); }
   int send(Slot& sl, const ChunkLayout& C) const {
     uint8_t* h = staging(sl);
     uint8_t* d = base(sl);
     const size_t head = C.status_off + sizeof(int) * C.count;
     HIPCHK(hipMemcpyAsync(d, h, head, hipMemcpyHostToDevice, sl.stream));
-    HIPCHK(launch_ragged_chunk(r, C, d, static_cast<const uint8_t*>(L.rag_tabs.p), dt, sl.stream));
+    HIPCHK(launch_ragged_chunk(r, C, d, static_cast<const uint8_t*>(L.rag_tabs.p), tab_off, sl.stream));
     if (C.sums_count) {
       Sha256RowsArgs a{};
       a.base = d;
@@ -140,10 +105,6 @@ struct RaggedStaged {
                           hipMemcpyDeviceToHost, sl.stream));
     HIPCHK(hipEventRecord(sl.done, sl.stream));
     r.count(1, 2);
-    return RS_OK;
-  }
-  int wait(Slot& sl) const {
-    HIPCHK(hipEventSynchronize(sl.done));
     return RS_OK;
   }
 };
@@ -161,35 +122,28 @@ struct RaggedInplace {
 
   int prepare_run() {
     const size_t P = r.mt.patterns.size();
-    Packer pk;
+    std::vector<TablePiece> pieces;  // built by the fill below, on an upload alone
     for (const MixedGroup& g : r.mt.groups) {
       pstride.push_back(4u + static_cast<uint32_t>(r.k) * g.R * kTabWords);
-      tab_off.push_back(pk.take(sizeof(uint32_t) * pstride.back() * P));
+      pieces.push_back({nullptr, sizeof(uint32_t) * pstride.back() * P});
     }
-    std::string key = ragged_key(r);
-    if (L.rag_small_tabs.p && L.rag_small_key == key) return RS_OK;
-    L.rag_small_key.clear();
-    if (const int rc = L.rag_small_tabs.ensure(pk.off)) return rc;
-    std::vector<uint8_t> h(pk.off, 0);
-    for (size_t gi = 0; gi < r.mt.groups.size(); ++gi) {
-      const MixedGroup& g = r.mt.groups[gi];
-      const size_t W = static_cast<size_t>(nibble_width(g.R));
-      for (size_t p = 0; p < P; ++p) {
-        auto* blk = reinterpret_cast<uint32_t*>(h.data() + tab_off[gi]) + p * pstride[gi];
-        blk[0] = g.vmask[p];
-        blk[1] = static_cast<uint32_t>(r.mt.patterns[p].missing);
-        for (int i = 0; i < r.k; ++i)
-          for (int row = 0; row < g.R; ++row) {
-            // the coefficient is entry 1 of the low nibble table: c * 1
-            const uint8_t c = g.arena[p * g.tab_stride + static_cast<size_t>(i) * 32u * W + W + row];
-            perm_tables(c, blk + 4 + (static_cast<size_t>(i) * g.R + row) * kTabWords);
-          }
+    return upload_lane_tables(r.ctx, L.rag_small_tabs, L.rag_small_key, ragged_key(r), pieces, tab_off, [&](uint8_t* h) {
+      for (size_t gi = 0; gi < r.mt.groups.size(); ++gi) {
+        const MixedGroup& g = r.mt.groups[gi];
+        const size_t W = static_cast<size_t>(nibble_width(g.R));
+        for (size_t p = 0; p < P; ++p) {
+          auto* blk = reinterpret_cast<uint32_t*>(h + tab_off[gi]) + p * pstride[gi];
+          blk[0] = g.vmask[p];
+          blk[1] = static_cast<uint32_t>(r.mt.patterns[p].missing);
+          for (int i = 0; i < r.k; ++i)
+            for (int row = 0; row < g.R; ++row) {
+              // the coefficient is entry 1 of the low nibble table: c * 1
+              const uint8_t c = g.arena[p * g.tab_stride + static_cast<size_t>(i) * 32u * W + W + row];
+              perm_tables(c, blk + 4 + (static_cast<size_t>(i) * g.R + row) * kTabWords);
+            }
+        }
       }
-    }
-    HIPCHK(hipMemcpy(L.rag_small_tabs.p, h.data(), h.size(), hipMemcpyHostToDevice));
-    r.ctx->n_copies.fetch_add(1, std::memory_order_relaxed);
-    L.rag_small_key = std::move(key);
-    return RS_OK;
+    });
   }
   int prepare(Slot& sl, size_t bytes) {
     done_off = round_up(bytes, 256);
@@ -233,11 +187,10 @@ struct RaggedInplace {
   }
 };
 
-// The chunk loop of a ragged run, in the style of run_chunks: chunks rotate through the
-// lane's slots; per chunk the metadata is written and the input rows are copied into the
-// slot's staging, the transport sends it, and the output rows of the chunk the slot held
-// before are copied out first. in / out take a stripe of the call's runnable
-// list and a shard index; flags (per runnable stripe) receive 1 where a compared row
+// The ragged job of the chunk pipeline (host_chunks.hpp): per chunk the metadata is written and
+// the input rows are copied into the slot's staging, the transport sends it, and the output rows
+// come out of the staging when the chunk has landed. in / out take a stripe of the call's
+// runnable list and a shard index; flags (per runnable stripe) receive 1 where a compared row
 // mismatched.
 // A checksummed codec batch (r.sums): a chunk with a message table gets it and -- a decode --
 // its slots' expected digests written beside the metadata, and its digests or flags are read
@@ -247,43 +200,48 @@ struct RaggedInplace {
 // stripe with a mismatch (the caller runs it again): the join of a device-checked item's
 // present data shards therefore waits for the chunk's flags and is copied from its staging.
 template <class Transport, class InF, class OutF>
-int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>& items,
-                      const std::vector<ChunkLayout>& chunks, Transport& tr, InF& in, OutF& out,
-                      int* flags) {
-  int rc;
-  if ((rc = tr.prepare_run())) return rc;
-  size_t bytes = 0;
-  for (const ChunkLayout& C : chunks) bytes = std::max(bytes, C.out_end);
-  const size_t nchunks = chunks.size();
-  const size_t nslots = std::min<size_t>(nchunks, static_cast<size_t>(pipeline_slots()));
-  for (size_t si = 0; si < nslots; ++si) {
-    if ((rc = tr.prepare(L.slot[si], bytes))) return rc;
-    L.slot[si].pending = false;
-  }
+struct RaggedJob {
+  const RaggedRun& r;
+  const std::vector<RaggedItem>& items;
+  Transport& tr;
+  InF& in;
+  OutF& out;
+  int* flags;
   const size_t k = static_cast<size_t>(r.k);
-  std::vector<CopyPool::Seg> segs;
   const SumsCall* sums = r.sums;
   const bool check = sums && sums->mode == SumsMode::kCheck;
-  std::vector<SumsTask> tasks;
+  std::vector<SumsTask> tasks;  // host hashes, gathered by collect and stage
+
+  int prepare_run() { return tr.prepare_run(); }
+  size_t staging_bytes(const ChunkLayout& C) const { return C.out_end; }
+  int prepare(Slot& sl, size_t bytes) { return tr.prepare(sl, bytes); }
+  int send(Slot& sl, const ChunkLayout& C) { return tr.send(sl, C); }
+  int wait(Slot& sl) { return tr.wait(sl); }
+  // an encode's host-hashed stripes that just completed: their rows are in the caller's buffers
+  int landed() { return run_tasks(); }
+  int run_tasks() {
+    run_sums_tasks(r.ctx->pool, tasks);
+    tasks.clear();
+    return RS_OK;
+  }
+
   // the shards of stripe s that are hashed, by the pattern: valid[], the compared rows and
   // (an encode) the written rows
-  auto hashed_shards = [&](int s, auto&& fn) {
+  template <class F>
+  void hashed_shards(int s, F&& fn) const {
     const MixedPattern& pt = r.pattern(s);
     for (int i : pt.valid) fn(i);
     for (size_t row = 0; row < pt.rows.size(); ++row)
       if (!check || row >= static_cast<size_t>(pt.missing)) fn(pt.rows[row]);
-  };
-  auto stripe_bad = [&](int s) {
+  }
+  bool stripe_bad(int s) const {
     bool any = false;
     hashed_shards(s, [&](int i) { any |= sums->bad[sums->at(r.ids[static_cast<size_t>(s)], i)] != 0; });
     return any;
-  };
-  auto on_host = [&](int s) { return sums && r.sums_host[static_cast<size_t>(s)]; };
-  auto drain = [&](Slot& sl) -> int {
-    if (!sl.pending) return RS_OK;
-    const int wrc = tr.wait(sl);
-    if (wrc) return wrc;
-    const ChunkLayout& C = chunks[sl.rag_chunk];
+  }
+  bool on_host(int s) const { return sums && r.sums_host[static_cast<size_t>(s)]; }
+
+  int collect(Slot& sl, const ChunkLayout& C, std::vector<CopyPool::Seg>& segs) {
     uint8_t* h = tr.staging(sl);
     const int* st = reinterpret_cast<const int*>(h + C.status_off);
     if (C.sums_count) {
@@ -317,20 +275,10 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
                         tee.first, tee.second});
       }
     }
-    sl.pending = false;
     return RS_OK;
-  };
-  for (size_t c = 0; c < nchunks; ++c) {
-    Slot& sl = L.slot[c % nslots];
-    segs.clear();
-    if ((rc = drain(sl))) return rc;
-    // the last chunk's output rows leave before this chunk's layout overwrites them (chunks
-    // of one run are laid out differently: its inputs may lie where those outputs were)
-    if (!segs.empty()) r.ctx->pool.run(segs);
-    segs.clear();
-    run_sums_tasks(r.ctx->pool, tasks);  // an encode's host-hashed stripes that just completed
-    tasks.clear();
-    const ChunkLayout& C = chunks[c];
+  }
+
+  int stage(Slot& sl, const ChunkLayout& C, std::vector<CopyPool::Seg>& segs) {
     uint8_t* h = tr.staging(sl);
     uint8_t* b = tr.base(sl);
     if (check) {
@@ -342,8 +290,7 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
           tasks.push_back(sums_task(*sums, id, i, in(id, i), r.sh.size[static_cast<size_t>(it.stripe)]));
         });
       }
-      run_sums_tasks(r.ctx->pool, tasks);
-      tasks.clear();
+      run_tasks();
     }
     // a row's address by the pattern's row number: written rows in the output part, compared
     // ones behind the k inputs
@@ -370,7 +317,6 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
       for (size_t row = static_cast<size_t>(pt.missing); row < pt.rows.size(); ++row)
         segs.push_back({row_at(h, j, static_cast<int>(row)), in(id, pt.rows[row]) + it.off, it.w});
     }
-    r.ctx->pool.run(segs);
     if (C.sums_count) {
       const std::vector<SumsSlot> slots = sums_slots(C, r.sh, items, r.mt);
       sums_fill_table(slots, reinterpret_cast<uint32_t*>(h + C.sums_tab_off));
@@ -378,18 +324,16 @@ int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>
         std::memcpy(h + C.sums_expect_off + 32 * s,
                     sums->expected + 32 * sums->at(r.ids[static_cast<size_t>(slots[s].stripe)], slots[s].shard), 32);
     }
-    if ((rc = tr.send(sl, C))) return rc;
-    sl.pending = true;
-    sl.rag_chunk = c;
+    return RS_OK;
   }
-  for (size_t c = nchunks - nslots; c < nchunks; ++c) {
-    segs.clear();
-    if ((rc = drain(L.slot[c % nslots]))) return rc;
-    r.ctx->pool.run(segs);
-    run_sums_tasks(r.ctx->pool, tasks);
-    tasks.clear();
-  }
-  return RS_OK;
+};
+
+template <class Transport, class InF, class OutF>
+int run_ragged_chunks(const RaggedRun& r, Lane& L, const std::vector<RaggedItem>& items,
+                      const std::vector<ChunkLayout>& chunks, Transport& tr, InF& in, OutF& out,
+                      int* flags) {
+  RaggedJob<Transport, InF, OutF> job{r, items, tr, in, out, flags};
+  return run_chunk_pipeline(r.ctx, L, chunks, job);
 }
 
 // Direct: every buffer of the run lies in rs_host_alloc memory. One metadata upload (the
@@ -407,9 +351,9 @@ int run_ragged_direct(const RaggedRun& r, Lane& L, InF& in, OutF& out, int* flag
   }
   if (ntiles > kRaggedMaxTiles) return RS_E_ARG;
   const ChunkLayout C = layout_chunk(r.sh, items, 0, items.size(), false);
-  RaggedStaged tabs{r, L, {}};
+  std::vector<size_t> tab_off;
   int rc;
-  if ((rc = tabs.prepare_run())) return rc;
+  if ((rc = upload_ragged_tables(r, L, tab_off))) return rc;
   Slot& sl = L.slot[0];
   if ((rc = sl.meta.ensure(C.out_end)) || (rc = sl.hmeta.ensure(C.out_end)) ||
       (rc = sl.hstat.ensure(sizeof(int) * C.count)))
@@ -430,7 +374,7 @@ int run_ragged_direct(const RaggedRun& r, Lane& L, InF& in, OutF& out, int* flag
                   [&](size_t j, int i) { return shard(j, r.pattern(static_cast<int>(j)).valid[static_cast<size_t>(i)]); },
                   [&](size_t j, int row) { return shard(j, r.pattern(static_cast<int>(j)).rows[static_cast<size_t>(row)]); });
   HIPCHK(hipMemcpyAsync(d, h, C.out_end, hipMemcpyHostToDevice, sl.stream));
-  HIPCHK(launch_ragged_chunk(r, C, d, static_cast<const uint8_t*>(L.rag_tabs.p), tabs.dt, sl.stream));
+  HIPCHK(launch_ragged_chunk(r, C, d, static_cast<const uint8_t*>(L.rag_tabs.p), tab_off, sl.stream));
   if (compares)
     HIPCHK(hipMemcpyAsync(sl.hstat.p, d + C.status_off, sizeof(int) * C.count, hipMemcpyDeviceToHost,
                           sl.stream));
@@ -505,53 +449,46 @@ int run_ragged_on_lane(rs_ctx* ctx, Lane& L, int device, int k, int m, bool by_m
       if (me == TableError::kSingular) return RS_E_SINGULAR;
       // every pattern of the class has its rows: the tables are what the kernels expect
       if (me != TableError::kOk || !mixed_rows_are(r.mt, cls.rows)) return RS_E_ARG;
-      r.sh.k = k;
-      for (const MixedGroup& g : r.mt.groups) r.sh.group_rows.push_back(g.R);
-      for (int s = 0; s < count; ++s) {
+      std::vector<size_t> sizes(r.ids.size());
+      for (size_t s = 0; s < sizes.size(); ++s) sizes[s] = S[static_cast<size_t>(r.ids[s])];
+      r.sh = ragged_shape(k, r.mt.groups, std::move(sizes), [&](int s) {
         const MixedPattern& pt = r.pattern(s);
-        r.sh.size.push_back(S[static_cast<size_t>(r.ids[static_cast<size_t>(s)])]);
-        r.sh.nin.push_back(k + static_cast<int>(pt.rows.size()) - pt.missing);
-        r.sh.nout.push_back(pt.missing);
-      }
+        return std::make_pair(k + static_cast<int>(pt.rows.size()) - pt.missing, pt.missing);
+      });
       int rc;
       if (direct) {
         if ((rc = run_ragged_direct(r, L, in, out, flags))) return rc;
         continue;
       }
-      const std::vector<RaggedItem> items = ragged_items(r.sh, chunk_bytes());
+      RaggedWork w(r.sh, chunk_bytes());
       if (sums) {
         // packed with the regions of the hash launch; the rule then takes them out of the
         // chunks that hash on the host
         const SumsKnob knob = sums_device_knob();
-        std::vector<ChunkLayout> chunks = ragged_chunks(r.sh, items, chunk_bytes(), true,
-                                                        knob == SumsKnob::kHost ? SumsMode::kNone : sums->mode);
-        r.sums_host = sums_route(r.sh, items, chunks, knob);
-        for (const ChunkLayout& C : chunks)
-          if (C.ntiles > kRaggedMaxTiles) return RS_E_ARG;
-        RaggedStaged tr{r, L, {}};
-        if ((rc = run_ragged_chunks(r, L, items, chunks, tr, in, out, flags))) return rc;
+        if (!w.cut(r.sh, chunk_bytes(), knob == SumsKnob::kHost ? SumsMode::kNone : sums->mode)) return RS_E_ARG;
+        r.sums_host = sums_route(r.sh, w.items, w.chunks, knob);
+        RaggedStaged tr(r, L);
+        if ((rc = run_ragged_chunks(r, L, w.items, w.chunks, tr, in, out, flags))) return rc;
         continue;
       }
       // the whole run as one in-place chunk on slot 0
-      if (items.size() <= kRaggedMaxItems && small_max_bytes() > 0) {
-        std::vector<ChunkLayout> one(1, layout_chunk(r.sh, items, 0, items.size()));
+      if (w.items.size() <= kRaggedMaxItems && small_max_bytes() > 0) {
+        std::vector<ChunkLayout> one(1, layout_chunk(r.sh, w.items, 0, w.items.size()));
         if (one[0].out_end <= small_max_bytes() && RaggedInplace::fits(one[0])) {
           RaggedInplace tr{r, L, {}, {}, 0};
-          if ((rc = run_ragged_chunks(r, L, items, one, tr, in, out, flags))) return rc;
+          if ((rc = run_ragged_chunks(r, L, w.items, one, tr, in, out, flags))) return rc;
           continue;
         }
       }
-      const std::vector<ChunkLayout> chunks = ragged_chunks(r.sh, items, chunk_bytes());
+      if (!w.cut(r.sh, chunk_bytes())) return RS_E_ARG;
       bool inplace = inplace_pipeline();
-      for (const ChunkLayout& C : chunks) inplace = inplace && RaggedInplace::fits(C);
-      for (const ChunkLayout& C : chunks)
-        if (C.ntiles > kRaggedMaxTiles) return RS_E_ARG;
+      for (const ChunkLayout& C : w.chunks) inplace = inplace && RaggedInplace::fits(C);
       if (inplace) {
         RaggedInplace tr{r, L, {}, {}, 0};
-        rc = run_ragged_chunks(r, L, items, chunks, tr, in, out, flags);
+        rc = run_ragged_chunks(r, L, w.items, w.chunks, tr, in, out, flags);
       } else {
-        RaggedStaged tr{r, L, {}};
-        rc = run_ragged_chunks(r, L, items, chunks, tr, in, out, flags);
+        RaggedStaged tr(r, L);
+        rc = run_ragged_chunks(r, L, w.items, w.chunks, tr, in, out, flags);
       }
       if (rc) return rc;
     }

@@ -6,7 +6,9 @@
 // ragged launch per launch group (ragged_tables.hpp, "stripe" meaning item). Also the split of
 // a call into classes by row count (a reconstruct without verification: by missing count), and
 // of a class into segments whose pattern tables stay within kRaggedArenaBudget. Both read the
-// kShard* flag rows that admission writes (host_path.hpp). Plain C++ with no HIP
+// kShard* flag rows that admission writes (host_path.hpp). The update and locate routes
+// (host_update.hpp, host_locate.hpp) cut their calls with the same ragged_segments over their own
+// flag rows and set a run up with the same ragged_shape and RaggedWork. Plain C++ with no HIP
 // dependence: tests/native/ragged_chunks_test.cpp builds it with g++ on the CPU.
 #pragma once
 
@@ -225,6 +227,48 @@ inline std::vector<ChunkLayout> ragged_chunks(const RaggedShape& sh, const std::
   return chunks;
 }
 
+// The shape of a run: k pointer slots per item, the launch groups' rows, the stripes' sizes and,
+// from rows_of(s) = {nin, nout}, the rows stripe s stages.
+template <class Groups, class RowsF>
+RaggedShape ragged_shape(int k, const Groups& groups, std::vector<size_t> sizes, RowsF rows_of) {
+  RaggedShape sh;
+  sh.k = k;
+  for (const auto& g : groups) sh.group_rows.push_back(g.R);
+  sh.size = std::move(sizes);
+  for (int s = 0; s < sh.stripes(); ++s) {
+    const std::pair<int, int> rows = rows_of(s);
+    sh.nin.push_back(rows.first);
+    sh.nout.push_back(rows.second);
+  }
+  return sh;
+}
+
+// A run's work list: its items, and once cut() its chunks.
+struct RaggedWork {
+  std::vector<RaggedItem> items;
+  std::vector<ChunkLayout> chunks;
+  RaggedWork(const RaggedShape& sh, size_t budget) : items(ragged_items(sh, budget)) {}
+  // Packs the items into chunks; false where a chunk has more tiles than a launch's grid holds.
+  bool cut(const RaggedShape& sh, size_t budget, SumsMode sums = SumsMode::kNone) {
+    chunks = ragged_chunks(sh, items, budget, true, sums);
+    for (const ChunkLayout& C : chunks)
+      if (C.ntiles > kRaggedMaxTiles) return false;
+    return true;
+  }
+};
+
+// The part of a chunk's metadata every tile-map kernel reads, at `h` (the start of its
+// staging): the items' sizes and the tile map over them.
+inline void fill_chunk_tile_map(const ChunkLayout& L, const std::vector<RaggedItem>& items, uint8_t* h) {
+  std::vector<size_t> widths(L.count);
+  auto* size = reinterpret_cast<uint64_t*>(h + L.size_off);
+  for (size_t j = 0; j < L.count; ++j) size[j] = widths[j] = items[L.first + j].w;
+  TileMap tm;
+  (void)build_tile_map(static_cast<int>(L.count), widths.data(), nullptr, tm);
+  std::memcpy(h + L.tile0_off, tm.tile0.data(), sizeof(uint32_t) * tm.tile0.size());
+  std::memcpy(h + L.tile_stripe_off, tm.tile_stripe.data(), sizeof(uint32_t) * tm.tile_stripe.size());
+}
+
 // Fills a chunk's metadata at `h` (the start of its staging). stripe_pat[b]: the pattern of
 // the run's stripe b in `mt`. in_ptr(j, i): the address the kernels read item j's input i
 // (the pattern's valid[i]) at; row_ptr(j, r): that of its row r (rows[r]: written for
@@ -236,11 +280,8 @@ void fill_chunk_meta(const ChunkLayout& L, const RaggedShape& sh, const std::vec
   const size_t k = static_cast<size_t>(sh.k);
   auto* in = reinterpret_cast<const uint8_t**>(h + L.in_tab_off);
   auto* pat = reinterpret_cast<uint32_t*>(h + L.pat_off);
-  std::vector<size_t> widths(L.count);
   for (size_t j = 0; j < L.count; ++j) {
-    const RaggedItem& it = items[L.first + j];
-    widths[j] = it.w;
-    pat[j] = stripe_pat[it.stripe];
+    pat[j] = stripe_pat[items[L.first + j].stripe];
     for (size_t i = 0; i < k; ++i) in[j * k + i] = in_ptr(j, static_cast<int>(i));
   }
   for (size_t gi = 0; gi < mt.groups.size(); ++gi) {
@@ -249,17 +290,12 @@ void fill_chunk_meta(const ChunkLayout& L, const RaggedShape& sh, const std::vec
     for (size_t j = 0; j < L.count; ++j)
       for (int r = 0; r < g.R; ++r) out[j * g.R + r] = row_ptr(j, g.row0 + r);
   }
-  TileMap tm;
-  (void)build_tile_map(static_cast<int>(L.count), widths.data(), nullptr, tm);
-  auto* size = reinterpret_cast<uint64_t*>(h + L.size_off);
-  for (size_t j = 0; j < L.count; ++j) size[j] = widths[j];
-  std::memcpy(h + L.tile0_off, tm.tile0.data(), sizeof(uint32_t) * tm.tile0.size());
-  std::memcpy(h + L.tile_stripe_off, tm.tile_stripe.data(), sizeof(uint32_t) * tm.tile_stripe.size());
+  fill_chunk_tile_map(L, items, h);
   auto* tab = reinterpret_cast<uint32_t*>(h + L.item_tab_off);
   for (size_t j = 0; j < L.count; ++j) {
     tab[4 * j + 0] = static_cast<uint32_t>(L.items[j].in_off / 16);
     tab[4 * j + 1] = static_cast<uint32_t>(L.items[j].out_off / 16);
-    tab[4 * j + 2] = static_cast<uint32_t>(widths[j]);
+    tab[4 * j + 2] = static_cast<uint32_t>(items[L.first + j].w);
     tab[4 * j + 3] = pat[j];
   }
   std::memset(h + L.status_off, 0, sizeof(int) * L.count);
@@ -311,20 +347,18 @@ inline size_t pattern_arena_bytes(int k, int rows) {
   return bytes;
 }
 
-// Cuts a class's stripe list into segments [begin, end) of consecutive entries whose distinct
-// patterns' tables stay within `budget` (one pattern always fits). A pattern is a stripe's whole
-// row of kShard* flags: the mask and the wanted missing shards.
-inline std::vector<std::pair<size_t, size_t>> ragged_segments(int k, int n, int rows,
+// Cuts a stripe list into segments [begin, end) of consecutive entries whose distinct patterns'
+// tables stay within `budget` (one pattern always fits). A pattern is a stripe's whole flag row,
+// `width` bytes at flags + stripe * width, and costs `per` bytes of tables.
+inline std::vector<std::pair<size_t, size_t>> ragged_segments(size_t width, size_t per,
                                                               const std::vector<int>& stripes,
                                                               const uint8_t* flags, size_t budget) {
-  const size_t per = pattern_arena_bytes(k, rows);
   const size_t max_patterns = std::max<size_t>(1, budget / std::max<size_t>(per, 1));
   std::vector<std::pair<size_t, size_t>> segs;
   std::set<std::string> seen;
   size_t begin = 0;
   for (size_t j = 0; j < stripes.size(); ++j) {
-    std::string key(reinterpret_cast<const char*>(flags + static_cast<size_t>(stripes[j]) * n),
-                    static_cast<size_t>(n));
+    std::string key(reinterpret_cast<const char*>(flags + static_cast<size_t>(stripes[j]) * width), width);
     if (!seen.count(key) && seen.size() == max_patterns) {
       segs.push_back({begin, j});
       begin = j;
@@ -334,6 +368,13 @@ inline std::vector<std::pair<size_t, size_t>> ragged_segments(int k, int n, int 
   }
   if (begin < stripes.size()) segs.push_back({begin, stripes.size()});
   return segs;
+}
+// A class of the ragged route: the pattern is the row of n kShard* flags (the mask and the
+// wanted missing shards), its tables those of `rows` rows.
+inline std::vector<std::pair<size_t, size_t>> ragged_segments(int k, int n, int rows,
+                                                              const std::vector<int>& stripes,
+                                                              const uint8_t* flags, size_t budget) {
+  return ragged_segments(static_cast<size_t>(n), pattern_arena_bytes(k, rows), stripes, flags, budget);
 }
 
 }  // namespace callfs

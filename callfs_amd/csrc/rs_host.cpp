@@ -10,7 +10,8 @@
 // wanted set (ReconstructSome / ReconstructData) or without, is admitted into the same kShard*
 // flag rows and takes the same path from there. Locate (which shard is corrupt, DESIGN.md
 // §5.12) runs through host_locate.hpp, and the heal calls compose it with the reconstructs;
-// correct (repair in place from the syndromes, §5.13) through host_correct.hpp. The checksummed
+// correct (repair in place from the syndromes, §5.13) through host_correct.hpp. The ragged,
+// update and locate routes are jobs of one chunk pipeline (host_chunks.hpp, §7.5). The checksummed
 // codec batches (§7.7) are the codec batches with a SumsCall handed to the ragged pipeline; what
 // they hash where, and a decode's follow-up run, are the HIP-free sums_table.hpp / sums_host.hpp.
 #include "codec_batch.hpp"

@@ -204,7 +204,7 @@ struct Slot {
   bool pending = false;  // a chunk's outputs wait in staging
   int b0 = 0, count = 0;  // its stripes
   size_t off = 0, width = 0;  // and columns
-  size_t rag_chunk = 0;       // the ragged chunk in flight (host_ragged.hpp run_ragged_chunks)
+  size_t rag_chunk = 0;       // the chunk in flight (host_chunks.hpp run_chunk_pipeline)
 };
 
 constexpr int kMaxSlots = 6;

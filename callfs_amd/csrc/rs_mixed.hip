@@ -590,24 +590,21 @@ const std::array<std::array<UpdateFn, 3>, 2> kUpdate = {{
     {kUpdateInstance<4, true>, kUpdateInstance<8, true>, kUpdateInstance<16, true>}}};
 
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
-// per-device attribute (dispatch.hpp DeviceOnce; key 0 the mixed instance, 1 the ragged one, 2 the
-// required one, 3 the single-source update instance, 4 the pair one, 5 the locate one, 6 the
-// pair locate one, 7 the correct one)
+// per-device attribute (dispatch.hpp DeviceOnce), keyed by the 16-row instance it is set on
+enum class WideLds { kMixed, kRagged, kRaggedSome, kUpdate, kUpdatePair, kLocate, kLocate2, kCorrect };
 DeviceOnce g_mixed_wide_lds;
 
-// The vector launch every kind shares: the dynamic-LDS opt-in (`once_key`: 0 the mixed
-// instance, 1 the ragged one, 2 the required one, 3 and 4 the update ones, 5 and 6 the locate ones, 7 the correct one),
-// then `grid` tiles
-// in equal consecutive slices of `streams` shard streams, as launch_apply cuts them. A slice
-// boundary may fall inside a stripe (tiles are numbered over the whole grid).
+// The vector launch every kind shares: the dynamic-LDS opt-in, then `grid` tiles in equal
+// consecutive slices of `streams` shard streams, as launch_apply cuts them. A slice boundary
+// may fall inside a stripe (tiles are numbered over the whole grid).
 template <class X>
-hipError_t launch_tiles(void (*fn)(ApplyArgs, X), int once_key, uint32_t grid, ApplyArgs& a,
+hipError_t launch_tiles(void (*fn)(ApplyArgs, X), WideLds once_key, uint32_t grid, ApplyArgs& a,
                         const X& x, int streams, hipStream_t stream, const LaunchEvents& ev) {
   const size_t lds = dev::lds_bytes(a.K, a.R > 8 ? 16 : 8);
   if (lds > (64u << 10)) {
     int device = -1;
     if (hipGetDevice(&device) != hipSuccess) return hipErrorInvalidDevice;
-    g_mixed_wide_lds.run(device, once_key, [fn] {
+    g_mixed_wide_lds.run(device, static_cast<int>(once_key), [fn] {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
     });
@@ -616,6 +613,15 @@ hipError_t launch_tiles(void (*fn)(ApplyArgs, X), int once_key, uint32_t grid, A
     dispatch(fn, dim3(blocks), dim3(kMixedBlock), lds, stream, ev, first, last, a, x);
   });
   return hipGetLastError();
+}
+
+// What every launch over a tile map (X: RaggedArgs or UpdateArgs) checks of its arguments: the
+// launch group's shape, the pointer tables and the map.
+template <class X>
+bool tile_map_ok(const ApplyArgs& a, const X& x) {
+  return a.R >= 1 && a.R <= kMaxRowsPerLaunch && a.K >= 1 && a.K <= kMaxK && a.batch >= 1 && a.ltabs &&
+         x.pat && x.size && x.tile0 && a.in_tab && a.out_tab && x.ntiles <= 0x7fffffffu &&
+         (x.ntiles == 0 || x.tile_stripe);
 }
 
 }  // namespace
@@ -638,15 +644,13 @@ hipError_t launch_mixed(ApplyArgs a, const MixedArgs& x, hipStream_t stream, Lau
   const uint64_t tps = (a.nvec + kMixedTileVecs - 1) / kMixedTileVecs;
   const uint64_t ntiles = tps * static_cast<uint64_t>(a.batch);
   if (ntiles > 0x7fffffffull) return hipErrorInvalidValue;
-  return launch_tiles(kMixed[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], 0, static_cast<uint32_t>(ntiles), a, x,
+  return launch_tiles(kMixed[a.R > 8 ? 2 : a.R > 4 ? 1 : 0], WideLds::kMixed, static_cast<uint32_t>(ntiles), a, x,
                       a.K + a.R, stream, ev);
 }
 
 hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, const uint32_t* nrows, bool any_tail,
                          hipStream_t stream, LaunchEvents ev) {
-  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
-      !x.pat || !x.vmask || !x.size || !x.tile0 || !a.in_tab || !a.out_tab || !a.status ||
-      x.ntiles > 0x7fffffffu || (x.ntiles && !x.tile_stripe) ||
+  if (!tile_map_ok(a, x) || !x.vmask || !a.status ||
       (!nrows && x.ntiles < static_cast<uint32_t>(a.batch)))  // without row counts every stripe has a tile
     return hipErrorInvalidValue;
   if (x.ntiles == 0) return hipSuccess;  // no stripe has a row in this launch group
@@ -656,21 +660,19 @@ hipError_t launch_ragged(ApplyArgs a, const RaggedArgs& x, const uint32_t* nrows
   // with no tail leave lds_tail at once
   a.tail_in_vec = any_tail ? 1u : 0u;
   const int inst = a.R > 8 ? 2 : a.R > 4 ? 1 : 0;
-  return nrows ? launch_tiles(kRaggedSome[inst], 2, x.ntiles, a, RaggedSomeArgs{x, nrows}, a.K + a.R, stream, ev)
-               : launch_tiles(kRagged[inst], 1, x.ntiles, a, x, a.K + a.R, stream, ev);
+  return nrows ? launch_tiles(kRaggedSome[inst], WideLds::kRaggedSome, x.ntiles, a, RaggedSomeArgs{x, nrows},
+                              a.K + a.R, stream, ev)
+               : launch_tiles(kRagged[inst], WideLds::kRagged, x.ntiles, a, x, a.K + a.R, stream, ev);
 }
 
 namespace {
 
 // launch_locate and launch_correct: `fns` with the dynamic-LDS key `once_key`
-hipError_t launch_locate_kind(const std::array<LocateFn, 3>& fns, int once_key, ApplyArgs a, const LocateArgs& x,
+hipError_t launch_locate_kind(const std::array<LocateFn, 3>& fns, WideLds once_key, ApplyArgs a, const LocateArgs& x,
                               bool any_tail, hipStream_t stream, LaunchEvents ev, int max_errors) {
   const RaggedArgs& r = x.r;
-  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
-      !r.pat || !r.vmask || !r.size || !r.tile0 || !a.in_tab || !a.out_tab || !a.status ||
-      r.ntiles > 0x7fffffffu || (r.ntiles && !r.tile_stripe) || !x.nrows || !x.gf || !x.loc ||
-      !x.counts || max_errors < 1 || max_errors > 2 || x.loc_stride != locate_stride(a.K, max_errors) ||
-      x.nbins < 2)
+  if (!tile_map_ok(a, r) || !r.vmask || !a.status || !x.nrows || !x.gf || !x.loc || !x.counts ||
+      max_errors < 1 || max_errors > 2 || x.loc_stride != locate_stride(a.K, max_errors) || x.nbins < 2)
     return hipErrorInvalidValue;
   if (r.ntiles == 0) return hipSuccess;  // no stripe has a row
   a.t_base = 0;
@@ -683,21 +685,18 @@ hipError_t launch_locate_kind(const std::array<LocateFn, 3>& fns, int once_key, 
 
 hipError_t launch_locate(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
                          LaunchEvents ev, int max_errors) {
-  return max_errors == 2 ? launch_locate_kind(kLocate2, 6, a, x, any_tail, stream, ev, 2)
-                         : launch_locate_kind(kLocate, 5, a, x, any_tail, stream, ev, max_errors);
+  return max_errors == 2 ? launch_locate_kind(kLocate2, WideLds::kLocate2, a, x, any_tail, stream, ev, 2)
+                         : launch_locate_kind(kLocate, WideLds::kLocate, a, x, any_tail, stream, ev, max_errors);
 }
 
 hipError_t launch_correct(ApplyArgs a, const LocateArgs& x, bool any_tail, hipStream_t stream,
                           LaunchEvents ev) {
-  return launch_locate_kind(kCorrect, 7, a, x, any_tail, stream, ev, 1);
+  return launch_locate_kind(kCorrect, WideLds::kCorrect, a, x, any_tail, stream, ev, 1);
 }
 
 hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_tail,
                          hipStream_t stream, LaunchEvents ev) {
-  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 1 || a.K > kMaxK || a.batch < 1 || !a.ltabs ||
-      !x.pat || !x.nsrc || !x.size || !x.tile0 || !a.in_tab || !a.out_tab ||
-      x.ntiles > 0x7fffffffu || (x.ntiles && !x.tile_stripe) ||
-      x.in_stride != static_cast<uint32_t>(a.K) * (pair ? 2u : 1u))
+  if (!tile_map_ok(a, x) || !x.nsrc || x.in_stride != static_cast<uint32_t>(a.K) * (pair ? 2u : 1u))
     return hipErrorInvalidValue;
   if (x.ntiles == 0) return hipSuccess;  // no stripe has a changed shard
   a.t_base = 0;
@@ -705,7 +704,8 @@ hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_t
   a.verify_mask = 0;
   a.tail_in_vec = any_tail ? 1u : 0u;  // wave 0 of each stripe's first tile
   // per tile: the sources (twice for pairs), and every row read and written
-  return launch_tiles(kUpdate[pair ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0], pair ? 4 : 3, x.ntiles, a, x,
+  return launch_tiles(kUpdate[pair ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0],
+                      pair ? WideLds::kUpdatePair : WideLds::kUpdate, x.ntiles, a, x,
                       a.K * (pair ? 2 : 1) + 2 * a.R, stream, ev);
 }
 

@@ -16,6 +16,10 @@ std::vector<std::vector<unsigned char>>& uploads() {
   static std::vector<std::vector<unsigned char>> u;
   return u;
 }
+AsyncCopies& async_copies() {
+  static AsyncCopies c;
+  return c;
+}
 }  // namespace fake_mem
 
 extern "C" {
@@ -42,8 +46,14 @@ hipError_t hipMemcpy(void* dst, const void* src, size_t n, hipMemcpyKind kind) {
   }
   return hipSuccess;
 }
-hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t) {
+hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t) {
   std::memcpy(dst, src, n);
+  if (kind == hipMemcpyHostToDevice) ++fake_mem::async_copies().h2d;
+  if (kind == hipMemcpyDeviceToHost) ++fake_mem::async_copies().d2h;
+  return hipSuccess;
+}
+hipError_t hipMemset(void* dst, int v, size_t n) {
+  std::memset(dst, v, n);
   return hipSuccess;
 }
 hipError_t hipMemsetAsync(void* dst, int v, size_t n, hipStream_t) {

@@ -10,4 +10,10 @@ namespace fake_mem {
 // The bytes of every host-to-device hipMemcpy, in order.
 std::vector<std::vector<unsigned char>>& uploads();
 
+// How many hipMemcpyAsync calls went each way.
+struct AsyncCopies {
+  long h2d = 0, d2h = 0;
+};
+AsyncCopies& async_copies();
+
 }  // namespace fake_mem

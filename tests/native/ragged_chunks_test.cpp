@@ -331,6 +331,85 @@ void check_all_wanted_rules(int k, int m, std::mt19937& rng) {
   }
 }
 
+// The form the update and locate routes call: a flag row of any width and the caller's own cost
+// per pattern. The expectation is written out from the rule (a segment ends before the row that
+// would be one distinct row more than max(1, budget / per)); the class form is this one at
+// width n and pattern_arena_bytes.
+void check_segments_of_any_row(int k, int m, std::mt19937& rng) {
+  const int n = k + m, stripes = 50;
+  for (const size_t width : {size_t(1), static_cast<size_t>(k), static_cast<size_t>(n)}) {
+    std::vector<uint8_t> rows(static_cast<size_t>(stripes) * width);
+    for (uint8_t& f : rows) f = static_cast<uint8_t>(rng() % 2);
+    for (int b = 5; b < stripes; b += 2) {  // repeats of earlier rows
+      const size_t src = rng() % static_cast<unsigned>(b);
+      std::copy(rows.begin() + src * width, rows.begin() + (src + 1) * width, rows.begin() + b * width);
+    }
+    std::vector<int> order(stripes);
+    for (int b = 0; b < stripes; ++b) order[b] = b;
+    std::shuffle(order.begin(), order.end(), rng);
+    order.resize(40);  // a call's runnable stripes: not every row is named
+    for (const size_t per : {size_t(0), size_t(1), size_t(1000), pattern_arena_bytes(k, m) + 77})
+      for (const size_t budget : {size_t(0), size_t(999), size_t(1000), size_t(3500), size_t(1) << 30}) {
+        const size_t cap = std::max<size_t>(1, budget / std::max<size_t>(per, 1));
+        std::vector<std::pair<size_t, size_t>> cuts;
+        std::vector<std::vector<uint8_t>> held;
+        size_t begin = 0;
+        for (size_t j = 0; j < order.size(); ++j) {
+          const std::vector<uint8_t> row(rows.begin() + order[j] * width, rows.begin() + (order[j] + 1) * width);
+          const bool known = std::find(held.begin(), held.end(), row) != held.end();
+          if (!known && held.size() == cap) {
+            cuts.push_back({begin, j});
+            begin = j;
+            held.clear();
+          }
+          if (!known) held.push_back(row);
+        }
+        cuts.push_back({begin, order.size()});
+        CHECK(ragged_segments(width, per, order, rows.data(), budget) == cuts);
+        if (width == static_cast<size_t>(n) && per == pattern_arena_bytes(k, m) + 77)
+          CHECK(ragged_segments(k, n, m, order, rows.data(), budget) ==
+                ragged_segments(width, pattern_arena_bytes(k, m), order, rows.data(), budget));
+      }
+    CHECK(ragged_segments(width, 1000, {}, rows.data(), 1000).empty());
+  }
+}
+
+// A run's set-up: the shape from the per-stripe rows, and the work list's items and chunks.
+void check_shape_and_work(int k, int m) {
+  struct G {
+    int R;
+  };
+  const std::vector<G> groups = {{16}, {3}};
+  const std::vector<size_t> sizes = {100003, 17, 8197, 40003, 9, 65536};
+  const RaggedShape sh = ragged_shape(k, groups, sizes, [&](int s) { return std::make_pair(k + s % 2, m - s % 2); });
+  CHECK(sh.k == k && sh.group_rows == std::vector<int>({16, 3}) && sh.size == sizes);
+  for (int s = 0; s < sh.stripes(); ++s) CHECK(sh.nin[s] == k + s % 2 && sh.nout[s] == m - s % 2);
+  const size_t budget = 64u << 10;
+  RaggedWork w(sh, budget);
+  CHECK(w.chunks.empty() && w.items.size() == ragged_items(sh, budget).size());
+  CHECK(w.cut(sh, budget));
+  const auto want = ragged_chunks(sh, w.items, budget);
+  CHECK(w.chunks.size() == want.size() && w.chunks.size() > 3);
+  for (size_t c = 0; c < want.size(); ++c)
+    CHECK(w.chunks[c].first == want[c].first && w.chunks[c].count == want[c].count &&
+          w.chunks[c].out_end == want[c].out_end && w.chunks[c].ntiles == want[c].ntiles);
+  // the tile-map part of the metadata is fill_chunk_meta's
+  for (const ChunkLayout& C : w.chunks) {
+    std::vector<uint8_t> h(C.out_end, 0xEE);
+    fill_chunk_tile_map(C, w.items, h.data());
+    const auto* size = reinterpret_cast<const uint64_t*>(h.data() + C.size_off);
+    const auto* tile0 = reinterpret_cast<const uint32_t*>(h.data() + C.tile0_off);
+    const auto* tile_stripe = reinterpret_cast<const uint32_t*>(h.data() + C.tile_stripe_off);
+    uint32_t t = 0;
+    for (size_t j = 0; j < C.count; ++j) {
+      CHECK(size[j] == w.items[C.first + j].w && tile0[j] == t);
+      for (uint64_t q = 0; q < ragged_tiles(w.items[C.first + j].w); ++q) CHECK(tile_stripe[t++] == j);
+    }
+    CHECK(tile0[C.count] == t && t == C.ntiles);
+    CHECK(h[C.in_tab_off] == 0xEE && h[C.pat_off] == 0xEE && h[C.status_off] == 0xEE);
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -361,6 +440,8 @@ int main() {
     }
     check_classes_and_segments(k, m, rng);
     check_all_wanted_rules(k, m, rng);
+    check_segments_of_any_row(k, m, rng);
+    check_shape_and_work(k, m);
   }
   // an RS(128,128) batch of 500 patterns stays within the arena budget per segment
   {

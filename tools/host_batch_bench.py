@@ -33,6 +33,11 @@ rs_reconstruct_batch + CPU join (one copy per object each way, the cheapest a ca
 A library that has rs_codec_decode_data_batch is also timed through it on the
 decode leg (route "data": only the lost data shards are rebuilt).
 
+`--routes` instead times the other calls that take the chunk pipeline, through the same
+alternation of libraries: rs_locate_batch and rs_correct_batch on clean stripes, rs_correct_batch
+with one corrupt byte per stripe (corrupted again before every call, outside the timed part) and
+rs_update_batch with one changed data shard per stripe.
+
 `--crossover` instead times W3-like batches scaled from 64 KiB to 8 MiB of staging on one
 library; run it once with CALLFS_RS_SMALL_MAX_BYTES=0 (staged) and once with a large value (in
 place) to find where the two transports cross.
@@ -406,6 +411,120 @@ def run_codec_workload(name, libs, rounds, out, seed):
             lib.free(base)
 
 
+class RoutesBatch(Batch):
+    """A Batch for the update, locate and correct calls: one changed data shard per stripe (its
+    new bytes are the next data shard's), every shard present, and one byte per stripe to corrupt."""
+
+    def __init__(self, k, m, sizes, base, arr, rng_seed):
+        super().__init__(k, m, sizes, base, arr, rng_seed)
+        n, B = self.n, self.B
+        rng = np.random.default_rng(rng_seed + 11)
+        changed = rng.integers(0, k, B)
+        self.old = (_vp * (B * k))()
+        self.new = (_vp * (B * k))()
+        for b in range(B):
+            c = int(changed[b])
+            self.old[b * k + c] = self.shard_ptr[b][c]
+            self.new[b * k + c] = self.shard_ptr[b][(c + 1) % k]
+        self.full = (_sz * (B * n))(*[S for S in sizes for _ in range(n)])
+        self.counts = (ctypes.c_uint64 * (B * (n + 1)))()
+        cols = np.array([int(rng.integers(0, S)) for S in sizes], np.int64)
+        ptrs = np.array([self.shard_ptr[b][int(self.lost[b])] for b in range(B)], np.int64)
+        self.corrupt_at = ptrs - base + cols
+
+    def prepare(self, leg):
+        if leg == "correct_1":
+            self.arr[self.corrupt_at] ^= 0x5A
+
+    def run(self, lib, leg):
+        so, ctx = lib.so, lib.ctx
+        if leg == "update":
+            return so.rs_update_batch(ctx, self.k, self.m, self.B, self.csizes, self.old, self.new, self.parity,
+                                      self.status)
+        fn = so.rs_locate_batch if leg == "locate" else so.rs_correct_batch
+        return fn(ctx, self.k, self.m, self.B, self.shards, self.full, self.counts, self.status)
+
+
+def time_route(batch, lib, leg, reps):
+    all_dt = []
+    for _ in range(reps):
+        batch.prepare(leg)
+        t0 = time.perf_counter()
+        rc = batch.run(lib, leg)
+        dt = time.perf_counter() - t0
+        if rc:
+            raise RuntimeError(f"{lib.name} {leg}: rc={rc}")
+        all_dt.append(dt)
+    return min(all_dt) if reps <= 3 else statistics.median(all_dt)
+
+
+def run_routes_workload(name, libs, rounds, out, seed):
+    """rs_locate_batch and rs_correct_batch on clean stripes, rs_correct_batch with one corrupt
+    byte per stripe and rs_update_batch with one changed shard per stripe. The update leg comes
+    last: it leaves the parity that of other data."""
+    rng = np.random.default_rng(seed)
+    k, m, sizes = workload(name, rng)
+    total = Batch.nbytes(k, m, sizes)
+    reps = 200 if total < (8 << 20) else 2
+    sig = [_vp, _int, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_uint64),
+           ctypes.POINTER(_int)]
+    for lib in libs:
+        lib.so.rs_locate_batch.argtypes = lib.so.rs_correct_batch.argtypes = sig
+        lib.so.rs_update_batch.argtypes = [_vp, _int, _int, _int, ctypes.POINTER(_sz), ctypes.POINTER(_vp),
+                                           ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_int)]
+    for mem in ("pageable", "pinned"):
+        batches, frees = {}, []
+        for lib in libs:
+            if mem == "pageable":
+                if "shared" not in batches:
+                    arr = np.empty(total + 16, np.uint8)
+                    base = (arr.ctypes.data + 15) // 16 * 16
+                    view = arr[base - arr.ctypes.data:][:total]
+                    fill_random(view, rng)
+                    batches["shared"] = RoutesBatch(k, m, sizes, base, view, seed)
+                batches[lib.name] = batches["shared"]
+            else:
+                try:
+                    base, arr = lib.pinned(total)
+                except RuntimeError as e:  # e.g. a locked-memory limit: say so, go on
+                    out.write(json.dumps({"workload": name, "memory": mem, "skipped": str(e)}) + "\n")
+                    print(f"{name} pinned skipped: {e}", flush=True)
+                    for lb, bs in frees:
+                        lb.free(bs)
+                    return
+                frees.append((lib, base))
+                fill_random(arr, np.random.default_rng(seed + 1))
+                batches[lib.name] = RoutesBatch(k, m, sizes, base, arr, seed)
+        for leg in ("locate", "correct_clean", "correct_1", "update"):
+            times = {lib.name: [] for lib in libs}
+            counters = {}
+            for lib in libs:  # warm-up: allocations, tables; the encode makes the parity valid
+                b = batches[lib.name]
+                if b.encode(lib):
+                    raise RuntimeError(f"{lib.name}: rs_encode_batch failed")
+                time_route(b, lib, leg, 1)
+                c0 = lib.counters()
+                time_route(b, lib, leg, 1)
+                c1 = lib.counters()
+                counters[lib.name] = c0 and {key: c1[key] - c0[key] for key in c0}
+            for _ in range(rounds):
+                for lib in libs:
+                    times[lib.name].append(time_route(batches[lib.name], lib, leg, reps))
+            for lib in libs:
+                t = times[lib.name]
+                line = {"workload": name, "k": k, "m": m, "stripes": len(sizes), "bytes": total, "leg": leg,
+                        "memory": mem, "lib": lib.name, "reps_per_round": reps,
+                        "seconds": [round(x, 7) for x in t], "median_s": statistics.median(t),
+                        "us_per_call": round(statistics.median(t) * 1e6, 1),
+                        "counters_per_call": counters[lib.name]}
+                out.write(json.dumps(line) + "\n")
+                out.flush()
+                print(json.dumps({key: line[key] for key in ("workload", "leg", "memory", "lib", "us_per_call",
+                                                             "counters_per_call")}), flush=True)
+        for lib, base in frees:
+            lib.free(base)
+
+
 def run_crossover(lib, rounds, out, seed):
     """W3-like batches scaled to 64 KiB .. 8 MiB of total staging, pageable."""
     for target in (64 << 10, 128 << 10, 256 << 10, 512 << 10, 1 << 20, 2 << 20, 4 << 20, 8 << 20):
@@ -445,6 +564,8 @@ def main():
     ap.add_argument("--out", default="host_batch.jsonl")
     ap.add_argument("--crossover", action="store_true")
     ap.add_argument("--codec", action="store_true", help="the codec-level batch calls (objects in / out)")
+    ap.add_argument("--routes", action="store_true",
+                    help="rs_update_batch, rs_locate_batch and rs_correct_batch (DESIGN.md §7.5)")
     a = ap.parse_args()
     specs = a.lib or [f"current={DEFAULT_LIB}"]
     libs = [Lib(*s.split("=", 1)) for s in specs]
@@ -453,8 +574,9 @@ def main():
         if a.crossover:
             run_crossover(libs[0], a.rounds, out, a.seed)
         else:
+            run = run_routes_workload if a.routes else run_codec_workload if a.codec else run_workload
             for w in a.workloads.split(","):
-                (run_codec_workload if a.codec else run_workload)(w, libs, a.rounds, out, a.seed)
+                run(w, libs, a.rounds, out, a.seed)
     return 0
 
 
