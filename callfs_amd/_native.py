@@ -45,6 +45,8 @@ RS_E_ARG = -10
 RS_E_SINGULAR = -11
 RS_E_NOMEM = -12
 
+RS_DECODE_IDX_STORE = 1  # rs_plan_create_decode_idx / rs_decode_idx flags
+
 _vp = ctypes.c_void_p
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _sz = ctypes.c_size_t
@@ -156,6 +158,13 @@ SIGNATURES = {
                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_int)]),
     "rs_codec_decode_correct": (_int, [_vp, _int, _int, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _vp,
                                        _i64, _u8p]),
+    "rs_plan_create_decode_idx": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
+                                         ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_uint,
+                                         ctypes.POINTER(_vp)]),
+    "rs_decode_idx": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), _u8p, ctypes.POINTER(_vp),
+                             ctypes.c_uint]),
+    "rs_decode_idx_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_sz), ctypes.POINTER(_vp), _u8p,
+                                   ctypes.POINTER(_vp), ctypes.c_uint, ctypes.POINTER(_int)]),
     "rs_update": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                          ctypes.POINTER(_vp)]),
     "rs_encode_idx": (_int, [_vp, _int, _int, _sz, _vp, _int, ctypes.POINTER(_vp)]),

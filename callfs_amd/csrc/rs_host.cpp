@@ -19,6 +19,7 @@
 #include "host_locate.hpp"
 #include "host_ragged.hpp"
 #include "host_uniform.hpp"
+#include "host_decode_idx.hpp"
 #include "host_update.hpp"
 #include "overwrite_plan.hpp"
 
@@ -691,6 +692,58 @@ int rs_encode_idx(rs_ctx* ctx, int k, int m, size_t S, const uint8_t* shard, int
   int status = RS_OK;
   if ((rc = update_batch_host(ctx, k, m, 1, &S, nullptr, one.data(), parity, &status))) return rc;
   return status;
+}
+
+// ---- exported: progressive decode --------------------------------------
+
+// status[b]: the stripe's own refusal in the plan constructor's order -- the expect count
+// (RS_E_TOO_FEW_SHARDS, RS_E_ARG), a misplaced pointer (RS_E_ARG), a zero size with both an input
+// and a dst (RS_E_NO_DATA); the other stripes run. Stripes without an input or without a dst are
+// RS_OK and reach no device.
+int rs_decode_idx_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes, uint8_t* const* dst,
+                        const uint8_t* expect, const uint8_t* const* input, unsigned flags, int* status) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!sizes || !dst || !expect || !input || !status)) ||
+      (flags & ~RS_DECODE_IDX_STORE))
+    return RS_E_ARG;
+  const size_t B = static_cast<size_t>(batch), n = static_cast<size_t>(k + m);
+  std::vector<uint8_t> fl(B * n, 0);
+  std::vector<int> ids;
+  for (size_t b = 0; b < B; ++b) {
+    int ne = 0;
+    bool in = false, out = false, misplaced = false;
+    for (size_t i = 0; i < n; ++i) {
+      const size_t at = b * n + i;
+      const bool e = expect[at] != 0;
+      ne += e;
+      in |= input[at] != nullptr;
+      out |= dst[at] != nullptr;
+      misplaced |= e ? dst[at] != nullptr : input[at] != nullptr;
+      fl[at] = static_cast<uint8_t>((e ? 1 : 0) | (input[at] ? 2 : 0) | (dst[at] ? 4 : 0));
+    }
+    if (ne < k) status[b] = RS_E_TOO_FEW_SHARDS;
+    else if (ne > k || misplaced) status[b] = RS_E_ARG;
+    else if (!in || !out) status[b] = RS_OK;
+    else if (sizes[b] == 0) status[b] = RS_E_NO_DATA;
+    else {
+      status[b] = RS_OK;
+      ids.push_back(static_cast<int>(b));
+    }
+  }
+  if ((rc = run_decode_idx(ctx, k, m, (flags & RS_DECODE_IDX_STORE) != 0, ids, sizes, fl.data(),
+                           [&](int b, int i) { return input[static_cast<size_t>(b) * n + i]; },
+                           [&](int b, int i) { return dst[static_cast<size_t>(b) * n + i]; })))
+    return rc;
+  return first_error(status, batch);
+}
+
+int rs_decode_idx(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* dst, const uint8_t* expect,
+                  const uint8_t* const* input, unsigned flags) {
+  int status = RS_OK;
+  const int rc = rs_decode_idx_batch(ctx, k, m, 1, &S, dst, expect, input, flags, &status);
+  return rc ? rc : status;
 }
 
 int rs_codec_overwrite(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* shards, int64_t offset,

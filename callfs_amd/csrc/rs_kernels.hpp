@@ -291,6 +291,29 @@ constexpr int kOrderUpdate = 4096;
 hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_tail,
                          hipStream_t stream, LaunchEvents ev = {});
 
+// ---- decode-idx launches (rs_merge.hpp in rs_mixed.hip) ------------------
+// Upstream DecodeIdx: a single-source update launch group whose patterns have their own row
+// counts and whose rows are either merged into the destination or stored over it. Stripe s
+// reads the nsrc[pat[s]] delivered shards of its pattern and does, for r < nrows[pat[s]],
+//   out[s][r] ^= XOR_{i < nsrc} coef[r][i] * in[s][i]   (merge)
+//   out[s][r]  = XOR_{i < nsrc} coef[r][i] * in[s][i]   (store: the destination is never read)
+// u as for a single launch_update (in_stride = a.K); out_tab is pitched at a.R, the most rows a
+// pattern has in this launch group, and slots at and past a stripe's row count hold nothing the
+// kernel loads. A mapped stripe whose pattern has nrows 0 in this group is left untouched.
+struct MergeArgs {
+  UpdateArgs u;
+  const uint32_t* nrows;  // [P] rows of each pattern in this launch group, 0..a.R
+};
+
+// (kOrderDecodeIdx + the TileOrder it runs in, always consecutive: rs_plan_forms of a decode-idx plan)
+constexpr int kOrderDecodeIdx = 32768;
+
+// Enqueues the launch group: rs_merge_ragged (store: its STORE instances) over every mapped
+// stripe's [0, size), tails, misaligned shards, order and slicing as launch_update;
+// x.u.ntiles == 0 enqueues nothing. A merge launch is NOT idempotent; a store launch is.
+hipError_t launch_decode_idx(ApplyArgs a, const MergeArgs& x, bool store, bool any_tail,
+                             hipStream_t stream, LaunchEvents ev = {});
+
 // ---- locate launches (rs_mixed.hip) --------------------------------------
 // A required launch group in which every row is compared and none written, and a mismatching
 // byte column is classified instead of only flagged: locate_classify (locate_tables.hpp) turns

@@ -22,6 +22,7 @@
 #include "launch_util.hpp"
 #include "locate_tables.hpp"
 #include "rs_apply.hpp"
+#include "rs_merge.hpp"
 #include "rs_update.hpp"
 
 namespace callfs {
@@ -589,9 +590,18 @@ const std::array<std::array<UpdateFn, 3>, 2> kUpdate = {{
     {kUpdateInstance<4, false>, kUpdateInstance<8, false>, kUpdateInstance<16, false>},
     {kUpdateInstance<4, true>, kUpdateInstance<8, true>, kUpdateInstance<16, true>}}};
 
+// Decode-idx launches (rs_merge.hpp): [store][0: R <= 4, 1: R 5..8, 2: R 9..16]
+using MergeFn = void (*)(ApplyArgs, MergeArgs);
+template <int RT, bool STORE>
+constexpr MergeFn kMergeInstance = &dev::rs_merge_ragged<RT, dev::UpdatePolicyFor<RT, false>, STORE>;
+const std::array<std::array<MergeFn, 3>, 2> kMerge = {{
+    {kMergeInstance<4, false>, kMergeInstance<8, false>, kMergeInstance<16, false>},
+    {kMergeInstance<4, true>, kMergeInstance<8, true>, kMergeInstance<16, true>}}};
+
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
 // per-device attribute (dispatch.hpp DeviceOnce), keyed by the 16-row instance it is set on
-enum class WideLds { kMixed, kRagged, kRaggedSome, kUpdate, kUpdatePair, kLocate, kLocate2, kCorrect };
+enum class WideLds { kMixed, kRagged, kRaggedSome, kUpdate, kUpdatePair, kLocate, kLocate2, kCorrect,
+                     kMerge, kMergeStore };
 DeviceOnce g_mixed_wide_lds;
 
 // The vector launch every kind shares: the dynamic-LDS opt-in, then `grid` tiles in equal
@@ -707,6 +717,21 @@ hipError_t launch_update(ApplyArgs a, const UpdateArgs& x, bool pair, bool any_t
   return launch_tiles(kUpdate[pair ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0],
                       pair ? WideLds::kUpdatePair : WideLds::kUpdate, x.ntiles, a, x,
                       a.K * (pair ? 2 : 1) + 2 * a.R, stream, ev);
+}
+
+hipError_t launch_decode_idx(ApplyArgs a, const MergeArgs& x, bool store, bool any_tail,
+                             hipStream_t stream, LaunchEvents ev) {
+  if (!tile_map_ok(a, x.u) || !x.u.nsrc || !x.nrows || x.u.in_stride != static_cast<uint32_t>(a.K))
+    return hipErrorInvalidValue;
+  if (x.u.ntiles == 0) return hipSuccess;  // no stripe has both a delivered and a wanted shard
+  a.t_base = 0;
+  a.S = a.nvec = 0;  // per stripe, read by the kernel
+  a.verify_mask = 0;
+  a.tail_in_vec = any_tail ? 1u : 0u;  // wave 0 of each stripe's first tile
+  // per tile: the sources, and every row written (merge: read as well)
+  return launch_tiles(kMerge[store ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0],
+                      store ? WideLds::kMergeStore : WideLds::kMerge, x.u.ntiles, a, x,
+                      a.K + (store ? 1 : 2) * a.R, stream, ev);
 }
 
 }  // namespace callfs

@@ -418,6 +418,42 @@ class Plan:
         self.handle = h
         return self
 
+    @classmethod
+    def decode_idx(cls, k: int, m: int, sizes: Sequence[int], expect, input_ptrs, dst_ptrs,
+                   store: bool = False, device: int = 0,
+                   context: Optional[N.Context] = None) -> "Plan":
+        """rs_plan_create_decode_idx: upstream DecodeIdx on device memory.
+        expect: batch rows of k+m flags, exactly k set per row: the shards the decode will be
+        fed over all plans. input_ptrs: batch*(k+m) device pointers, nonzero = delivered with
+        this plan (expected indices only); dst_ptrs: batch*(k+m), nonzero = wanted (indices that
+        are not expected only). A launch adds C[:, delivered] * inputs into the wanted shards
+        (C = E[wanted] * inv(E[expected])), or with store=True stores it without reading them.
+        After every expected shard has been delivered once the wanted shards hold what a
+        reconstruct from those k shards gives. A merge launch is NOT idempotent."""
+        batch = len(sizes)
+        n = k + m
+        rows = _mask_rows(expect)
+        if rows is None or len(rows) != batch or any(len(r) != n for r in rows):
+            raise ValueError("expect: batch rows of k+m flags")
+        if len(input_ptrs) != batch * n or len(dst_ptrs) != batch * n:
+            raise ValueError("need batch*(k+m) input pointers and batch*(k+m) dst pointers")
+        self = cls.__new__(cls)
+        self.ctx = context or N.default_context()
+        self.k, self.m, self.S, self.batch, self.device = k, m, None, batch, device
+        self.sizes = [int(s) for s in sizes]
+        self.handle = None
+        flags = (ctypes.c_uint8 * max(1, batch * n))(*[1 if f else 0 for r in rows for f in r])
+        szs = (ctypes.c_size_t * max(1, batch))(*self.sizes)
+        arr = lambda p: (ctypes.c_void_p * max(1, len(p)))(*[int(x) or None for x in p])  # noqa: E731
+        h = ctypes.c_void_p()
+        N.check(N.lib.rs_plan_create_decode_idx(self.ctx.handle, device, k, m, batch, szs, flags,
+                                                arr(input_ptrs), arr(dst_ptrs),
+                                                N.RS_DECODE_IDX_STORE if store else 0,
+                                                ctypes.byref(h)),
+                "rs_plan_create_decode_idx")
+        self.handle = h
+        return self
+
     @property
     def bytes(self) -> int:
         """Algorithmic HBM bytes one launch moves."""
@@ -472,7 +508,7 @@ class Plan:
                    198: "dma-x32", 224: "tridb-g4", 225: "tridb-g8", 256: "bs", 257: "bs-g8",
                    258: "bs-g2", 259: "bs-q8", 260: "bs-q16", 261: "bs-x8", 262: "bs-x32",
                    512: "mixed", 1024: "ragged", 2048: "required", 4096: "update",
-                   8192: "locate", 16384: "correct"}
+                   8192: "locate", 16384: "correct", 32768: "decode-idx"}
 
     def tune(self, reps: int = 5, stream: Optional[torch.cuda.Stream] = None) -> list:
         """rs_plan_tune: time each launch group in every tile order its kernel offers

@@ -737,6 +737,72 @@ def update_batch(old_data: Optional[Sequence[Sequence]], new_data: Sequence[Sequ
     return out
 
 
+def _decode_idx_rows(dst, expect, inputs, k, m):
+    """One stripe's checks for decode_idx / decode_idx_batch: k+m entries each, one shard size
+    over every given buffer, writable destinations. Returns that size (0: nothing given)."""
+    n = k + m
+    if len(dst) != n or len(expect) != n or len(inputs) != n:
+        raise ErrTooFewShards()
+    given = [s for s in list(dst) + list(inputs) if s is not None]
+    S = len(given[0]) if given else 0
+    if any(len(s) != S for s in given):
+        raise ErrShardSize()
+    if not all(s is None or _writable(s) for s in dst):
+        raise TypeError("dst shards must be writable")
+    return S
+
+
+def decode_idx(dst: Sequence, expect: Sequence[bool], inputs: Sequence, k: int, m: int,
+               store: bool = False, context: Optional[N.Context] = None) -> None:
+    """upstream enc.DecodeIdx(dst, expectInput, input): the decode twin of encode_idx. expect
+    (k+m flags, exactly k set) fixes the shards the decode will be fed over all calls; inputs
+    (k+m entries, None = not delivered with this call) are the shards that have arrived; dst
+    (k+m entries, None = not wanted) are writable buffers at indices that are not expected.
+    Adds the delivered shards' contribution into every wanted shard, or with store=True stores
+    it without reading them. Zero dst before the first call (or store first); once every
+    expected shard has been delivered, in any order, dst holds what reconstruct gives from
+    those k shards. Fewer than k expected raises ErrTooFewShards; more, an input that is not
+    expected or a dst that is raise ErrInvalidInput."""
+    ctx = context or N.default_context()
+    S = _decode_idx_rows(dst, expect, inputs, k, m)
+    ex = (ctypes.c_uint8 * (k + m))(*[1 if e else 0 for e in expect])
+    rc = N.lib.rs_decode_idx(ctx.handle, k, m, S, _shard_ptrs(list(dst)), ex, _shard_ptrs(list(inputs)),
+                             N.RS_DECODE_IDX_STORE if store else 0)
+    if rc == N.RS_E_ARG:
+        raise ErrInvalidInput()
+    if rc == N.RS_E_INVALID_PROFILE:
+        raise ErrInvalidProfile()
+    if rc != N.RS_OK:
+        raise _wrapped(rc, "decode_idx")
+
+
+def decode_idx_batch(dst: Sequence[Sequence], expect: Sequence[Sequence[bool]],
+                     inputs: Sequence[Sequence], k: int, m: int, store: bool = False,
+                     context: Optional[N.Context] = None) -> List[int]:
+    """rs_decode_idx_batch: stripe b has dst[b], expect[b] and inputs[b] as decode_idx takes
+    them; stripes may differ in shard size, expected set, wanted set and what is delivered.
+    Returns status[b] (RS_OK, RS_E_TOO_FEW_SHARDS, RS_E_ARG, RS_E_NO_DATA)."""
+    ctx = context or N.default_context()
+    B = len(dst)
+    if len(expect) != B or len(inputs) != B:
+        raise ValueError("one row of dst / expect / input entries per stripe")
+    sizes = (ctypes.c_size_t * max(B, 1))()
+    for b in range(B):
+        sizes[b] = _decode_idx_rows(dst[b], expect[b], inputs[b], k, m)
+
+    def ptrs(rows):
+        return _shard_ptrs([s for row in rows for s in row] or [None])
+
+    ex = (ctypes.c_uint8 * max(1, B * (k + m)))(*[1 if e else 0 for row in expect for e in row])
+    status = (ctypes.c_int * max(B, 1))()
+    rc = N.lib.rs_decode_idx_batch(ctx.handle, k, m, B, sizes, ptrs(dst), ex, ptrs(inputs),
+                                   N.RS_DECODE_IDX_STORE if store else 0, status)
+    out = list(status)[:B]
+    if rc != N.RS_OK and rc not in out:
+        N.check(rc, "rs_decode_idx_batch")
+    return out
+
+
 def verify(shards: List, k: int, m: int, context: Optional[N.Context] = None) -> bool:
     """upstream enc.Verify(shards) (codec.go:59)."""
     ctx = context or N.default_context()

@@ -133,6 +133,28 @@ func (c *Codec) UpdateBatch(shards, newData [][][]byte, profile ErasureProfile) 
 	return errs
 }
 
+// DecodeIdx is upstream enc.DecodeIdx(dst, expectInput, input) on builds without the GPU codec.
+func (c *Codec) DecodeIdx(dst [][]byte, expectInput []bool, input [][]byte, profile ErasureProfile) error {
+	if profile.DataShards < 1 || profile.ParityShards < 1 {
+		return ErrInvalidProfile
+	}
+	return cpuDecodeIdx(dst, expectInput, input, profile.DataShards, profile.ParityShards)
+}
+
+// DecodeIdxBatch is DecodeIdx per stripe on builds without the GPU codec.
+func (c *Codec) DecodeIdxBatch(dst [][][]byte, expectInput [][]bool, input [][][]byte, profile ErasureProfile) []error {
+	errs := make([]error, len(dst))
+	for b := range dst {
+		if len(expectInput) != len(dst) || len(input) != len(dst) {
+			errs[b] = fmt.Errorf("erasure: %d expect rows and %d input rows for %d stripes", len(expectInput),
+				len(input), len(dst))
+			continue
+		}
+		errs[b] = c.DecodeIdx(dst[b], expectInput[b], input[b], profile)
+	}
+	return errs
+}
+
 // ErrLocateUnavailable is what Locate reports on builds without the GPU codec: the CPU codec
 // has no locator (the reference finds a bad shard by its checksum, manager.go:250-320).
 var ErrLocateUnavailable = errors.New("erasure: locating corrupt shards needs the GPU codec")

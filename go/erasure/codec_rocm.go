@@ -919,6 +919,139 @@ func (c *Codec) UpdateBatch(shards, newData [][][]byte, profile ErasureProfile) 
 	return errs
 }
 
+// ---- progressive decode (upstream DecodeIdx; DESIGN.md §5.14) ---------------------------
+
+// decodeIdxErr maps the codes of the decode-idx calls as updateErr does, inside Decode's wrapper.
+func decodeIdxErr(rc C.int) error {
+	switch rc {
+	case C.RS_OK:
+		return nil
+	case C.RS_E_INVALID_PROFILE:
+		return ErrInvalidProfile
+	case C.RS_E_ARG:
+		return fmt.Errorf("erasure: failed to decode: %w", reedsolomon.ErrInvalidInput)
+	}
+	return fmt.Errorf("erasure: failed to decode: %w", upstreamErr(rc))
+}
+
+// checkDecodeIdx checks one stripe's argument counts and sizes: k+m entries each, one size over
+// every given dst and input. The expect count and the misplaced entries are the library's to
+// refuse (RS_E_TOO_FEW_SHARDS, RS_E_ARG). Returns the shard size (0: nothing given).
+func checkDecodeIdx(dst [][]byte, expectInput []bool, input [][]byte, k, m int) (int, error) {
+	wrap := func(err error) error { return fmt.Errorf("erasure: failed to decode: %w", err) }
+	if len(dst) != k+m || len(expectInput) != k+m || len(input) != k+m {
+		return 0, wrap(reedsolomon.ErrTooFewShards)
+	}
+	S := 0
+	for _, rows := range [][][]byte{dst, input} {
+		for _, s := range rows {
+			if len(s) == 0 {
+				continue
+			}
+			if S == 0 {
+				S = len(s)
+			}
+			if len(s) != S {
+				return 0, wrap(reedsolomon.ErrShardSize)
+			}
+		}
+	}
+	return S, nil
+}
+
+// DecodeIdx is upstream enc.DecodeIdx(dst, expectInput, input) (rs_decode_idx), the decode twin
+// of EncodeIdx: expectInput (k+m flags, exactly k set) fixes the shards the decode will be fed
+// over all calls, input (k+m entries, nil = not delivered with this call) holds the shards that
+// have arrived, dst (k+m entries, nil = not wanted) the shards to rebuild, at indices that are
+// not expected. The delivered shards' contribution is added into every wanted shard. Zero dst
+// before the first call; once every expected shard has been delivered, in any order, dst holds
+// what Reconstruct gives from those k shards. Each call pays its own round trip to the device.
+// Not in the reference API.
+func (c *Codec) DecodeIdx(dst [][]byte, expectInput []bool, input [][]byte, profile ErasureProfile) error {
+	errs := c.DecodeIdxBatch([][][]byte{dst}, [][]bool{expectInput}, [][][]byte{input}, profile)
+	return errs[0]
+}
+
+// DecodeIdxBatch is DecodeIdx for many stripes of one profile in one call (rs_decode_idx_batch:
+// one pipeline over all of them, whatever their sizes, expected sets, wanted sets and delivered
+// shards). dst[b], expectInput[b] and input[b] are stripe b's arguments to DecodeIdx; errs[b]
+// is what it would report.
+func (c *Codec) DecodeIdxBatch(dst [][][]byte, expectInput [][]bool, input [][][]byte, profile ErasureProfile) []error {
+	k, m := profile.DataShards, profile.ParityShards
+	errs := make([]error, len(dst))
+	if len(expectInput) != len(dst) || len(input) != len(dst) {
+		for b := range errs {
+			errs[b] = fmt.Errorf("erasure: %d expect rows and %d input rows for %d stripes", len(expectInput),
+				len(input), len(dst))
+		}
+		return errs
+	}
+	if k < 1 || m < 1 {
+		for b := range errs {
+			errs[b] = ErrInvalidProfile
+		}
+		return errs
+	}
+	if len(dst) == 0 {
+		return errs
+	}
+	if k+m > 256 || device() == nil {
+		for b := range dst {
+			errs[b] = cpuDecodeIdx(dst[b], expectInput[b], input[b], k, m)
+		}
+		return errs
+	}
+	B, n := len(dst), k+m
+	ins, outs := newCArray(B*n), newCArray(B*n)
+	defer ins.free()
+	defer outs.free()
+	sizes := make([]C.size_t, B)
+	status := make([]C.int, B)
+	expect := make([]C.uint8_t, B*n)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for b := range dst {
+		S, err := checkDecodeIdx(dst[b], expectInput[b], input[b], k, m)
+		if err != nil {
+			errs[b] = err
+			for i := 0; i < k && i < n; i++ { // a well-formed stripe with nothing to do for the library
+				expect[b*n+i] = 1
+			}
+			continue
+		}
+		sizes[b] = C.size_t(S)
+		for i := 0; i < n; i++ {
+			if expectInput[b][i] {
+				expect[b*n+i] = 1
+			}
+			if len(input[b][i]) > 0 {
+				pin.Pin(&input[b][i][0])
+				ins.set(b*n+i, unsafe.Pointer(&input[b][i][0]))
+			}
+			if len(dst[b][i]) > 0 {
+				pin.Pin(&dst[b][i][0])
+				outs.set(b*n+i, unsafe.Pointer(&dst[b][i][0]))
+			}
+		}
+	}
+	rc := C.rs_decode_idx_batch(gpuCtx, C.int(k), C.int(m), C.int(B), &sizes[0], outs.at(0), &expect[0],
+		ins.at(0), 0, &status[0])
+	if rc != C.RS_OK && !hasStatus(status, rc) { // a call-level error: no status was written
+		for b := range errs {
+			if errs[b] == nil {
+				errs[b] = decodeIdxErr(rc)
+			}
+		}
+		return errs
+	}
+	for b := range errs {
+		if errs[b] == nil {
+			errs[b] = decodeIdxErr(status[b])
+		}
+	}
+	return errs
+}
+
 // Overwrite replaces bytes [offset, offset+len(data)) of the object whose n shards these are
 // (Encode's layout: object byte x in data shard x/S at column x%S) and brings the parity up to
 // date (rs_codec_overwrite): only the affected parity columns are read and rewritten, through

@@ -7,7 +7,8 @@ import (
 )
 
 // The CPU forms of the calls that update parity in place (UpdateParity, EncodeIdx, UpdateBatch,
-// Overwrite): upstream Update / EncodeIdx. Both builds use them: the default build for every
+// Overwrite) and of the progressive decode (DecodeIdx, DecodeIdxBatch): upstream Update /
+// EncodeIdx / DecodeIdx. Both builds use them: the default build for every
 // call, the GPU build for k+m > 256 and when there is no device.
 
 // cpuUpdateParity is upstream enc.Update(shards, newData): shards holds the old data shards
@@ -32,6 +33,19 @@ func cpuEncodeIdx(dataShard []byte, idx int, parity [][]byte, k, m int) error {
 	}
 	if err := enc.EncodeIdx(dataShard, idx, parity); err != nil {
 		return fmt.Errorf("erasure: failed to update parity: %w", err)
+	}
+	return nil
+}
+
+// cpuDecodeIdx is upstream enc.DecodeIdx(dst, expectInput, input): the contribution of the
+// delivered input shards is added into the wanted dst shards.
+func cpuDecodeIdx(dst [][]byte, expectInput []bool, input [][]byte, k, m int) error {
+	enc, err := reedsolomon.New(k, m)
+	if err != nil {
+		return fmt.Errorf("erasure: failed to create encoder: %w", err)
+	}
+	if err := enc.DecodeIdx(dst, expectInput, input); err != nil {
+		return fmt.Errorf("erasure: failed to decode: %w", err)
 	}
 	return nil
 }

@@ -297,6 +297,39 @@ int rs_update_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes,
 int rs_codec_overwrite(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* shards,
                        int64_t offset, const uint8_t* data, size_t len);
 
+/* ---- Progressive decode, host memory -------------------------------
+ * Upstream DecodeIdx(dst, expectInput, input) for stripes in host memory: expect, input, dst and
+ * flags exactly as for rs_plan_create_decode_idx (below), over n = k+m entries per stripe, and
+ * the same result: merge adds the delivered shards' terms into the wanted shards, store
+ * (RS_DECODE_IDX_STORE) stores them without reading the wanted shards. After every expected shard
+ * has been delivered once, in any order and any grouping of calls, dst holds bit for bit what
+ * rs_reconstruct gives with exactly those k shards present -- from zeroed destinations, or when
+ * the first call stores.
+ * rs_decode_idx: one stripe of S-byte shards. Errors in the plan constructor's order: the
+ *   profile; a NULL ctx, dst, expect or input, or a flag bit other than RS_DECODE_IDX_STORE
+ *   (RS_E_ARG); the expect count (RS_E_TOO_FEW_SHARDS below k, RS_E_ARG above); a misplaced
+ *   pointer (RS_E_ARG); S == 0 with both an input and a dst (RS_E_NO_DATA).
+ * rs_decode_idx_batch: stripe b has sizes[b]-byte shards and entries b*n + i of dst, expect and
+ *   input. The profile, NULL arrays, batch < 0 and the flag bits fail the call; the per-stripe
+ *   refusals land in status[b] (in the same order) and the other stripes run. The return value
+ *   follows rs_update_batch's rule. No dst byte of one stripe may overlap a dst byte of another
+ *   stripe or any input.
+ * A stripe with no input or no wanted shard keeps every byte; a call in which no stripe has both
+ * reaches no device, moves no counter and returns RS_OK.
+ * Both take the staged ragged pipeline on one device, whatever memory the buffers are in. A
+ * chunk: one H2D of metadata and the delivered shards; in merge mode a second H2D of the wanted
+ * shards' current bytes -- A STORE CALL DOES NOT UPLOAD THE WANTED SHARDS, and `copies` of
+ * rs_host_counters shows it (2 per store chunk, 3 per merge chunk); one launch per group of 16
+ * wanted rows; one D2H of the wanted rows. A stripe above CALLFS_RS_CHUNK_BYTES is cut into column
+ * parts. Every call pays its own round trip: the accumulators do not stay on the device between
+ * calls (use a decode-idx plan for that). rs_host_counters counts the calls like the others. */
+#define RS_DECODE_IDX_STORE 1u
+int rs_decode_idx(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* dst,
+                  const uint8_t* expect, const uint8_t* const* input, unsigned flags);
+int rs_decode_idx_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes,
+                        uint8_t* const* dst, const uint8_t* expect,
+                        const uint8_t* const* input, unsigned flags, int* status);
+
 /* ---- counters of the host-memory path -----------------------------------------------
  * Monotonic per-context counts (relaxed atomics; what an operator graphs, and what shows
  * that a batch cost one round trip):
@@ -554,6 +587,58 @@ int rs_decode_dev_required(rs_ctx* ctx, int device, int k, int m, int batch, con
 int rs_plan_create_update(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
                           const uint8_t* changed, const uint8_t* const* old_data,
                           const uint8_t* const* new_data, uint8_t* const* parity, rs_plan** out);
+
+/* ---- decode-idx plans: progressive decode ---------------------------
+ * Upstream DecodeIdx(dst, expectInput, input), the decode twin of EncodeIdx, for device-resident
+ * batches: the k shards a decode will be fed are fixed up front, and every launch adds the
+ * contribution of the shards that have arrived so far into the wanted outputs, in any order and
+ * any grouping. Stripe b has sizes[b]-byte shards and, over its n = k+m shard indices, entries
+ * b*n + i of three arrays:
+ *   expect  (flags)    nonzero = shard i will be delivered over all calls. Exactly k must be set:
+ *                      fewer is RS_E_TOO_FEW_SHARDS, more is RS_E_ARG.
+ *   input   (pointers) non-NULL = shard i is delivered with this plan. An input at an index that
+ *                      is not expected is RS_E_ARG.
+ *   dst     (pointers) non-NULL = shard i is wanted. A dst at an expected index is RS_E_ARG. Any
+ *                      index that is not expected may be wanted, data or parity, and any may be
+ *                      left out: it is then neither read nor written.
+ *   flags              0 = merge, RS_DECODE_IDX_STORE = store; any other bit is RS_E_ARG.
+ * With V the expected indices in ascending order and C = E[w] * inv(E[V]) (E = rs_encode_matrix;
+ * C's row for w is the row rs_decode_rows returns for a presence mask equal to expect), a launch
+ * sets for every wanted w of every stripe that has both an input and a dst
+ *     merge:  dst[w] ^= sum over the delivered v of C[w][v] * input[v]
+ *     store:  dst[w]  = sum over the delivered v of C[w][v] * input[v]   (dst is neither read nor
+ *                                                                        zeroed)
+ * After every expected shard has been delivered once, dst holds bit for bit what a reconstruct
+ * with exactly those k shards present gives -- from zeroed destinations, or when the first launch
+ * stores. With expect = the data shards and dst = the parity this is EncodeIdx. A stripe with no
+ * input or no wanted shard is in no launch and keeps every byte, in both modes.
+ * A MERGE LAUNCH IS NOT IDEMPOTENT: it adds the terms to the destination's current bytes, and a
+ * second launch adds them again, which restores what the first started from. A store launch is
+ * idempotent.
+ * The caller's contract: no dst byte of a stripe overlaps a dst byte of another stripe or any
+ * input.
+ * It is an ordinary plan: rs_plan_launch / _launch_timed only enqueue (no allocation, no sync;
+ * graph-capturable), one launch per group of 16 wanted rows; _destroy as for any plan, and
+ *   rs_plan_groups  returns the number of row groups, 0 when no stripe is in a launch;
+ *   rs_plan_bytes   returns the sum over the stripes in the launch, with c_b delivered and r_b
+ *                   wanted shards, of sizes[b] * (c_b + 2 r_b) in merge mode and
+ *                   sizes[b] * (c_b + r_b) in store mode;
+ *   rs_plan_forms   reports RS_ORDER_DECODE_IDX + RS_ORDER_CONSECUTIVE;
+ *   rs_plan_status  reports 0 (nothing is compared);
+ *   rs_plan_tune    times nothing and fills -1, rs_plan_set_orders accepts only -1, and the
+ *                   ceiling launches return RS_E_ARG; no bit-sliced kernel, no hiprtc compile, no
+ *                   tune-table entry.
+ * Errors, in this order: the profile (RS_E_INVALID_PROFILE, RS_E_UNSUPPORTED); a NULL sizes,
+ * expect, input, dst or out, batch < 1, or a flag bit other than RS_DECODE_IDX_STORE (RS_E_ARG);
+ * a stripe whose expect count is not k (RS_E_TOO_FEW_SHARDS below k, RS_E_ARG above); an input at
+ * an index that is not expected or a dst at one that is (RS_E_ARG); sizes[b] == 0 on a stripe with
+ * both an input and a dst (RS_E_NO_DATA). Each check runs over the whole batch before the next.
+ * Nothing is created on an error. */
+#define RS_ORDER_DECODE_IDX 32768
+int rs_plan_create_decode_idx(rs_ctx* ctx, int device, int k, int m, int batch,
+                              const size_t* sizes, const uint8_t* expect,
+                              const uint8_t* const* input, uint8_t* const* dst,
+                              unsigned flags, rs_plan** out);
 
 /* ---- locate plans: which shard is corrupt --------------------------
  * Not in the reference API. Every other plan tells that a stripe's compared shards mismatch; a

@@ -504,6 +504,18 @@ shift
 timeout -k 10 400 python3 -u tools/update_bench.py "$@" | tee $O/update_bench.jsonl || exit $?
 }
 
+# Decode-idx plans against the launches that move the same bytes (tools/decode_idx_bench.py,
+# DESIGN.md §5.14): RS(10,4), 256 stripes of 1 MiB; a one-shard merge against the EncodeIdx update
+# plan, a ten-shard store against the required reconstruct plan. One JSON line per shape on stdout
+# and in <out dir>/decode_idx_bench.jsonl (the lines kept in profiles/r20/decode_idx/).
+# Usage: bash tools/jobs.sh decode_idx_bench <out dir> [decode_idx_bench.py args]
+job_decode_idx_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+O=${1:-decode_idx_out}; mkdir -p "$O" || exit $?
+shift
+timeout -k 10 400 python3 -u tools/decode_idx_bench.py "$@" | tee $O/decode_idx_bench.jsonl || exit $?
+}
+
 # Locate plans against the compare-only plan of the same batch and against batched SHA-256 of
 # every shard (tools/locate_bench.py): RS(10,4) x 256 stripes of 64 KiB..4 MiB
 # and RS(16,4) x 4,096 stripes of 1..16 KiB, clean and with one shard of every stripe wholly
