@@ -77,6 +77,13 @@ constexpr int encode(Form f) {
   return (static_cast<int>(f.family) - 1) * kOrderRealign + f.member;
 }
 
+// (kOrderDecodeCheck + consecutive: what rs_plan_forms reports for a final decode-check plan,
+// DESIGN.md §5.15. A plan's form code like the mixed and ragged ones: no launch order, no
+// bit-sliced form, no tune-table entry.)
+constexpr int kOrderDecodeCheck = 65536;
+static_assert(!decode_order(kOrderDecodeCheck).valid() && encode(decode_order(kOrderDecodeCheck)) == -1,
+              "a plan form code names no launch order");
+
 static_assert(encode(Form{Family::kRealign, 0}) == kOrderRealign && encode(Form{Family::kWix, 0}) == kOrderWix &&
                   encode(Form{Family::kTri, 0}) == kOrderTri &&
                   encode(Form{Family::kRealignTri, 0}) == kOrderRealignTri &&

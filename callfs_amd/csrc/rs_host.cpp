@@ -732,9 +732,10 @@ int rs_decode_idx_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* size
       ids.push_back(static_cast<int>(b));
     }
   }
-  if ((rc = run_decode_idx(ctx, k, m, (flags & RS_DECODE_IDX_STORE) != 0, ids, sizes, fl.data(),
-                           [&](int b, int i) { return input[static_cast<size_t>(b) * n + i]; },
-                           [&](int b, int i) { return dst[static_cast<size_t>(b) * n + i]; })))
+  if ((rc = run_decode_idx<DecodeIdxTables>(ctx, k, m, (flags & RS_DECODE_IDX_STORE) != 0, false, ids, sizes,
+                                            fl.data(),
+                                            [&](int b, int i) { return input[static_cast<size_t>(b) * n + i]; },
+                                            [&](int b, int i) { return dst[static_cast<size_t>(b) * n + i]; })))
     return rc;
   return first_error(status, batch);
 }
@@ -743,6 +744,67 @@ int rs_decode_idx(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* dst, cons
                   const uint8_t* const* input, unsigned flags) {
   int status = RS_OK;
   const int rc = rs_decode_idx_batch(ctx, k, m, 1, &S, dst, expect, input, flags, &status);
+  return rc ? rc : status;
+}
+
+// rs_decode_idx_batch with compared shards. A stripe in the launch -- an input
+// and a wanted or check row, or under RS_DECODE_CHECK_FINAL a check row alone -- runs; a final
+// call's flagged stripe is RS_E_CORRUPT, with its wanted rows delivered all the same.
+int rs_decode_check_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes, uint8_t* const* dst,
+                          uint8_t* const* check, const uint8_t* expect, const uint8_t* const* input,
+                          unsigned flags, int* status) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!sizes || !dst || !check || !expect || !input || !status)) ||
+      (flags & ~(RS_DECODE_IDX_STORE | RS_DECODE_CHECK_FINAL)))
+    return RS_E_ARG;
+  const bool final = (flags & RS_DECODE_CHECK_FINAL) != 0;
+  const size_t B = static_cast<size_t>(batch), n = static_cast<size_t>(k + m);
+  std::vector<uint8_t> fl(B * n, 0);
+  std::vector<int> ids;
+  for (size_t b = 0; b < B; ++b) {
+    int ne = 0;
+    bool in = false, row = false, chk = false, misplaced = false;
+    for (size_t i = 0; i < n; ++i) {
+      const size_t at = b * n + i;
+      const bool e = expect[at] != 0;
+      ne += e;
+      in |= input[at] != nullptr;
+      row |= dst[at] != nullptr || check[at] != nullptr;
+      chk |= check[at] != nullptr;
+      misplaced |= e ? dst[at] != nullptr || check[at] != nullptr
+                     : (input[at] != nullptr && !check[at]) || (check[at] != nullptr && dst[at] != nullptr);
+      fl[at] = static_cast<uint8_t>((e ? 1 : 0) | (input[at] ? 2 : 0) | (dst[at] ? 4 : 0) | (check[at] ? 8 : 0));
+    }
+    if (ne < k) status[b] = RS_E_TOO_FEW_SHARDS;
+    else if (ne > k || misplaced) status[b] = RS_E_ARG;
+    else if (!((in && row) || (final && chk))) status[b] = RS_OK;
+    else if (sizes[b] == 0) status[b] = RS_E_NO_DATA;
+    else {
+      status[b] = RS_OK;
+      ids.push_back(static_cast<int>(b));
+    }
+  }
+  std::vector<int> corrupt(B, 0);
+  if ((rc = run_decode_idx<DecodeCheckTables>(
+           ctx, k, m, (flags & RS_DECODE_IDX_STORE) != 0, final, ids, sizes, fl.data(),
+           [&](int b, int i) { return input[static_cast<size_t>(b) * n + i]; },
+           [&](int b, int i) {
+             const size_t at = static_cast<size_t>(b) * n + i;
+             return check[at] ? check[at] : dst[at];
+           },
+           corrupt.data())))
+    return rc;
+  for (int b : ids)
+    if (corrupt[static_cast<size_t>(b)]) status[b] = RS_E_CORRUPT;
+  return first_error(status, batch);
+}
+
+int rs_decode_check(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* dst, uint8_t* const* check,
+                    const uint8_t* expect, const uint8_t* const* input, unsigned flags) {
+  int status = RS_OK;
+  const int rc = rs_decode_check_batch(ctx, k, m, 1, &S, dst, check, expect, input, flags, &status);
   return rc ? rc : status;
 }
 

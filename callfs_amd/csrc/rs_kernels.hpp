@@ -314,6 +314,27 @@ constexpr int kOrderDecodeIdx = 32768;
 hipError_t launch_decode_idx(ApplyArgs a, const MergeArgs& x, bool store, bool any_tail,
                              hipStream_t stream, LaunchEvents ev = {});
 
+// ---- final decode-check launches (rs_check.hpp in rs_mixed.hip) ----------
+// Progressive Verify: a decode-idx launch group in which some rows are check rows, syndrome
+// accumulators that the final launch tests instead of writing. For r < nrows[pat[s]] with bit r
+// of cmask[pat[s]] set, the value out[s][r] would have received (merge: its bytes XOR the
+// computed row; store: the computed row, out[s][r] never read) is tested byte by byte, nothing is
+// stored, and a nonzero byte ORs 1 into status[s * status_stride]; the other rows are merged or
+// stored as by launch_decode_idx. A pattern may have no source at all (nsrc 0, and a.K 0 when no
+// pattern has one): its rows' current bytes are what is tested (merge) and nothing else moves.
+struct CheckArgs {
+  MergeArgs m;
+  const uint32_t* cmask;  // [P] bit r: row r of pattern p in this launch group is a check row
+};
+
+// Enqueues the launch group: rs_check_ragged (store: its STORE instances) over every mapped
+// stripe's [0, size); a.status is required; tails, misaligned shards, order and slicing as
+// launch_decode_idx (rs_plan_forms: kOrderDecodeCheck of order_code.hpp + consecutive);
+// x.m.u.ntiles == 0 enqueues nothing. A merge launch with a row that is no check row is NOT
+// idempotent; every other launch is.
+hipError_t launch_decode_check(ApplyArgs a, const CheckArgs& x, bool store, bool any_tail,
+                               hipStream_t stream, LaunchEvents ev = {});
+
 // ---- locate launches (rs_mixed.hip) --------------------------------------
 // A required launch group in which every row is compared and none written, and a mismatching
 // byte column is classified instead of only flagged: locate_classify (locate_tables.hpp) turns

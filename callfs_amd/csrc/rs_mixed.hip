@@ -22,6 +22,7 @@
 #include "launch_util.hpp"
 #include "locate_tables.hpp"
 #include "rs_apply.hpp"
+#include "rs_check.hpp"
 #include "rs_merge.hpp"
 #include "rs_update.hpp"
 
@@ -598,10 +599,18 @@ const std::array<std::array<MergeFn, 3>, 2> kMerge = {{
     {kMergeInstance<4, false>, kMergeInstance<8, false>, kMergeInstance<16, false>},
     {kMergeInstance<4, true>, kMergeInstance<8, true>, kMergeInstance<16, true>}}};
 
+// Final decode-check launches (rs_check.hpp): [store][0: R <= 4, 1: R 5..8, 2: R 9..16]
+using CheckFn = void (*)(ApplyArgs, CheckArgs);
+template <int RT, bool STORE>
+constexpr CheckFn kCheckInstance = &dev::rs_check_ragged<RT, dev::UpdatePolicyFor<RT, false>, STORE>;
+const std::array<std::array<CheckFn, 3>, 2> kCheck = {{
+    {kCheckInstance<4, false>, kCheckInstance<8, false>, kCheckInstance<16, false>},
+    {kCheckInstance<4, true>, kCheckInstance<8, true>, kCheckInstance<16, true>}}};
+
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
 // per-device attribute (dispatch.hpp DeviceOnce), keyed by the 16-row instance it is set on
 enum class WideLds { kMixed, kRagged, kRaggedSome, kUpdate, kUpdatePair, kLocate, kLocate2, kCorrect,
-                     kMerge, kMergeStore };
+                     kMerge, kMergeStore, kCheck, kCheckStore };
 DeviceOnce g_mixed_wide_lds;
 
 // The vector launch every kind shares: the dynamic-LDS opt-in, then `grid` tiles in equal
@@ -732,6 +741,24 @@ hipError_t launch_decode_idx(ApplyArgs a, const MergeArgs& x, bool store, bool a
   return launch_tiles(kMerge[store ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0],
                       store ? WideLds::kMergeStore : WideLds::kMerge, x.u.ntiles, a, x,
                       a.K + (store ? 1 : 2) * a.R, stream, ev);
+}
+
+hipError_t launch_decode_check(ApplyArgs a, const CheckArgs& x, bool store, bool any_tail,
+                               hipStream_t stream, LaunchEvents ev) {
+  const UpdateArgs& u = x.m.u;
+  // tile_map_ok, but for a.K: no pattern of a final launch need have a source
+  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 0 || a.K > kMaxK || a.batch < 1 || !a.ltabs || !u.pat ||
+      !u.size || !u.tile0 || !a.in_tab || !a.out_tab || u.ntiles > 0x7fffffffu || (u.ntiles != 0 && !u.tile_stripe) ||
+      !u.nsrc || !x.m.nrows || !x.cmask || !a.status || u.in_stride != static_cast<uint32_t>(a.K))
+    return hipErrorInvalidValue;
+  if (u.ntiles == 0) return hipSuccess;  // no stripe has a row
+  a.t_base = 0;
+  a.S = a.nvec = 0;  // per stripe, read by the kernel
+  a.verify_mask = 0;
+  a.tail_in_vec = any_tail ? 1u : 0u;  // wave 0 of each stripe's first tile
+  // per tile: the sources, and every row read (merge) or written (store) at least once
+  return launch_tiles(kCheck[store ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0],
+                      store ? WideLds::kCheckStore : WideLds::kCheck, u.ntiles, a, x, a.K + a.R, stream, ev);
 }
 
 }  // namespace callfs

@@ -7,6 +7,7 @@
 // tile-order tuner and the one-shot device calls built on them.
 #include <cstdio>
 
+#include "decode_check_tables.hpp"
 #include "decode_idx_tables.hpp"
 #include "locate_tables.hpp"
 #include "mixed_tables.hpp"
@@ -55,10 +56,14 @@ struct MixedPlan {
 // update_tables.hpp sit in the plan's device buffer. One tile map, over the stripes with a
 // changed shard, for every launch group; no launch group at all when nothing changed.
 // A decode-idx plan (rs_plan_create_decode_idx, §5.14) is laid out the same way from
-// decode_idx_tables.hpp: single sources, and per launch group the patterns' row counts.
+// decode_idx_tables.hpp: single sources, and per launch group the patterns' row counts. A
+// decode-check plan (rs_plan_create_decode_check, §5.15) is a decode-idx plan from
+// decode_check_tables.hpp that also holds per launch group the patterns' check rows; a final one
+// launches the kernel that tests them.
 struct UpdatePlan {
   bool pair = true;  // sources are (old, new) pairs; false: EncodeIdx mode
   bool decode_idx = false, store = false;  // a decode-idx plan, and whether it stores or merges
+  bool check_final = false;                // a final decode-check plan (decode_idx is set too)
   int cmax = 0;
   size_t in_off = 0, pat_off = 0, nsrc_off = 0, size_off = 0, tile0_off = 0, tile_stripe_off = 0;
   uint32_t ntiles = 0;
@@ -68,6 +73,7 @@ struct UpdatePlan {
     size_t out_off, arena_off;
     uint32_t tab_stride;
     size_t nrows_off = 0;  // a decode-idx plan's [P] row counts
+    size_t cmask_off = 0;  // a decode-check plan's [P] check-row masks (read by a final one)
   };
   std::vector<Group> groups;
 };
@@ -178,11 +184,18 @@ hipError_t plan_launch(const rs_plan& plan, hipStream_t s, const std::vector<int
       x.tab_stride = g.tab_stride;
       x.ntiles = up.ntiles;
       x.in_stride = static_cast<uint32_t>(up.cmax) * (up.pair ? 2u : 1u);
-      const hipError_t e =
-          up.decode_idx
-              ? launch_decode_idx(a, MergeArgs{x, reinterpret_cast<const uint32_t*>(d + g.nrows_off)}, up.store,
-                                  up.any_tail, s, group_events(ev, gi, ng))
-              : launch_update(a, x, up.pair, up.any_tail, s, group_events(ev, gi, ng));
+      const MergeArgs xm{x, reinterpret_cast<const uint32_t*>(d + g.nrows_off)};
+      hipError_t e;
+      if (up.check_final) {
+        a.status = reinterpret_cast<int*>(d + plan.status_off);
+        a.status_stride = 1;
+        e = launch_decode_check(a, CheckArgs{xm, reinterpret_cast<const uint32_t*>(d + g.cmask_off)}, up.store,
+                                up.any_tail, s, group_events(ev, gi, ng));
+      } else if (up.decode_idx) {
+        e = launch_decode_idx(a, xm, up.store, up.any_tail, s, group_events(ev, gi, ng));
+      } else {
+        e = launch_update(a, x, up.pair, up.any_tail, s, group_events(ev, gi, ng));
+      }
       if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -495,6 +508,87 @@ int one_shot(Create create, void* stream) {
   return rc;
 }
 
+const std::vector<int>& pattern_rows(const DecodeIdxPattern& p) { return p.wanted; }
+const std::vector<int>& pattern_rows(const DecodeCheckPattern& p) { return p.rows; }
+const std::vector<uint32_t>* group_cmask(const DecodeIdxGroup&) { return nullptr; }
+const std::vector<uint32_t>* group_cmask(const DecodeCheckGroup& g) { return &g.cmask; }
+
+// The body of the decode-idx and decode-check constructors once the tables stand: the plan's
+// layout, its pointer tables and the upload. T: DecodeIdxTables or DecodeCheckTables; row(at):
+// the pointer of the row at entry at = b * n + i (a wanted shard, or a check accumulator).
+template <class T, class Row>
+int finish_decode_plan(int device, const T& t, const size_t* sizes, const uint8_t* const* input, Row row,
+                       bool store, bool check_final, uint64_t bytes, rs_plan** out) {
+  const int batch = t.batch, n = t.k + t.m;
+  size_t smax = 0;
+  for (int b = 0; b < batch; ++b)
+    if (t.has[static_cast<size_t>(b)]) smax = std::max(smax, sizes[b]);
+  auto plan = new_plan(device, smax, batch);
+  plan->update = std::make_unique<UpdatePlan>();
+  UpdatePlan& up = *plan->update;
+  up.pair = false;
+  up.decode_idx = true;
+  up.store = store;
+  up.check_final = check_final;
+  up.cmax = t.cmax;
+  up.ntiles = t.map.ntiles;
+  up.any_tail = t.map.any_tail;
+  plan->fixed_form = RS_ORDER_CONSECUTIVE + (check_final ? kOrderDecodeCheck : kOrderDecodeIdx);
+  plan->bytes = bytes;
+  const size_t stride = static_cast<size_t>(t.cmax);
+  const size_t P = t.patterns.size();
+  Packer pk;
+  plan->status_off = pk.take(sizeof(int) * static_cast<size_t>(batch));
+  up.in_off = pk.take(sizeof(void*) * std::max<size_t>(1, static_cast<size_t>(batch) * stride));
+  up.pat_off = pk.take(sizeof(uint32_t) * static_cast<size_t>(batch));
+  up.nsrc_off = pk.take(sizeof(uint32_t) * std::max<size_t>(1, P));
+  up.size_off = pk.take(sizeof(uint64_t) * static_cast<size_t>(batch));
+  up.tile0_off = pk.take(sizeof(uint32_t) * t.map.tile0.size());
+  up.tile_stripe_off = pk.take(sizeof(uint32_t) * std::max<size_t>(1, t.map.tile_stripe.size()));
+  for (const auto& g : t.groups) {
+    UpdatePlan::Group at{g.R, pk.take(sizeof(void*) * static_cast<size_t>(batch) * g.R),
+                         pk.take(std::max<size_t>(1, g.arena.size())), static_cast<uint32_t>(g.tab_stride)};
+    at.nrows_off = pk.take(sizeof(uint32_t) * P);
+    if (group_cmask(g)) at.cmask_off = pk.take(sizeof(uint32_t) * P);
+    up.groups.push_back(at);
+  }
+  std::vector<uint8_t> h(pk.off, 0);
+  auto put = [&](size_t off, const auto& v) {
+    if (!v.empty()) std::memcpy(h.data() + off, v.data(), sizeof(v[0]) * v.size());
+  };
+  // sources of stripe b: its pattern's delivered shards in ascending order; slots past its
+  // source count, and every slot of a stripe in no launch, stay null and unread
+  auto* in = reinterpret_cast<const uint8_t**>(h.data() + up.in_off);
+  for (int b = 0; b < batch; ++b) {
+    if (!t.has[static_cast<size_t>(b)]) continue;
+    const std::vector<int>& idx = t.patterns[t.pat[static_cast<size_t>(b)]].delivered;
+    for (size_t c = 0; c < idx.size(); ++c) in[b * stride + c] = input[static_cast<size_t>(b) * n + idx[c]];
+  }
+  put(up.pat_off, t.pat);
+  put(up.nsrc_off, t.nsrc);
+  put(up.size_off, t.size);
+  put(up.tile0_off, t.map.tile0);
+  put(up.tile_stripe_off, t.map.tile_stripe);
+  for (size_t gi = 0; gi < t.groups.size(); ++gi) {
+    const auto& g = t.groups[gi];
+    // rows of stripe b in this group: its pattern's rows row0 .. row0 + nrows[p]
+    auto* o = reinterpret_cast<uint8_t**>(h.data() + up.groups[gi].out_off);
+    for (int b = 0; b < batch; ++b) {
+      if (!t.has[static_cast<size_t>(b)]) continue;
+      const uint32_t p = t.pat[static_cast<size_t>(b)];
+      const std::vector<int>& w = pattern_rows(t.patterns[p]);
+      for (uint32_t r = 0; r < g.nrows[p]; ++r)
+        o[static_cast<size_t>(b) * g.R + r] = row(static_cast<size_t>(b) * n + w[g.row0 + r]);
+    }
+    put(up.groups[gi].arena_off, g.arena);
+    put(up.groups[gi].nrows_off, g.nrows);
+    if (const std::vector<uint32_t>* cm = group_cmask(g)) put(up.groups[gi].cmask_off, *cm);
+  }
+  if (const int rc = upload(plan->dmeta, device, h.data(), h.size())) return rc;
+  *out = plan.release();
+  return RS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -692,8 +786,7 @@ int rs_plan_create_decode_idx(rs_ctx* ctx, int device, int k, int m, int batch, 
   int rc = check_plan_args(ctx, k, m, batch, sizes && expect && input && dst && !(flags & ~RS_DECODE_IDX_STORE),
                            out);
   if (rc) return rc;
-  const int n = k + m;
-  const size_t cells = static_cast<size_t>(batch) * n;
+  const size_t cells = static_cast<size_t>(batch) * (k + m);
   std::vector<uint8_t> have_in(cells), have_dst(cells);
   for (size_t i = 0; i < cells; ++i) {
     have_in[i] = input[i] != nullptr;
@@ -705,70 +798,35 @@ int rs_plan_create_decode_idx(rs_ctx* ctx, int device, int k, int m, int batch, 
     return rc;
   if (!ctx->device(device)) return RS_E_ARG;
   const bool store = (flags & RS_DECODE_IDX_STORE) != 0;
-  size_t smax = 0;
-  for (int b = 0; b < batch; ++b)
-    if (t.has[static_cast<size_t>(b)]) smax = std::max(smax, sizes[b]);
-  auto plan = new_plan(device, smax, batch);
-  plan->update = std::make_unique<UpdatePlan>();
-  UpdatePlan& up = *plan->update;
-  up.pair = false;
-  up.decode_idx = true;
-  up.store = store;
-  up.cmax = t.cmax;
-  up.ntiles = t.map.ntiles;
-  up.any_tail = t.map.any_tail;
-  plan->fixed_form = RS_ORDER_CONSECUTIVE + kOrderDecodeIdx;
-  plan->bytes = store ? t.bytes_store : t.bytes_merge;
-  const size_t stride = static_cast<size_t>(t.cmax);
-  const size_t P = t.patterns.size();
-  Packer pk;
-  plan->status_off = pk.take(sizeof(int) * static_cast<size_t>(batch));
-  up.in_off = pk.take(sizeof(void*) * std::max<size_t>(1, static_cast<size_t>(batch) * stride));
-  up.pat_off = pk.take(sizeof(uint32_t) * static_cast<size_t>(batch));
-  up.nsrc_off = pk.take(sizeof(uint32_t) * std::max<size_t>(1, P));
-  up.size_off = pk.take(sizeof(uint64_t) * static_cast<size_t>(batch));
-  up.tile0_off = pk.take(sizeof(uint32_t) * t.map.tile0.size());
-  up.tile_stripe_off = pk.take(sizeof(uint32_t) * std::max<size_t>(1, t.map.tile_stripe.size()));
-  for (const DecodeIdxGroup& g : t.groups) {
-    UpdatePlan::Group at{g.R, pk.take(sizeof(void*) * static_cast<size_t>(batch) * g.R),
-                         pk.take(g.arena.size()), static_cast<uint32_t>(g.tab_stride)};
-    at.nrows_off = pk.take(sizeof(uint32_t) * P);
-    up.groups.push_back(at);
+  return finish_decode_plan(device, t, sizes, input, [&](size_t at) { return dst[at]; }, store, false,
+                            store ? t.bytes_store : t.bytes_merge, out);
+}
+
+int rs_plan_create_decode_check(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                                const uint8_t* expect, const uint8_t* const* input, uint8_t* const* dst,
+                                uint8_t* const* check, unsigned flags, rs_plan** out) {
+  DeviceGuard dg;
+  int rc = check_plan_args(ctx, k, m, batch,
+                           sizes && expect && input && dst && check &&
+                               !(flags & ~(RS_DECODE_IDX_STORE | RS_DECODE_CHECK_FINAL)),
+                           out);
+  if (rc) return rc;
+  const size_t cells = static_cast<size_t>(batch) * (k + m);
+  std::vector<uint8_t> have_in(cells), have_dst(cells), have_chk(cells);
+  for (size_t i = 0; i < cells; ++i) {
+    have_in[i] = input[i] != nullptr;
+    have_dst[i] = dst[i] != nullptr;
+    have_chk[i] = check[i] != nullptr;
   }
-  std::vector<uint8_t> h(pk.off, 0);
-  auto put = [&](size_t off, const auto& v) {
-    if (!v.empty()) std::memcpy(h.data() + off, v.data(), sizeof(v[0]) * v.size());
-  };
-  // sources of stripe b: its pattern's delivered shards in ascending order; slots past its
-  // source count, and every slot of a stripe in no launch, stay null and unread
-  auto* in = reinterpret_cast<const uint8_t**>(h.data() + up.in_off);
-  for (int b = 0; b < batch; ++b) {
-    if (!t.has[static_cast<size_t>(b)]) continue;
-    const std::vector<int>& idx = t.patterns[t.pat[static_cast<size_t>(b)]].delivered;
-    for (size_t c = 0; c < idx.size(); ++c) in[b * stride + c] = input[static_cast<size_t>(b) * n + idx[c]];
-  }
-  put(up.pat_off, t.pat);
-  put(up.nsrc_off, t.nsrc);
-  put(up.size_off, t.size);
-  put(up.tile0_off, t.map.tile0);
-  put(up.tile_stripe_off, t.map.tile_stripe);
-  for (size_t gi = 0; gi < t.groups.size(); ++gi) {
-    const DecodeIdxGroup& g = t.groups[gi];
-    // rows of stripe b in this group: its pattern's wanted shards row0 .. row0 + nrows[p]
-    auto* o = reinterpret_cast<uint8_t**>(h.data() + up.groups[gi].out_off);
-    for (int b = 0; b < batch; ++b) {
-      if (!t.has[static_cast<size_t>(b)]) continue;
-      const uint32_t p = t.pat[static_cast<size_t>(b)];
-      const std::vector<int>& w = t.patterns[p].wanted;
-      for (uint32_t r = 0; r < g.nrows[p]; ++r)
-        o[static_cast<size_t>(b) * g.R + r] = dst[static_cast<size_t>(b) * n + w[g.row0 + r]];
-    }
-    put(up.groups[gi].arena_off, g.arena);
-    put(up.groups[gi].nrows_off, g.nrows);
-  }
-  if ((rc = upload(plan->dmeta, device, h.data(), h.size()))) return rc;
-  *out = plan.release();
-  return RS_OK;
+  const bool store = (flags & RS_DECODE_IDX_STORE) != 0, final = (flags & RS_DECODE_CHECK_FINAL) != 0;
+  DecodeCheckTables t;
+  if ((rc = decode_idx_status(build_decode_check_tables(k, m, batch, sizes, expect, have_in.data(),
+                                                        have_dst.data(), have_chk.data(), final, t))))
+    return rc;
+  if (!ctx->device(device)) return RS_E_ARG;
+  // a non-final plan runs the decode-idx kernels: a check row is an ordinary row there
+  return finish_decode_plan(device, t, sizes, input, [&](size_t at) { return check[at] ? check[at] : dst[at]; },
+                            store, final, t.bytes[(final ? 2 : 0) + (store ? 1 : 0)], out);
 }
 
 void rs_plan_destroy(rs_plan* plan) {

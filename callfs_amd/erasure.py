@@ -803,6 +803,73 @@ def decode_idx_batch(dst: Sequence[Sequence], expect: Sequence[Sequence[bool]],
     return out
 
 
+def _decode_check_rows(dst, check, expect, inputs, k, m):
+    """_decode_idx_rows with the accumulators: writable, of the stripe's shard size, at indices
+    that are not wanted."""
+    if len(check) != k + m or len(dst) != k + m:
+        raise ErrTooFewShards()
+    if any(d is not None and c is not None for d, c in zip(dst, check)):
+        raise ErrInvalidInput()
+    return _decode_idx_rows([d if d is not None else c for d, c in zip(dst, check)], expect, inputs, k, m)
+
+
+def _decode_check_bits(store, final):
+    return (N.RS_DECODE_IDX_STORE if store else 0) | (N.RS_DECODE_CHECK_FINAL if final else 0)
+
+
+def decode_check(dst: Sequence, check: Sequence, expect: Sequence[bool], inputs: Sequence, k: int, m: int,
+                 store: bool = False, final: bool = False, context: Optional[N.Context] = None) -> None:
+    """decode_idx that also checks the shards fetched beyond the k expected ones (DESIGN.md
+    §5.15). check (k+m entries, None = not compared) are writable syndrome accumulators at
+    indices that are neither expected nor wanted; inputs may then deliver the compared shard
+    itself. Every call adds the delivered expected shards' terms, and the compared shard when it
+    arrives, into its accumulator (store=True: stores them). final=True writes no accumulator:
+    the value it would have received is tested, and a nonzero byte raises ErrShardCorrupted
+    after the wanted shards have been written -- what upstream Decode's Verify reports. With
+    store=True as well the accumulators are not read: the one-shot decode plus Verify."""
+    ctx = context or N.default_context()
+    S = _decode_check_rows(dst, check, expect, inputs, k, m)
+    ex = (ctypes.c_uint8 * (k + m))(*[1 if e else 0 for e in expect])
+    rc = N.lib.rs_decode_check(ctx.handle, k, m, S, _shard_ptrs(list(dst)), _shard_ptrs(list(check)), ex,
+                               _shard_ptrs(list(inputs)), _decode_check_bits(store, final))
+    if rc == N.RS_E_ARG:
+        raise ErrInvalidInput()
+    if rc == N.RS_E_INVALID_PROFILE:
+        raise ErrInvalidProfile()
+    if rc == N.RS_E_CORRUPT:
+        raise ErrShardCorrupted()
+    if rc != N.RS_OK:
+        raise _wrapped(rc, "decode_check")
+
+
+def decode_check_batch(dst: Sequence[Sequence], check: Sequence[Sequence], expect: Sequence[Sequence[bool]],
+                       inputs: Sequence[Sequence], k: int, m: int, store: bool = False, final: bool = False,
+                       context: Optional[N.Context] = None) -> List[int]:
+    """rs_decode_check_batch: stripe b has dst[b], check[b], expect[b] and inputs[b] as
+    decode_check takes them. Returns status[b] (RS_OK, RS_E_TOO_FEW_SHARDS, RS_E_ARG,
+    RS_E_NO_DATA, and with final=True RS_E_CORRUPT for a stripe whose compared shards do not
+    lie on the expected shards' codeword)."""
+    ctx = context or N.default_context()
+    B = len(dst)
+    if len(check) != B or len(expect) != B or len(inputs) != B:
+        raise ValueError("one row of dst / check / expect / input entries per stripe")
+    sizes = (ctypes.c_size_t * max(B, 1))()
+    for b in range(B):
+        sizes[b] = _decode_check_rows(dst[b], check[b], expect[b], inputs[b], k, m)
+
+    def ptrs(rows):
+        return _shard_ptrs([s for row in rows for s in row] or [None])
+
+    ex = (ctypes.c_uint8 * max(1, B * (k + m)))(*[1 if e else 0 for row in expect for e in row])
+    status = (ctypes.c_int * max(B, 1))()
+    rc = N.lib.rs_decode_check_batch(ctx.handle, k, m, B, sizes, ptrs(dst), ptrs(check), ex, ptrs(inputs),
+                                     _decode_check_bits(store, final), status)
+    out = list(status)[:B]
+    if rc != N.RS_OK and rc not in out:
+        N.check(rc, "rs_decode_check_batch")
+    return out
+
+
 def verify(shards: List, k: int, m: int, context: Optional[N.Context] = None) -> bool:
     """upstream enc.Verify(shards) (codec.go:59)."""
     ctx = context or N.default_context()

@@ -155,6 +155,29 @@ func (c *Codec) DecodeIdxBatch(dst [][][]byte, expectInput [][]bool, input [][][
 	return errs
 }
 
+// DecodeCheck is DecodeIdx with compared shards (DESIGN.md §5.15) on builds without the GPU
+// codec.
+func (c *Codec) DecodeCheck(dst, check [][]byte, expectInput []bool, input [][]byte, final bool, profile ErasureProfile) error {
+	if profile.DataShards < 1 || profile.ParityShards < 1 {
+		return ErrInvalidProfile
+	}
+	return cpuDecodeCheck(dst, check, expectInput, input, final, profile.DataShards, profile.ParityShards)
+}
+
+// DecodeCheckBatch is DecodeCheck per stripe on builds without the GPU codec.
+func (c *Codec) DecodeCheckBatch(dst, check [][][]byte, expectInput [][]bool, input [][][]byte, final bool, profile ErasureProfile) []error {
+	errs := make([]error, len(dst))
+	for b := range dst {
+		if len(check) != len(dst) || len(expectInput) != len(dst) || len(input) != len(dst) {
+			errs[b] = fmt.Errorf("erasure: %d check rows, %d expect rows and %d input rows for %d stripes", len(check),
+				len(expectInput), len(input), len(dst))
+			continue
+		}
+		errs[b] = c.DecodeCheck(dst[b], check[b], expectInput[b], input[b], final, profile)
+	}
+	return errs
+}
+
 // ErrLocateUnavailable is what Locate reports on builds without the GPU codec: the CPU codec
 // has no locator (the reference finds a bad shard by its checksum, manager.go:250-320).
 var ErrLocateUnavailable = errors.New("erasure: locating corrupt shards needs the GPU codec")

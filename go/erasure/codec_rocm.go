@@ -1052,6 +1052,127 @@ func (c *Codec) DecodeIdxBatch(dst [][][]byte, expectInput [][]bool, input [][][
 	return errs
 }
 
+// ---- progressive Verify (DESIGN.md §5.15) ------------------------------------------------
+
+// DecodeCheck is DecodeIdx that also checks the shards fetched beyond the k expected ones
+// (rs_decode_check): check (k+m entries, nil = not compared) holds one syndrome accumulator per
+// compared shard, at indices that are neither expected nor wanted, zeroed before the first call;
+// input may then deliver the compared shard itself. Every call adds the delivered expected
+// shards' terms, and the compared shard when it arrives, into its accumulator. A final call
+// writes no accumulator: it tests the value each would have received and returns
+// ErrShardCorrupted when a byte of it is nonzero -- after the wanted shards have been written,
+// as Decode's Verify fails after Reconstruct. RetrieveFile with DecodeCheck is Decode, Verify
+// included. Not in the reference API.
+func (c *Codec) DecodeCheck(dst, check [][]byte, expectInput []bool, input [][]byte, final bool, profile ErasureProfile) error {
+	errs := c.DecodeCheckBatch([][][]byte{dst}, [][][]byte{check}, [][]bool{expectInput}, [][][]byte{input}, final, profile)
+	return errs[0]
+}
+
+// DecodeCheckBatch is DecodeCheck for many stripes of one profile in one call
+// (rs_decode_check_batch); errs[b] is what DecodeCheck would report for stripe b.
+func (c *Codec) DecodeCheckBatch(dst, check [][][]byte, expectInput [][]bool, input [][][]byte, final bool, profile ErasureProfile) []error {
+	k, m := profile.DataShards, profile.ParityShards
+	errs := make([]error, len(dst))
+	if len(check) != len(dst) || len(expectInput) != len(dst) || len(input) != len(dst) {
+		for b := range errs {
+			errs[b] = fmt.Errorf("erasure: %d check rows, %d expect rows and %d input rows for %d stripes", len(check),
+				len(expectInput), len(input), len(dst))
+		}
+		return errs
+	}
+	if k < 1 || m < 1 {
+		for b := range errs {
+			errs[b] = ErrInvalidProfile
+		}
+		return errs
+	}
+	if len(dst) == 0 {
+		return errs
+	}
+	if k+m > 256 || device() == nil {
+		for b := range dst {
+			errs[b] = cpuDecodeCheck(dst[b], check[b], expectInput[b], input[b], final, k, m)
+		}
+		return errs
+	}
+	B, n := len(dst), k+m
+	ins, outs, accs := newCArray(B*n), newCArray(B*n), newCArray(B*n)
+	defer ins.free()
+	defer outs.free()
+	defer accs.free()
+	sizes := make([]C.size_t, B)
+	status := make([]C.int, B)
+	expect := make([]C.uint8_t, B*n)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for b := range dst {
+		var S int
+		var err error
+		if len(check[b]) != n || len(dst[b]) != n {
+			err = fmt.Errorf("erasure: failed to decode: %w", reedsolomon.ErrTooFewShards)
+		} else {
+			// the accumulators take part in the size check as the destinations do
+			rows := make([][]byte, n)
+			for i := range rows {
+				rows[i] = dst[b][i]
+				if len(check[b][i]) > 0 {
+					rows[i] = check[b][i]
+				}
+			}
+			S, err = checkDecodeIdx(rows, expectInput[b], input[b], k, m)
+		}
+		if err != nil {
+			errs[b] = err
+			for i := 0; i < k && i < n; i++ { // a well-formed stripe with nothing to do for the library
+				expect[b*n+i] = 1
+			}
+			continue
+		}
+		sizes[b] = C.size_t(S)
+		for i := 0; i < n; i++ {
+			if expectInput[b][i] {
+				expect[b*n+i] = 1
+			}
+			if len(input[b][i]) > 0 {
+				pin.Pin(&input[b][i][0])
+				ins.set(b*n+i, unsafe.Pointer(&input[b][i][0]))
+			}
+			if len(dst[b][i]) > 0 {
+				pin.Pin(&dst[b][i][0])
+				outs.set(b*n+i, unsafe.Pointer(&dst[b][i][0]))
+			}
+			if len(check[b][i]) > 0 {
+				pin.Pin(&check[b][i][0])
+				accs.set(b*n+i, unsafe.Pointer(&check[b][i][0]))
+			}
+		}
+	}
+	flags := C.uint(0)
+	if final {
+		flags = C.RS_DECODE_CHECK_FINAL
+	}
+	rc := C.rs_decode_check_batch(gpuCtx, C.int(k), C.int(m), C.int(B), &sizes[0], outs.at(0), accs.at(0), &expect[0],
+		ins.at(0), flags, &status[0])
+	if rc != C.RS_OK && !hasStatus(status, rc) { // a call-level error: no status was written
+		for b := range errs {
+			if errs[b] == nil {
+				errs[b] = decodeIdxErr(rc)
+			}
+		}
+		return errs
+	}
+	for b := range errs {
+		if errs[b] == nil {
+			if status[b] == C.RS_E_CORRUPT {
+				errs[b] = ErrShardCorrupted
+			} else {
+				errs[b] = decodeIdxErr(status[b])
+			}
+		}
+	}
+	return errs
+}
+
 // Overwrite replaces bytes [offset, offset+len(data)) of the object whose n shards these are
 // (Encode's layout: object byte x in data shard x/S at column x%S) and brings the parity up to
 // date (rs_codec_overwrite): only the affected parity columns are read and rewritten, through

@@ -7,8 +7,8 @@ import (
 )
 
 // The CPU forms of the calls that update parity in place (UpdateParity, EncodeIdx, UpdateBatch,
-// Overwrite) and of the progressive decode (DecodeIdx, DecodeIdxBatch): upstream Update /
-// EncodeIdx / DecodeIdx. Both builds use them: the default build for every
+// Overwrite) and of the progressive decode (DecodeIdx, DecodeIdxBatch, DecodeCheck,
+// DecodeCheckBatch): upstream Update / EncodeIdx / DecodeIdx. Both builds use them: the default build for every
 // call, the GPU build for k+m > 256 and when there is no device.
 
 // cpuUpdateParity is upstream enc.Update(shards, newData): shards holds the old data shards
@@ -46,6 +46,66 @@ func cpuDecodeIdx(dst [][]byte, expectInput []bool, input [][]byte, k, m int) er
 	}
 	if err := enc.DecodeIdx(dst, expectInput, input); err != nil {
 		return fmt.Errorf("erasure: failed to decode: %w", err)
+	}
+	return nil
+}
+
+// cpuDecodeCheck is DecodeCheck on the CPU (DESIGN.md §5.15): upstream DecodeIdx into the wanted
+// shards and the accumulators alike, the compared shards that arrive with the call XORed into
+// their accumulators, and in a final call the result tested for zero on copies, so that no
+// accumulator is written.
+func cpuDecodeCheck(dst, check [][]byte, expectInput []bool, input [][]byte, final bool, k, m int) error {
+	wrap := func(err error) error { return fmt.Errorf("erasure: failed to decode: %w", err) }
+	n := k + m
+	if len(dst) != n || len(check) != n || len(expectInput) != n || len(input) != n {
+		return wrap(reedsolomon.ErrTooFewShards)
+	}
+	rows, in := make([][]byte, n), make([][]byte, n)
+	fed := false
+	for i := 0; i < n; i++ {
+		rows[i] = dst[i]
+		if len(check[i]) > 0 {
+			if expectInput[i] || len(dst[i]) > 0 {
+				return wrap(reedsolomon.ErrInvalidInput)
+			}
+			rows[i] = check[i]
+			if final {
+				rows[i] = append([]byte(nil), check[i]...)
+			}
+		}
+		if len(input[i]) > 0 && !expectInput[i] {
+			if len(check[i]) == 0 {
+				return wrap(reedsolomon.ErrInvalidInput)
+			}
+			continue // the compared shard itself: XORed in below
+		}
+		in[i] = input[i]
+		fed = fed || len(input[i]) > 0
+	}
+	if fed {
+		if err := cpuDecodeIdx(rows, expectInput, in, k, m); err != nil {
+			return err
+		}
+	}
+	corrupt := false
+	for i := 0; i < n; i++ {
+		if len(check[i]) == 0 {
+			continue
+		}
+		if len(input[i]) > 0 {
+			if len(input[i]) != len(rows[i]) {
+				return wrap(reedsolomon.ErrShardSize)
+			}
+			for x, b := range input[i] {
+				rows[i][x] ^= b
+			}
+		}
+		for _, b := range rows[i] {
+			corrupt = corrupt || (final && b != 0)
+		}
+	}
+	if corrupt {
+		return ErrShardCorrupted
 	}
 	return nil
 }

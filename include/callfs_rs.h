@@ -330,6 +330,33 @@ int rs_decode_idx_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* size
                         uint8_t* const* dst, const uint8_t* expect,
                         const uint8_t* const* input, unsigned flags, int* status);
 
+/* ---- Progressive Verify, host memory --------------------------------
+ * rs_decode_idx and rs_decode_idx_batch with compared shards: expect, input, dst, check and flags
+ * exactly as for rs_plan_create_decode_check (below), the accumulators in host memory, and the
+ * same result. With RS_DECODE_CHECK_FINAL a stripe in which some compared shard differs from what
+ * the expected shards imply is RS_E_CORRUPT -- rs_decode_check's return value, status[b] of a
+ * batch -- and its wanted shards are delivered all the same, as upstream Decode delivers them
+ * before Verify fails; no check row is written.
+ * rs_decode_check: one stripe of S-byte shards. Errors in the plan constructor's order.
+ * rs_decode_check_batch: as rs_decode_idx_batch; the profile, NULL arrays (check included),
+ *   batch < 0 and an unknown flag bit fail the call, the per-stripe refusals land in status[b].
+ * A stripe that is in no launch -- no input, or no wanted and no check row; under FINAL a check
+ * row alone puts it into the launch -- keeps every byte; a call in which no stripe is reaches no
+ * device, moves no counter and returns RS_OK.
+ * Both take rs_decode_idx's staged pipeline, with the check rows staged as output rows: a chunk
+ * is one H2D of metadata and the delivered shards (final: and the chunk's zeroed status words);
+ * in merge mode a second H2D of the wanted and check rows' current bytes; one launch per group of
+ * 16 rows; one D2H of the rows, which under FINAL starts at the status words, is of them alone
+ * when the call has no wanted row, and from which no check row is copied back. `copies` of
+ * rs_host_counters: 2 per store chunk, 3 per merge chunk, final or not. A stripe above
+ * CALLFS_RS_CHUNK_BYTES is cut into column parts, and its flag is the OR of its parts' flags. The
+ * accumulators do not stay on the device between calls (use a decode-check plan for that). */
+int rs_decode_check(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* dst, uint8_t* const* check,
+                    const uint8_t* expect, const uint8_t* const* input, unsigned flags);
+int rs_decode_check_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes,
+                          uint8_t* const* dst, uint8_t* const* check, const uint8_t* expect,
+                          const uint8_t* const* input, unsigned flags, int* status);
+
 /* ---- counters of the host-memory path -----------------------------------------------
  * Monotonic per-context counts (relaxed atomics; what an operator graphs, and what shows
  * that a batch cost one round trip):
@@ -639,6 +666,66 @@ int rs_plan_create_decode_idx(rs_ctx* ctx, int device, int k, int m, int batch,
                               const size_t* sizes, const uint8_t* expect,
                               const uint8_t* const* input, uint8_t* const* dst,
                               unsigned flags, rs_plan** out);
+
+/* ---- decode-check plans: progressive Verify -------------------------
+ * A decode-idx plan that also checks the shards a download fetched beyond the k expected ones,
+ * so that a progressive decode ends with the Verify that upstream Decode makes (codec.go:59)
+ * without keeping the k expected shards resident. sizes, expect, input, dst and the store flag are
+ * those of rs_plan_create_decode_idx; a fourth array of batch * (k+m) pointers joins them:
+ *   check   (pointers) non-NULL = shard i is compared. Allowed only where expect[i] == 0 and
+ *                      dst[i] == NULL (RS_E_ARG otherwise). It names an S-byte syndrome
+ *                      accumulator owned by the caller, under dst's overlap contract: no byte of
+ *                      it overlaps a dst or check byte of another stripe or row, or any input.
+ *   input   (pointers) non-NULL is allowed at an expected index, or at an index whose check entry
+ *                      is non-NULL in the same call: the compared shard itself arriving. An input
+ *                      at any other index is RS_E_ARG.
+ *   flags              RS_DECODE_IDX_STORE and RS_DECODE_CHECK_FINAL; any other bit is RS_E_ARG.
+ * Wanted rows are computed as by a decode-idx plan; a compared shard's delivery adds nothing to
+ * them. With V and C as there, a launch sets for every compared j
+ *     check[j] (^)= sum over the delivered expected v of C[j][v] * input[v]
+ *                   ^ input[j] if shard j is delivered with this plan
+ * with ^= in merge mode and = under RS_DECODE_IDX_STORE. After every expected shard and shard j
+ * have been delivered once, in any order and grouping -- from a zeroed accumulator, or when the
+ * first launch stores -- check[j] is shard j XOR the shard the k expected ones imply: all zero
+ * exactly when shard j lies on their codeword.
+ * RS_DECODE_CHECK_FINAL changes what happens to the check rows: a check row is NOT WRITTEN; every
+ * byte of the value it would have received is tested, and a nonzero byte sets the stripe's status
+ * word, which rs_plan_status and rs_plan_stripe_status report and clear as for every compare.
+ * Wanted rows are still written. With FINAL|STORE check rows are neither read nor written and the
+ * pointer only marks the index: the one-shot decode plus Verify. Under FINAL a stripe with a
+ * check row is in the launch even when nothing is delivered with this plan, and the launch then
+ * only scans its accumulators; without FINAL a stripe needs an input and a (wanted or check) row
+ * to be in the launch. So after every expected and every compared shard has been delivered once,
+ * the last launch being FINAL, dst holds a reconstruct's bytes from exactly the k expected
+ * shards, and the stripe's flag is set exactly when some compared shard differs from what the
+ * expected shards imply -- the flag the compare launches of a ragged plan report for
+ * present = expected and compared. A compared shard that never arrives is left out by passing
+ * check[j] = NULL in the final plan.
+ * A NON-FINAL MERGE LAUNCH IS NOT IDEMPOTENT, for check rows as for wanted rows: a second launch
+ * adds the terms again. A FINAL LAUNCH WITHOUT WANTED ROWS IS IDEMPOTENT: it writes no shard byte
+ * (the status word it may set stays set until it is read).
+ * An ordinary plan, as a decode-idx plan, with these differences:
+ *   rs_plan_launch  a non-final plan dispatches the decode-idx kernels (a check row is an
+ *                   ordinary row there), a final plan the check kernels; one launch per group of
+ *                   16 rows of the wanted and compared indices in ascending order;
+ *   rs_plan_bytes   a decode-idx plan's count for the delivered (compared ones included) and
+ *                   wanted shards, plus per check row 2 sizes[b] in a non-final merge, sizes[b] in
+ *                   a non-final store or a final merge, and nothing under FINAL|STORE;
+ *   rs_plan_forms   a final plan reports RS_ORDER_DECODE_CHECK + RS_ORDER_CONSECUTIVE, a
+ *                   non-final one RS_ORDER_DECODE_IDX + RS_ORDER_CONSECUTIVE;
+ *   rs_plan_status  reports what the final launches since the last read flagged.
+ * Errors, in rs_plan_create_decode_idx's order: the profile; a NULL sizes, expect, input, dst,
+ * check or out, batch < 1, or an unknown flag bit (RS_E_ARG); the expect count; a misplaced
+ * pointer -- an input at an index that is neither expected nor compared, a dst or a check at an
+ * expected index, a check and a dst at one index (RS_E_ARG); sizes[b] == 0 on a stripe in the
+ * launch (RS_E_NO_DATA). Each check runs over the whole batch before the next. Nothing is created
+ * on an error. */
+#define RS_DECODE_CHECK_FINAL 2u
+#define RS_ORDER_DECODE_CHECK 65536
+int rs_plan_create_decode_check(rs_ctx* ctx, int device, int k, int m, int batch,
+                                const size_t* sizes, const uint8_t* expect,
+                                const uint8_t* const* input, uint8_t* const* dst,
+                                uint8_t* const* check, unsigned flags, rs_plan** out);
 
 /* ---- locate plans: which shard is corrupt --------------------------
  * Not in the reference API. Every other plan tells that a stripe's compared shards mismatch; a

@@ -516,6 +516,18 @@ shift
 timeout -k 10 400 python3 -u tools/decode_idx_bench.py "$@" | tee $O/decode_idx_bench.jsonl || exit $?
 }
 
+# The final decode-check launch of the last survivor against the decode-idx merge launch followed
+# by a compare-only ragged plan (tools/decode_check_bench.py): RS(10,4) and
+# RS(10,6), 256 stripes of 1 MiB, planar. One JSON line per shape on stdout and in
+# <out dir>/decode_check_bench.jsonl (the lines kept in profiles/r21/decode_check/).
+# Usage: bash tools/jobs.sh decode_check_bench <out dir> [decode_check_bench.py args]
+job_decode_check_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+O=${1:-decode_check_out}; mkdir -p "$O" || exit $?
+shift
+timeout -k 10 400 python3 -u tools/decode_check_bench.py "$@" | tee $O/decode_check_bench.jsonl || exit $?
+}
+
 # Locate plans against the compare-only plan of the same batch and against batched SHA-256 of
 # every shard (tools/locate_bench.py): RS(10,4) x 256 stripes of 64 KiB..4 MiB
 # and RS(16,4) x 4,096 stripes of 1..16 KiB, clean and with one shard of every stripe wholly
