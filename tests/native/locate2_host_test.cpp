@@ -14,6 +14,12 @@
 //    and under seeded masks that leave r' >= 4: seeded pairs, pairs with shard 0 among them,
 //    are blamed on exactly the pair; seeded columns with 3..r'-2 errors are unexplained;
 //  - patterns with r' <= 3: the verdict is locate_classify's on seeded 1- and 2-error columns;
+//  - wide profiles, where positions and points need all eight bits of the tables' bytes:
+//    RS(129,9) and RS(240,16) with everything present (256 examined shards: position 255 has its
+//    own encoding in the point table) and RS(240,16) with two data shards missing, sampled: every
+//    examined position as the single corrupt shard with a handful of values, every pair drawn
+//    from the positions {0, 1, 127, 128, k-1, k, 254, 255} with a few value pairs, seeded pairs
+//    and seeded 3..r'-2 errors;
 // all in every packing width the kernel instances use.
 #include <algorithm>
 #include <cstdio>
@@ -300,6 +306,50 @@ void profile(int k, int m, bool short_rows, std::mt19937& rng) {
   }
 }
 
+long g_wide_singles = 0, g_wide_pairs = 0;
+
+// A wide profile, where positions and points need all eight bits of the tables' bytes: stripe 0
+// with everything present and, when `lost` names shards, stripe 1 without them. Sampled: every
+// examined position as the single corrupt shard with a handful of error values, and every pair
+// of the positions {0, 1, 127, 128, k-1, k, 254, 255} that the pattern has, with a few value
+// pairs.
+void wide_profile(int k, int m, const std::vector<int>& lost, std::mt19937& rng) {
+  const int n = k + m, batch = lost.empty() ? 1 : 2;
+  std::vector<uint8_t> pres(static_cast<size_t>(batch) * n, 1);
+  for (int i : lost) pres[static_cast<size_t>(n + i)] = 0;
+  const std::vector<size_t> sizes(static_cast<size_t>(batch), 8211);
+  LocateTables t, t1;
+  CHECK(build_locate_tables(k, m, batch, sizes.data(), pres.data(), t, 2) == TableError::kOk);
+  CHECK(build_locate_tables(k, m, batch, sizes.data(), pres.data(), t1, 1) == TableError::kOk);
+  CHECK(t.ragged.mixed.patterns.size() == static_cast<size_t>(batch));
+  static const uint8_t kValues[] = {1, 2, 0x53, 0x80, 0xFE, 0xFF};
+  static const uint8_t kValuePairs[][2] = {{1, 1}, {1, 0xFF}, {0xFF, 1}, {0xFF, 0xFF}, {0x53, 0x80}, {2, 0xFE}};
+  for (size_t p = 0; p < t.ragged.mixed.patterns.size(); ++p) {
+    const Pattern P = make_pattern(k, m, t, p);
+    const int nT = static_cast<int>(P.T.size());
+    CHECK(P.rows >= 4 && nT == k + P.rows);
+    check_tables(k, t, t1, p, P, rng);
+    uint8_t s[16];
+    for (int j = 0; j < nT; ++j)
+      for (uint8_t e : kValues) {
+        syndromes(P, &j, &e, 1, s);
+        CHECK(classify1_all(s, P.rows, P.k, P.gf, P.blk) == static_cast<uint32_t>(P.T[static_cast<size_t>(j)]));
+        CHECK(classify2_all(s, P.rows, P.k, P.gf, P.blk) == static_cast<uint32_t>(P.T[static_cast<size_t>(j)]));
+        ++g_wide_singles;
+      }
+    const int cand[] = {0, 1, 127, 128, k - 1, k, 254, 255};
+    std::vector<int> at;
+    for (int c : cand)
+      if (c < nT && std::find(at.begin(), at.end(), c) == at.end()) at.push_back(c);
+    const long before = g_pairs;
+    for (size_t a = 0; a < at.size(); ++a)
+      for (size_t b = a + 1; b < at.size(); ++b)
+        for (const auto& e : kValuePairs) check_pair(P, at[a], at[b], e[0], e[1]);
+    g_wide_pairs += g_pairs - before;
+    check_seeded(P, rng);
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -353,6 +403,13 @@ int main() {
   const int shorts[][2] = {{10, 4}, {6, 3}, {4, 2}, {10, 8}};
   for (const auto& pr : shorts) profile(pr[0], pr[1], true, rng);
   CHECK(g_short > 0 && g_multis > 0);
+  // positions, points and shard indices at and past 128; RS(240,16) with everything present
+  // examines 256 shards, and position 255 has its own byte in the point table
+  wide_profile(129, 9, {}, rng);
+  wide_profile(240, 16, {1, 128}, rng);
+  CHECK(g_wide_singles == 6L * (138 + 256 + 254));
+  CHECK(g_wide_pairs == 6L * (10 + 28 + 15));  // 5, 8 and 6 distinct positions of the eight exist
+  std::printf("wide singles %ld wide pairs %ld\n", g_wide_singles, g_wide_pairs);
   std::printf("singles %ld pairs %ld multis %ld short %ld\nlocate2_host_test ok\n", g_singles, g_pairs,
               g_multis, g_short);
   return 0;

@@ -9,7 +9,13 @@
 //    with 2..r'-1 errors are unexplained, r' = 1 is unexplained, no error is clean -- in every
 //    packing width the kernel instances use;
 //  - the tile map holds only the stripes with a row, a batch without one has no launch group,
-//    and RS(10,20) with everything present uses 16 rows in one group.
+//    and RS(10,20) with everything present uses 16 rows in one group;
+//  - wide profiles, where positions and shard indices need all eight bits of the tables' bytes:
+//    RS(129,9) and RS(240,16) with everything present (the latter examines exactly 256 shards)
+//    and RS(240,16) with two data shards missing. Sampled: every examined position as the single
+//    corrupt shard with a handful of error values, 1 and 0xFF among them, through locate_classify
+//    and locate_correct (which must also return the position and the error value).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -47,6 +53,8 @@ uint8_t ginv(uint8_t a) {
   return 0;
 }
 
+uint8_t g_mul[256][256];  // gmul, tabulated once
+
 // The syndromes of one column, from the definition: stored cmp ^ G . valid.
 std::vector<uint8_t> syndromes(const std::vector<uint8_t>& col, const std::vector<int>& valid,
                                const std::vector<int>& cmp, const Mat& G, int rows) {
@@ -54,7 +62,7 @@ std::vector<uint8_t> syndromes(const std::vector<uint8_t>& col, const std::vecto
   for (int x = 0; x < rows; ++x) {
     uint8_t v = col[static_cast<size_t>(cmp[static_cast<size_t>(x)])];
     for (size_t j = 0; j < valid.size(); ++j)
-      v ^= gmul(G.at(x, static_cast<int>(j)), col[static_cast<size_t>(valid[j])]);
+      v ^= g_mul[G.at(x, static_cast<int>(j))][col[static_cast<size_t>(valid[j])]];
     s[static_cast<size_t>(x)] = v;
   }
   return s;
@@ -76,9 +84,35 @@ uint32_t classify_all(const std::vector<uint8_t>& s, int rows, int k, const uint
   return v;
 }
 
-long g_singles = 0, g_multis = 0;
+// locate_correct in the width NW: locate_classify's verdict for rows >= 3 (unexplained for
+// every mismatch below), and for a shard verdict the position in valid then cmp and the value.
+template <int NW>
+void correct_one(const std::vector<uint8_t>& s, int rows, int k, const uint8_t* gf, const uint8_t* pt,
+                 uint32_t verdict, uint32_t want_pos, uint32_t want_value) {
+  uint32_t w[NW] = {0};
+  for (int x = 0; x < NW * 4; ++x)
+    w[x >> 2] |= static_cast<uint32_t>(x < rows ? s[static_cast<size_t>(x)] : 0xA5u) << (8 * (x & 3));
+  uint32_t pos = 0xdeadu, value = 0xdeadu;
+  const uint32_t v = locate_correct(w, rows, k, gf, pt, pos, value);
+  if (rows < 3) {
+    CHECK(v == (verdict == kLocateClean ? kLocateClean : kLocateUnexplained));
+    return;
+  }
+  CHECK(v == verdict);
+  if (v < 256u) CHECK(pos == want_pos && value == want_value);
+}
 
-void check_pattern(int k, int m, const LocateTables& t, size_t p, std::mt19937& rng) {
+void correct_all(const std::vector<uint8_t>& s, int rows, int k, const uint8_t* gf, const uint8_t* pt,
+                 uint32_t verdict, uint32_t want_pos, uint32_t want_value) {
+  correct_one<4>(s, rows, k, gf, pt, verdict, want_pos, want_value);
+  if (rows <= 8) correct_one<2>(s, rows, k, gf, pt, verdict, want_pos, want_value);
+  if (rows <= 4) correct_one<1>(s, rows, k, gf, pt, verdict, want_pos, want_value);
+}
+
+long g_singles = 0, g_multis = 0, g_wide_singles = 0;
+
+// sampled: a handful of error values per position instead of all 255, and locate_correct too
+void check_pattern(int k, int m, const LocateTables& t, size_t p, std::mt19937& rng, bool sampled = false) {
   const int n = k + m;
   const MixedPattern& pt = t.ragged.mixed.patterns[p];
   const uint8_t* blk = &t.loc[p * t.stride];
@@ -123,14 +157,23 @@ void check_pattern(int k, int m, const LocateTables& t, size_t p, std::mt19937& 
   // G . valid = cmp: a clean column is clean
   CHECK(classify_all(syndromes(col, dp.valid, cmp, dp.rows, rows), rows, k, gf, blk) == kLocateClean);
   // every single error
-  for (int shard : examined)
-    for (int e = 1; e < 256; ++e) {
+  static const int kSampled[] = {1, 2, 0x53, 0x80, 0xFE, 0xFF};
+  for (size_t at = 0; at < examined.size(); ++at) {
+    const int shard = examined[at];
+    for (int q = 1; q < (sampled ? 1 + static_cast<int>(sizeof kSampled / sizeof kSampled[0]) : 256); ++q) {
+      const int e = sampled ? kSampled[q - 1] : q;
       std::vector<uint8_t> bad(col);
       bad[static_cast<size_t>(shard)] ^= static_cast<uint8_t>(e);
-      const uint32_t v = classify_all(syndromes(bad, dp.valid, cmp, dp.rows, rows), rows, k, gf, blk);
+      const std::vector<uint8_t> s = syndromes(bad, dp.valid, cmp, dp.rows, rows);
+      const uint32_t v = classify_all(s, rows, k, gf, blk);
       CHECK(v == (rows < 2 ? kLocateUnexplained : static_cast<uint32_t>(shard)));
       ++g_singles;
+      if (sampled) {
+        correct_all(s, rows, k, gf, blk, v, static_cast<uint32_t>(at), static_cast<uint32_t>(e));
+        ++g_wide_singles;
+      }
     }
+  }
   // junk in shards that are not examined changes nothing
   {
     std::vector<uint8_t> bad(col);
@@ -201,9 +244,28 @@ void profile(int k, int m, std::mt19937& rng) {
   for (size_t p = 0; p < mt.patterns.size(); ++p) check_pattern(k, m, t, p, rng);
 }
 
+// A wide profile: stripe 0 with everything present and, when `lost` names shards, stripe 1
+// without them. Every pattern's tables and the sampled rule.
+void wide_profile(int k, int m, const std::vector<int>& lost, int want_rows_lost, std::mt19937& rng) {
+  const int n = k + m, batch = lost.empty() ? 1 : 2;
+  std::vector<uint8_t> pres(static_cast<size_t>(batch) * n, 1);
+  for (int i : lost) pres[static_cast<size_t>(n + i)] = 0;
+  const std::vector<size_t> sizes(static_cast<size_t>(batch), 8211);
+  LocateTables t;
+  CHECK(build_locate_tables(k, m, batch, sizes.data(), pres.data(), t) == TableError::kOk);
+  const MixedTables& mt = t.ragged.mixed;
+  CHECK(mt.groups.size() == 1 && mt.patterns.size() == static_cast<size_t>(batch));
+  CHECK(t.stride == locate_stride(k) && t.loc.size() == t.stride * mt.patterns.size());
+  CHECK(static_cast<int>(t.rows(mt.pat[0])) == std::min(m, kLocateRows));
+  if (batch > 1) CHECK(static_cast<int>(t.rows(mt.pat[1])) == want_rows_lost);
+  for (size_t p = 0; p < mt.patterns.size(); ++p) check_pattern(k, m, t, p, rng, true);
+}
+
 }  // namespace
 
 int main() {
+  for (int a = 0; a < 256; ++a)
+    for (int b = 0; b < 256; ++b) g_mul[a][b] = gmul(static_cast<uint8_t>(a), static_cast<uint8_t>(b));
   std::mt19937 rng(20261020);
   const int profiles[][2] = {{10, 4}, {4, 2}, {3, 2}, {6, 3}, {1, 3}, {20, 12}};
   for (const auto& pr : profiles) profile(pr[0], pr[1], rng);
@@ -239,6 +301,11 @@ int main() {
     pres[0] = pres[1] = pres[2] = 0;
     CHECK(build_locate_tables(k, m, 1, &one, pres.data(), t) == TableError::kTooFewShards);
   }
-  std::printf("singles %ld multis %ld\nlocate_host_test ok\n", g_singles, g_multis);
+  // positions and shard indices at and past 128, and the 256 examined shards of RS(240,16)
+  wide_profile(129, 9, {}, 0, rng);
+  wide_profile(240, 16, {1, 128}, 14, rng);
+  CHECK(g_wide_singles == 6L * (138 + 256 + 254));
+  std::printf("singles %ld multis %ld wide singles %ld\nlocate_host_test ok\n", g_singles, g_multis,
+              g_wide_singles);
   return 0;
 }
