@@ -48,6 +48,7 @@ RS_E_NOMEM = -12
 RS_DECODE_IDX_STORE = 1  # rs_plan_create_decode_idx / rs_decode_idx flags
 RS_DECODE_CHECK_FINAL = 2  # rs_plan_create_decode_check: test the check rows, write none
 RS_ORDER_DECODE_CHECK = 65536  # rs_plan_forms of a final decode-check plan (+ consecutive)
+RS_ORDER_DECODE_REPAIR = 131072  # rs_plan_forms of a decode-repair plan (+ consecutive)
 
 _vp = ctypes.c_void_p
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -166,11 +167,20 @@ SIGNATURES = {
     "rs_plan_create_decode_check": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
                                            ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                            ctypes.c_uint, ctypes.POINTER(_vp)]),
+    "rs_plan_create_decode_repair": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
+                                            ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                            ctypes.POINTER(_vp), ctypes.c_uint, ctypes.POINTER(_vp)]),
     "rs_decode_check": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u8p,
                                ctypes.POINTER(_vp), ctypes.c_uint]),
     "rs_decode_check_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_sz), ctypes.POINTER(_vp),
                                      ctypes.POINTER(_vp), _u8p, ctypes.POINTER(_vp), ctypes.c_uint,
                                      ctypes.POINTER(_int)]),
+    "rs_decode_repair": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                ctypes.POINTER(_vp), _u8p, ctypes.POINTER(_vp), ctypes.c_uint,
+                                ctypes.POINTER(ctypes.c_uint64)]),
+    "rs_decode_repair_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_sz), ctypes.POINTER(_vp),
+                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u8p, ctypes.POINTER(_vp),
+                                      ctypes.c_uint, ctypes.POINTER(_int), ctypes.POINTER(ctypes.c_uint64)]),
     "rs_decode_idx": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), _u8p, ctypes.POINTER(_vp),
                              ctypes.c_uint]),
     "rs_decode_idx_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_sz), ctypes.POINTER(_vp), _u8p,

@@ -84,6 +84,12 @@ constexpr int kOrderDecodeCheck = 65536;
 static_assert(!decode_order(kOrderDecodeCheck).valid() && encode(decode_order(kOrderDecodeCheck)) == -1,
               "a plan form code names no launch order");
 
+// (kOrderDecodeRepair + consecutive: rs_plan_forms of a decode-repair plan; a
+// plan form code in the same way.)
+constexpr int kOrderDecodeRepair = 131072;
+static_assert(!decode_order(kOrderDecodeRepair).valid() && encode(decode_order(kOrderDecodeRepair)) == -1,
+              "a plan form code names no launch order");
+
 static_assert(encode(Form{Family::kRealign, 0}) == kOrderRealign && encode(Form{Family::kWix, 0}) == kOrderWix &&
                   encode(Form{Family::kTri, 0}) == kOrderTri &&
                   encode(Form{Family::kRealignTri, 0}) == kOrderRealignTri &&

@@ -20,6 +20,7 @@
 #include "host_ragged.hpp"
 #include "host_uniform.hpp"
 #include "host_decode_idx.hpp"
+#include "host_decode_repair.hpp"
 #include "host_update.hpp"
 #include "overwrite_plan.hpp"
 
@@ -805,6 +806,80 @@ int rs_decode_check(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* dst, ui
                     const uint8_t* expect, const uint8_t* const* input, unsigned flags) {
   int status = RS_OK;
   const int rc = rs_decode_check_batch(ctx, k, m, 1, &S, dst, check, expect, input, flags, &status);
+  return rc ? rc : status;
+}
+
+// The final rs_decode_check_batch call that repairs what it flags. status[b]:
+// the stripe's own refusal in the plan constructor's order -- the expect count, a misplaced
+// pointer (a fix at an index that is neither expected nor compared among them), more than 16
+// rows (RS_E_UNSUPPORTED), a zero size in the launch -- while the other stripes run; RS_OK for a
+// clean stripe and for one whose mismatching columns were all explained (counts say what was
+// repaired); RS_E_CORRUPT when a column is unexplained, the wanted rows delivered all the same.
+int rs_decode_repair_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes, uint8_t* const* dst,
+                           uint8_t* const* check, uint8_t* const* fix, const uint8_t* expect,
+                           const uint8_t* const* input, unsigned flags, int* status, uint64_t* counts) {
+  DeviceGuard dg;
+  int rc = check_profile(k, m);
+  if (rc) return rc;
+  if (!ctx || batch < 0 || (batch && (!sizes || !dst || !check || !fix || !expect || !input || !status)) ||
+      (flags & ~RS_DECODE_IDX_STORE))
+    return RS_E_ARG;
+  const size_t B = static_cast<size_t>(batch), n = static_cast<size_t>(k + m);
+  std::vector<uint8_t> fl(B * n, 0);
+  std::vector<int> ids;
+  for (size_t b = 0; b < B; ++b) {
+    int ne = 0, rows = 0;
+    bool in = false, chk = false, misplaced = false;
+    for (size_t i = 0; i < n; ++i) {
+      const size_t at = b * n + i;
+      const bool e = expect[at] != 0;
+      ne += e;
+      in |= input[at] != nullptr;
+      rows += dst[at] != nullptr || check[at] != nullptr;
+      chk |= check[at] != nullptr;
+      misplaced |= e ? dst[at] != nullptr || check[at] != nullptr
+                     : (input[at] != nullptr && !check[at]) || (check[at] != nullptr && dst[at] != nullptr) ||
+                           (fix[at] != nullptr && !check[at]);
+      fl[at] = static_cast<uint8_t>((e ? 1 : 0) | (input[at] ? 2 : 0) | (dst[at] ? 4 : 0) | (check[at] ? 8 : 0) |
+                                    (fix[at] ? 16 : 0));
+    }
+    if (ne < k) status[b] = RS_E_TOO_FEW_SHARDS;
+    else if (ne > k || misplaced) status[b] = RS_E_ARG;
+    else if (rows > kRepairRows) status[b] = RS_E_UNSUPPORTED;
+    else if (!((in && rows) || chk)) status[b] = RS_OK;
+    else if (sizes[b] == 0) status[b] = RS_E_NO_DATA;
+    else {
+      status[b] = RS_OK;
+      ids.push_back(static_cast<int>(b));
+    }
+  }
+  std::vector<uint64_t> own;
+  if (!counts) {
+    own.assign(B * (n + 1), 0);
+    counts = own.data();
+  } else {
+    std::fill(counts, counts + B * (n + 1), 0);
+  }
+  std::vector<int> corrupt(B, 0);
+  if ((rc = run_decode_repair(
+           ctx, k, m, (flags & RS_DECODE_IDX_STORE) != 0, ids, sizes, fl.data(),
+           [&](int b, int i) { return input[static_cast<size_t>(b) * n + i]; },
+           [&](int b, int i) {
+             const size_t at = static_cast<size_t>(b) * n + i;
+             return check[at] ? check[at] : dst[at];
+           },
+           [&](int b, int i) { return fix[static_cast<size_t>(b) * n + i]; }, counts, corrupt.data())))
+    return rc;
+  for (int b : ids)
+    if (counts[static_cast<size_t>(b) * (n + 1) + n]) status[b] = RS_E_CORRUPT;
+  return first_error(status, batch);
+}
+
+int rs_decode_repair(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* dst, uint8_t* const* check,
+                     uint8_t* const* fix, const uint8_t* expect, const uint8_t* const* input, unsigned flags,
+                     uint64_t* counts) {
+  int status = RS_OK;
+  const int rc = rs_decode_repair_batch(ctx, k, m, 1, &S, dst, check, fix, expect, input, flags, &status, counts);
   return rc ? rc : status;
 }
 

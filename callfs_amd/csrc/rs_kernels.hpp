@@ -335,6 +335,37 @@ struct CheckArgs {
 hipError_t launch_decode_check(ApplyArgs a, const CheckArgs& x, bool store, bool any_tail,
                                hipStream_t stream, LaunchEvents ev = {});
 
+// ---- decode-repair launches (rs_repair.hpp in rs_mixed.hip) --------------
+// A final decode-check launch group that repairs what its check rows explain. Every pattern's
+// check rows are its rows [0, nchk[p]) (c.cmask[p] is the low nchk[p] bits) and every stripe has
+// at most 16 rows. A byte column's check values are its syndromes: locate_correct
+// (locate_tables.hpp) over them names an expected shard at position j with error e -- every
+// wanted row r, stored as computed, then gets G[r][j] . e XORed in where it lies, by the lane
+// that stored it -- or a compared shard x with
+// error s_x, or leaves the column unexplained (always, with fewer than 3 check rows). The error
+// value is XORed into the byte of fix[s * (k + 16) + position] when that pointer is non-null,
+// columns are added per verdict into counts[s * nbins + shard] (unexplained: bin nbins - 1) and
+// a stripe with a mismatching column has 1 ORed into its status word, repaired or not. Check
+// rows are never written.
+struct RepairArgs {
+  CheckArgs c;
+  const uint8_t* gf;    // log[256], exp[512]
+  const uint8_t* loc;   // [P] pattern blocks of loc_stride bytes (decode_repair_tables.hpp)
+  uint64_t* counts;     // [batch][nbins]
+  uint8_t* const* fix;  // [batch][k + 16] by position: expected V[j], then compared x; null allowed
+  uint32_t loc_stride;  // locate_stride(k)
+  uint32_t nbins;       // k + m + 1
+  int k;                // the code's k: positions below it are expected shards
+};
+
+// (kOrderDecodeRepair of order_code.hpp + consecutive: rs_plan_forms of a decode-repair plan.)
+// Enqueues the launch group: rs_repair_ragged (store: its STORE instances) over every mapped
+// stripe's [0, size); arguments, tails, misaligned shards, order and slicing as
+// launch_decode_check. Counts accumulate from launch to launch. A merge launch with a wanted row
+// is NOT idempotent, nor is a launch with a fix row; every other launch is.
+hipError_t launch_decode_repair(ApplyArgs a, const RepairArgs& x, bool store, bool any_tail,
+                                hipStream_t stream, LaunchEvents ev = {});
+
 // ---- locate launches (rs_mixed.hip) --------------------------------------
 // A required launch group in which every row is compared and none written, and a mismatching
 // byte column is classified instead of only flagged: locate_classify (locate_tables.hpp) turns

@@ -13,6 +13,8 @@
 // columns into per-stripe, per-shard counts; the pair instances (§5.12.1) classify with
 // locate_classify2 and add a column blamed on two shards into both shards' counts. Correct
 // launches (§5.13) are locate launches that XOR the error value into the blamed shard's byte.
+// Decode-repair launches (§5.16, rs_repair.hpp) are final decode-check launches that classify a
+// mismatching column from their check rows and repair the wanted rows before storing them.
 #include <algorithm>
 #include <array>
 
@@ -125,6 +127,15 @@ __device__ __forceinline__ void locate_wave_add(uint64_t* bins, uint32_t nbins, 
     live &= ~__ballot(mine);
   }
 }
+
+}  // namespace dev
+}  // namespace callfs
+
+// decode-repair launches: built on the locate helpers above
+#include "rs_repair.hpp"
+
+namespace callfs {
+namespace dev {
 
 // The S % 16 tail of a locate launch: lds_tail with every row compared, and a mismatching
 // byte classified and counted. Every thread of the waves that call it reaches the ballots.
@@ -607,10 +618,18 @@ const std::array<std::array<CheckFn, 3>, 2> kCheck = {{
     {kCheckInstance<4, false>, kCheckInstance<8, false>, kCheckInstance<16, false>},
     {kCheckInstance<4, true>, kCheckInstance<8, true>, kCheckInstance<16, true>}}};
 
+// Decode-repair launches (rs_repair.hpp): [store][0: R <= 4, 1: R 5..8, 2: R 9..16]
+using RepairFn = void (*)(ApplyArgs, RepairArgs);
+template <int RT, bool STORE>
+constexpr RepairFn kRepairInstance = &dev::rs_repair_ragged<RT, dev::UpdatePolicyFor<RT, false>, STORE>;
+const std::array<std::array<RepairFn, 3>, 2> kRepair = {{
+    {kRepairInstance<4, false>, kRepairInstance<8, false>, kRepairInstance<16, false>},
+    {kRepairInstance<4, true>, kRepairInstance<8, true>, kRepairInstance<16, true>}}};
+
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
 // per-device attribute (dispatch.hpp DeviceOnce), keyed by the 16-row instance it is set on
 enum class WideLds { kMixed, kRagged, kRaggedSome, kUpdate, kUpdatePair, kLocate, kLocate2, kCorrect,
-                     kMerge, kMergeStore, kCheck, kCheckStore };
+                     kMerge, kMergeStore, kCheck, kCheckStore, kRepair, kRepairStore };
 DeviceOnce g_mixed_wide_lds;
 
 // The vector launch every kind shares: the dynamic-LDS opt-in, then `grid` tiles in equal
@@ -759,6 +778,25 @@ hipError_t launch_decode_check(ApplyArgs a, const CheckArgs& x, bool store, bool
   // per tile: the sources, and every row read (merge) or written (store) at least once
   return launch_tiles(kCheck[store ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0],
                       store ? WideLds::kCheckStore : WideLds::kCheck, u.ntiles, a, x, a.K + a.R, stream, ev);
+}
+
+hipError_t launch_decode_repair(ApplyArgs a, const RepairArgs& x, bool store, bool any_tail,
+                                hipStream_t stream, LaunchEvents ev) {
+  const UpdateArgs& u = x.c.m.u;
+  // launch_decode_check's test, and what the slow path reads
+  if (a.R < 1 || a.R > kMaxRowsPerLaunch || a.K < 0 || a.K > kMaxK || a.batch < 1 || !a.ltabs || !u.pat ||
+      !u.size || !u.tile0 || !a.in_tab || !a.out_tab || u.ntiles > 0x7fffffffu || (u.ntiles != 0 && !u.tile_stripe) ||
+      !u.nsrc || !x.c.m.nrows || !x.c.cmask || !a.status || u.in_stride != static_cast<uint32_t>(a.K) || !x.gf ||
+      !x.loc || !x.counts || !x.fix || x.k < 1 || x.k > kMaxK || x.loc_stride != locate_stride(x.k) || x.nbins < 2)
+    return hipErrorInvalidValue;
+  if (u.ntiles == 0) return hipSuccess;  // no stripe has a row
+  a.t_base = 0;
+  a.S = a.nvec = 0;  // per stripe, read by the kernel
+  a.verify_mask = 0;
+  a.tail_in_vec = any_tail ? 1u : 0u;  // wave 0 of each stripe's first tile
+  // per tile: the sources, and every row read (merge) or written (store) at least once
+  return launch_tiles(kRepair[store ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0],
+                      store ? WideLds::kRepairStore : WideLds::kRepair, u.ntiles, a, x, a.K + a.R, stream, ev);
 }
 
 }  // namespace callfs

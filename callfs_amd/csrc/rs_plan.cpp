@@ -9,6 +9,7 @@
 
 #include "decode_check_tables.hpp"
 #include "decode_idx_tables.hpp"
+#include "decode_repair_tables.hpp"
 #include "locate_tables.hpp"
 #include "mixed_tables.hpp"
 #include "ragged_tables.hpp"
@@ -59,7 +60,9 @@ struct MixedPlan {
 // decode_idx_tables.hpp: single sources, and per launch group the patterns' row counts. A
 // decode-check plan (rs_plan_create_decode_check, §5.15) is a decode-idx plan from
 // decode_check_tables.hpp that also holds per launch group the patterns' check rows; a final one
-// launches the kernel that tests them.
+// launches the kernel that tests them. A decode-repair plan (rs_plan_create_decode_repair, §5.16)
+// is a final decode-check plan from decode_repair_tables.hpp plus the locate blocks, the fix
+// pointer table and the batch * (k + m + 1) counts; it launches the kernel that repairs.
 struct UpdatePlan {
   bool pair = true;  // sources are (old, new) pairs; false: EncodeIdx mode
   bool decode_idx = false, store = false;  // a decode-idx plan, and whether it stores or merges
@@ -76,6 +79,10 @@ struct UpdatePlan {
     size_t cmask_off = 0;  // a decode-check plan's [P] check-row masks (read by a final one)
   };
   std::vector<Group> groups;
+  // a decode-repair plan's pieces (check_final is set too)
+  bool repair = false;
+  int k = 0, m = 0;
+  size_t gf_off = 0, loc_off = 0, loc_stride = 0, fix_off = 0, counts_off = 0;
 };
 
 struct rs_plan {
@@ -186,7 +193,19 @@ hipError_t plan_launch(const rs_plan& plan, hipStream_t s, const std::vector<int
       x.in_stride = static_cast<uint32_t>(up.cmax) * (up.pair ? 2u : 1u);
       const MergeArgs xm{x, reinterpret_cast<const uint32_t*>(d + g.nrows_off)};
       hipError_t e;
-      if (up.check_final) {
+      if (up.repair) {
+        a.status = reinterpret_cast<int*>(d + plan.status_off);
+        a.status_stride = 1;
+        const RepairArgs xr{CheckArgs{xm, reinterpret_cast<const uint32_t*>(d + g.cmask_off)},
+                            d + up.gf_off,
+                            d + up.loc_off,
+                            reinterpret_cast<uint64_t*>(d + up.counts_off),
+                            reinterpret_cast<uint8_t* const*>(d + up.fix_off),
+                            static_cast<uint32_t>(up.loc_stride),
+                            static_cast<uint32_t>(up.k + up.m + 1),
+                            up.k};
+        e = launch_decode_repair(a, xr, up.store, up.any_tail, s, group_events(ev, gi, ng));
+      } else if (up.check_final) {
         a.status = reinterpret_cast<int*>(d + plan.status_off);
         a.status_stride = 1;
         e = launch_decode_check(a, CheckArgs{xm, reinterpret_cast<const uint32_t*>(d + g.cmask_off)}, up.store,
@@ -515,10 +534,14 @@ const std::vector<uint32_t>* group_cmask(const DecodeCheckGroup& g) { return &g.
 
 // The body of the decode-idx and decode-check constructors once the tables stand: the plan's
 // layout, its pointer tables and the upload. T: DecodeIdxTables or DecodeCheckTables; row(at):
-// the pointer of the row at entry at = b * n + i (a wanted shard, or a check accumulator).
+// the pointer of the row at entry at = b * n + i (a wanted shard, or a check accumulator). With
+// `rep` (a decode-repair plan; t is its decode-check part) also the shared log / exp block, the
+// patterns' locate blocks, the fix pointers by position (`fix`: batch * n, null allowed) and the
+// zeroed counts, each piece 256-B aligned.
 template <class T, class Row>
 int finish_decode_plan(int device, const T& t, const size_t* sizes, const uint8_t* const* input, Row row,
-                       bool store, bool check_final, uint64_t bytes, rs_plan** out) {
+                       bool store, bool check_final, uint64_t bytes, rs_plan** out,
+                       const DecodeRepairTables* rep = nullptr, uint8_t* const* fix = nullptr) {
   const int batch = t.batch, n = t.k + t.m;
   size_t smax = 0;
   for (int b = 0; b < batch; ++b)
@@ -533,7 +556,9 @@ int finish_decode_plan(int device, const T& t, const size_t* sizes, const uint8_
   up.cmax = t.cmax;
   up.ntiles = t.map.ntiles;
   up.any_tail = t.map.any_tail;
-  plan->fixed_form = RS_ORDER_CONSECUTIVE + (check_final ? kOrderDecodeCheck : kOrderDecodeIdx);
+  plan->fixed_form = RS_ORDER_CONSECUTIVE + (rep           ? kOrderDecodeRepair
+                                             : check_final ? kOrderDecodeCheck
+                                                           : kOrderDecodeIdx);
   plan->bytes = bytes;
   const size_t stride = static_cast<size_t>(t.cmax);
   const size_t P = t.patterns.size();
@@ -552,10 +577,35 @@ int finish_decode_plan(int device, const T& t, const size_t* sizes, const uint8_
     if (group_cmask(g)) at.cmask_off = pk.take(sizeof(uint32_t) * P);
     up.groups.push_back(at);
   }
+  if (rep) {
+    up.repair = true;
+    up.k = t.k;
+    up.m = t.m;
+    up.gf_off = pk.take(rep->gf.size());
+    up.loc_stride = rep->stride;
+    up.loc_off = pk.take(std::max<size_t>(1, rep->loc.size()));
+    up.fix_off = pk.take(sizeof(void*) * static_cast<size_t>(batch) * fix_slots(t.k));
+    up.counts_off = pk.take(sizeof(uint64_t) * static_cast<size_t>(batch) * (n + 1));
+  }
   std::vector<uint8_t> h(pk.off, 0);
   auto put = [&](size_t off, const auto& v) {
     if (!v.empty()) std::memcpy(h.data() + off, v.data(), sizeof(v[0]) * v.size());
   };
+  if (rep) {
+    put(up.gf_off, rep->gf);
+    put(up.loc_off, rep->loc);
+    // fix pointers of stripe b by position: its expected shards, then its compared shards
+    auto* f = reinterpret_cast<uint8_t**>(h.data() + up.fix_off);
+    for (int b = 0; b < batch; ++b) {
+      if (!t.has[static_cast<size_t>(b)]) continue;
+      const uint32_t p = t.pat[static_cast<size_t>(b)];
+      const auto& pt = t.patterns[p];
+      uint8_t** fb = f + static_cast<size_t>(b) * fix_slots(t.k);
+      for (int j = 0; j < t.k; ++j) fb[j] = fix[static_cast<size_t>(b) * n + pt.expect[static_cast<size_t>(j)]];
+      for (uint32_t x = 0; x < rep->nchk[p]; ++x)
+        fb[t.k + x] = fix[static_cast<size_t>(b) * n + pattern_rows(pt)[x]];
+    }
+  }
   // sources of stripe b: its pattern's delivered shards in ascending order; slots past its
   // source count, and every slot of a stripe in no launch, stay null and unread
   auto* in = reinterpret_cast<const uint8_t**>(h.data() + up.in_off);
@@ -829,6 +879,39 @@ int rs_plan_create_decode_check(rs_ctx* ctx, int device, int k, int m, int batch
                             store, final, t.bytes[(final ? 2 : 0) + (store ? 1 : 0)], out);
 }
 
+int rs_plan_create_decode_repair(rs_ctx* ctx, int device, int k, int m, int batch, const size_t* sizes,
+                                 const uint8_t* expect, const uint8_t* const* input, uint8_t* const* dst,
+                                 uint8_t* const* check, uint8_t* const* fix, unsigned flags, rs_plan** out) {
+  DeviceGuard dg;
+  int rc = check_plan_args(ctx, k, m, batch,
+                           sizes && expect && input && dst && check && fix && !(flags & ~RS_DECODE_IDX_STORE), out);
+  if (rc) return rc;
+  const size_t cells = static_cast<size_t>(batch) * (k + m);
+  std::vector<uint8_t> have_in(cells), have_dst(cells), have_chk(cells), have_fix(cells);
+  for (size_t i = 0; i < cells; ++i) {
+    have_in[i] = input[i] != nullptr;
+    have_dst[i] = dst[i] != nullptr;
+    have_chk[i] = check[i] != nullptr;
+    have_fix[i] = fix[i] != nullptr;
+  }
+  DecodeRepairTables t;
+  switch (build_decode_repair_tables(k, m, batch, sizes, expect, have_in.data(), have_dst.data(), have_chk.data(),
+                                     have_fix.data(), t)) {
+    case DecodeRepairError::kOk: break;
+    case DecodeRepairError::kArg: return RS_E_ARG;
+    case DecodeRepairError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
+    case DecodeRepairError::kUnsupported: return RS_E_UNSUPPORTED;
+    case DecodeRepairError::kNoData: return RS_E_NO_DATA;
+    case DecodeRepairError::kTooManyTiles: return RS_E_ARG;  // a grid past 2^31 - 1 tiles
+    case DecodeRepairError::kSingular: return RS_E_SINGULAR;
+  }
+  if (!ctx->device(device)) return RS_E_ARG;
+  const bool store = (flags & RS_DECODE_IDX_STORE) != 0;
+  // the final decode-check figure: the few repaired bytes are not counted
+  return finish_decode_plan(device, t.c, sizes, input, [&](size_t at) { return check[at] ? check[at] : dst[at]; },
+                            store, true, t.c.bytes[2 + (store ? 1 : 0)], out, &t, fix);
+}
+
 void rs_plan_destroy(rs_plan* plan) {
   DeviceGuard dg;
   delete plan;
@@ -1046,17 +1129,21 @@ int rs_plan_status(rs_plan* plan, void* stream, int* corrupt) {
   return RS_OK;
 }
 
-// The counts a locate plan's launches have added since the last read, then cleared (as
+// The counts a locate or decode-repair plan's launches have added since the last read, then cleared (as
 // rs_plan_stripe_status does with the flags): a plan launched twice before a read reports
 // every count doubled.
 int rs_plan_blame(rs_plan* plan, void* stream, uint64_t* counts) {
   DeviceGuard dg;
-  if (!plan || !counts || !plan->mixed || plan->mixed->kind != PlanKind::kLocate) return RS_E_ARG;
+  if (!plan || !counts) return RS_E_ARG;
+  const bool locate = plan->mixed && plan->mixed->kind == PlanKind::kLocate;
+  const bool repair = plan->update && plan->update->repair;
+  if (!locate && !repair) return RS_E_ARG;
   HIPCHK(hipSetDevice(plan->device));
   auto s = static_cast<hipStream_t>(stream);
-  const MixedPlan& mp = *plan->mixed;
-  auto* c = static_cast<uint8_t*>(plan->dmeta.p) + mp.counts_off;
-  const size_t bytes = sizeof(uint64_t) * static_cast<size_t>(plan->batch) * (mp.t.k + mp.t.m + 1);
+  const size_t off = locate ? plan->mixed->counts_off : plan->update->counts_off;
+  const int n = locate ? plan->mixed->t.k + plan->mixed->t.m : plan->update->k + plan->update->m;
+  auto* c = static_cast<uint8_t*>(plan->dmeta.p) + off;
+  const size_t bytes = sizeof(uint64_t) * static_cast<size_t>(plan->batch) * (n + 1);
   HIPCHK(hipMemcpyAsync(counts, c, bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemsetAsync(c, 0, bytes, s));
   HIPCHK(hipStreamSynchronize(s));

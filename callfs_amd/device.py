@@ -491,6 +491,45 @@ class Plan:
         self.handle = h
         return self
 
+    @classmethod
+    def decode_repair(cls, k: int, m: int, sizes: Sequence[int], expect, input_ptrs, dst_ptrs, check_ptrs,
+                      fix_ptrs=None, store: bool = False, device: int = 0,
+                      context: Optional[N.Context] = None) -> "Plan":
+        """rs_plan_create_decode_repair: a final decode_check plan whose launch
+        names the corrupt shard of a mismatching byte column from the finished check rows, repairs
+        the wanted rows within the launch and XORs the error values into the fix buffers.
+        fix_ptrs: batch*(k+m) device pointers (None: none), nonzero at expected or compared
+        indices only; a zeroed buffer ends as the shard's error row, the shard as delivered ends
+        restored (fix may be the input itself). Needs three check rows for a verdict; a stripe has
+        at most 16 rows. blame() reads and clears the per-shard column counts, corrupt_stripes()
+        the stripes that had a mismatch, repaired or not. A merge launch with wanted rows is NOT
+        idempotent."""
+        batch = len(sizes)
+        n = k + m
+        rows = _mask_rows(expect)
+        if rows is None or len(rows) != batch or any(len(r) != n for r in rows):
+            raise ValueError("expect: batch rows of k+m flags")
+        if fix_ptrs is None:
+            fix_ptrs = [0] * (batch * n)
+        if any(len(p) != batch * n for p in (input_ptrs, dst_ptrs, check_ptrs, fix_ptrs)):
+            raise ValueError("need batch*(k+m) input, dst, check and fix pointers each")
+        self = cls.__new__(cls)
+        self.ctx = context or N.default_context()
+        self.k, self.m, self.S, self.batch, self.device = k, m, None, batch, device
+        self.sizes = [int(s) for s in sizes]
+        self.handle = None
+        flags = (ctypes.c_uint8 * max(1, batch * n))(*[1 if f else 0 for r in rows for f in r])
+        szs = (ctypes.c_size_t * max(1, batch))(*self.sizes)
+        arr = lambda p: (ctypes.c_void_p * max(1, len(p)))(*[int(x) or None for x in p])  # noqa: E731
+        h = ctypes.c_void_p()
+        N.check(N.lib.rs_plan_create_decode_repair(self.ctx.handle, device, k, m, batch, szs, flags,
+                                                   arr(input_ptrs), arr(dst_ptrs), arr(check_ptrs),
+                                                   arr(fix_ptrs), N.RS_DECODE_IDX_STORE if store else 0,
+                                                   ctypes.byref(h)),
+                "rs_plan_create_decode_repair")
+        self.handle = h
+        return self
+
     @property
     def bytes(self) -> int:
         """Algorithmic HBM bytes one launch moves."""
@@ -546,7 +585,7 @@ class Plan:
                    258: "bs-g2", 259: "bs-q8", 260: "bs-q16", 261: "bs-x8", 262: "bs-x32",
                    512: "mixed", 1024: "ragged", 2048: "required", 4096: "update",
                    8192: "locate", 16384: "correct", 32768: "decode-idx",
-                   65536: "decode-check"}
+                   65536: "decode-check", 131072: "decode-repair"}
 
     def tune(self, reps: int = 5, stream: Optional[torch.cuda.Stream] = None) -> list:
         """rs_plan_tune: time each launch group in every tile order its kernel offers

@@ -870,6 +870,75 @@ def decode_check_batch(dst: Sequence[Sequence], check: Sequence[Sequence], expec
     return out
 
 
+def _decode_repair_rows(dst, check, fix, expect, inputs, k, m):
+    """_decode_check_rows with the fix buffers: k+m entries (None = none), writable, of the
+    stripe's shard size."""
+    S = _decode_check_rows(dst, check, expect, inputs, k, m)
+    if len(fix) != k + m:
+        raise ErrTooFewShards()
+    if any(f is not None and len(f) != S for f in fix):
+        raise ErrShardSize()
+    return S
+
+
+def decode_repair(dst: Sequence, check: Sequence, fix: Sequence, expect: Sequence[bool], inputs: Sequence,
+                  k: int, m: int, store: bool = False, context: Optional[N.Context] = None):
+    """The final decode_check call that repairs what it flags (rs_decode_repair).
+    dst, check, expect and inputs as decode_check takes them; fix (k+m entries, None = none) are
+    writable buffers at expected or compared indices into which the shard's error values are
+    XORed: a zeroed buffer ends as the error row, the shard as delivered ends restored, and
+    fix[i] may be inputs[i] itself when that is writable. Returns the k+m+1 counts: entry i the
+    byte columns blamed on shard i, the last the columns left unexplained. With three or more
+    compared shards a single corrupt shard per column is repaired in the wanted shards and
+    named; any unexplained column raises ErrShardCorrupted after the wanted shards have been
+    written, as decode_check does."""
+    ctx = context or N.default_context()
+    S = _decode_repair_rows(dst, check, fix, expect, inputs, k, m)
+    ex = (ctypes.c_uint8 * (k + m))(*[1 if e else 0 for e in expect])
+    counts = (ctypes.c_uint64 * (k + m + 1))()
+    rc = N.lib.rs_decode_repair(ctx.handle, k, m, S, _shard_ptrs(list(dst)), _shard_ptrs(list(check)),
+                                _shard_ptrs(list(fix)), ex, _shard_ptrs(list(inputs)),
+                                N.RS_DECODE_IDX_STORE if store else 0, counts)
+    if rc == N.RS_E_ARG:
+        raise ErrInvalidInput()
+    if rc == N.RS_E_INVALID_PROFILE:
+        raise ErrInvalidProfile()
+    if rc == N.RS_E_CORRUPT:
+        raise ErrShardCorrupted()
+    if rc != N.RS_OK:
+        raise _wrapped(rc, "decode_repair")
+    return list(counts)
+
+
+def decode_repair_batch(dst: Sequence[Sequence], check: Sequence[Sequence], fix: Sequence[Sequence],
+                        expect: Sequence[Sequence[bool]], inputs: Sequence[Sequence], k: int, m: int,
+                        store: bool = False, context: Optional[N.Context] = None):
+    """rs_decode_repair_batch: stripe b has dst[b], check[b], fix[b], expect[b] and inputs[b] as
+    decode_repair takes them. Returns (status, counts): status[b] is RS_OK for a clean stripe and
+    for one repaired in full, RS_E_CORRUPT where a column is unexplained, or the stripe's own
+    refusal; counts[b] its k+m+1 counts."""
+    ctx = context or N.default_context()
+    B = len(dst)
+    if len(check) != B or len(fix) != B or len(expect) != B or len(inputs) != B:
+        raise ValueError("one row of dst / check / fix / expect / input entries per stripe")
+    sizes = (ctypes.c_size_t * max(B, 1))()
+    for b in range(B):
+        sizes[b] = _decode_repair_rows(dst[b], check[b], fix[b], expect[b], inputs[b], k, m)
+
+    def ptrs(rows):
+        return _shard_ptrs([s for row in rows for s in row] or [None])
+
+    ex = (ctypes.c_uint8 * max(1, B * (k + m)))(*[1 if e else 0 for row in expect for e in row])
+    status = (ctypes.c_int * max(B, 1))()
+    counts = (ctypes.c_uint64 * max(1, B * (k + m + 1)))()
+    rc = N.lib.rs_decode_repair_batch(ctx.handle, k, m, B, sizes, ptrs(dst), ptrs(check), ptrs(fix), ex,
+                                      ptrs(inputs), N.RS_DECODE_IDX_STORE if store else 0, status, counts)
+    out = list(status)[:B]
+    if rc != N.RS_OK and rc not in out:
+        N.check(rc, "rs_decode_repair_batch")
+    return out, [list(counts[b * (k + m + 1):(b + 1) * (k + m + 1)]) for b in range(B)]
+
+
 def verify(shards: List, k: int, m: int, context: Optional[N.Context] = None) -> bool:
     """upstream enc.Verify(shards) (codec.go:59)."""
     ctx = context or N.default_context()

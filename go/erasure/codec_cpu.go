@@ -178,6 +178,30 @@ func (c *Codec) DecodeCheckBatch(dst, check [][][]byte, expectInput [][]bool, in
 	return errs
 }
 
+// DecodeRepair is the final DecodeCheck with fix buffers (DESIGN.md §5.16) on builds without the
+// GPU codec: cpuDecodeRepair, which flags and counts and never repairs.
+func (c *Codec) DecodeRepair(dst, check, fix [][]byte, expectInput []bool, input [][]byte, profile ErasureProfile) ([]uint64, error) {
+	if profile.DataShards < 1 || profile.ParityShards < 1 {
+		return nil, ErrInvalidProfile
+	}
+	return cpuDecodeRepair(dst, check, fix, expectInput, input, profile.DataShards, profile.ParityShards)
+}
+
+// DecodeRepairBatch is DecodeRepair per stripe on builds without the GPU codec.
+func (c *Codec) DecodeRepairBatch(dst, check, fix [][][]byte, expectInput [][]bool, input [][][]byte, profile ErasureProfile) ([][]uint64, []error) {
+	errs := make([]error, len(dst))
+	counts := make([][]uint64, len(dst))
+	for b := range dst {
+		if len(check) != len(dst) || len(fix) != len(dst) || len(expectInput) != len(dst) || len(input) != len(dst) {
+			errs[b] = fmt.Errorf("erasure: %d check rows, %d fix rows, %d expect rows and %d input rows for %d stripes",
+				len(check), len(fix), len(expectInput), len(input), len(dst))
+			continue
+		}
+		counts[b], errs[b] = c.DecodeRepair(dst[b], check[b], fix[b], expectInput[b], input[b], profile)
+	}
+	return counts, errs
+}
+
 // ErrLocateUnavailable is what Locate reports on builds without the GPU codec: the CPU codec
 // has no locator (the reference finds a bad shard by its checksum, manager.go:250-320).
 var ErrLocateUnavailable = errors.New("erasure: locating corrupt shards needs the GPU codec")

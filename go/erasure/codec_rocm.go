@@ -1173,6 +1173,141 @@ func (c *Codec) DecodeCheckBatch(dst, check [][][]byte, expectInput [][]bool, in
 	return errs
 }
 
+// ---- progressive repair (DESIGN.md §5.16) ------------------------------------------------
+
+// DecodeRepair is the final DecodeCheck call that repairs what it flags (rs_decode_repair): dst,
+// check, expectInput and input as DecodeCheck takes them; fix (k+m entries, nil = none) holds
+// buffers at expected or compared indices into which the shard's error values are XORed -- a
+// zeroed buffer ends as the error row, the shard as delivered ends restored, and fix[i] may be
+// input[i]. With three or more compared shards a single corrupt shard per byte column is taken
+// out of the wanted shards and named: counts[i] is the number of columns blamed on shard i,
+// counts[k+m] the number left unexplained. A stripe with an unexplained column returns
+// ErrShardCorrupted after the wanted shards have been written, as DecodeCheck does. Like the
+// rest of this package it has never been compiled where the library is developed. Not in the
+// reference API.
+func (c *Codec) DecodeRepair(dst, check, fix [][]byte, expectInput []bool, input [][]byte, profile ErasureProfile) ([]uint64, error) {
+	counts, errs := c.DecodeRepairBatch([][][]byte{dst}, [][][]byte{check}, [][][]byte{fix}, [][]bool{expectInput},
+		[][][]byte{input}, profile)
+	return counts[0], errs[0]
+}
+
+// DecodeRepairBatch is DecodeRepair for many stripes of one profile in one call
+// (rs_decode_repair_batch); counts[b] and errs[b] are what DecodeRepair would report for stripe b.
+func (c *Codec) DecodeRepairBatch(dst, check, fix [][][]byte, expectInput [][]bool, input [][][]byte, profile ErasureProfile) ([][]uint64, []error) {
+	k, m := profile.DataShards, profile.ParityShards
+	errs := make([]error, len(dst))
+	counts := make([][]uint64, len(dst))
+	if len(check) != len(dst) || len(fix) != len(dst) || len(expectInput) != len(dst) || len(input) != len(dst) {
+		for b := range errs {
+			errs[b] = fmt.Errorf("erasure: %d check rows, %d fix rows, %d expect rows and %d input rows for %d stripes",
+				len(check), len(fix), len(expectInput), len(input), len(dst))
+		}
+		return counts, errs
+	}
+	if k < 1 || m < 1 {
+		for b := range errs {
+			errs[b] = ErrInvalidProfile
+		}
+		return counts, errs
+	}
+	if len(dst) == 0 {
+		return counts, errs
+	}
+	if k+m > 256 || device() == nil {
+		for b := range dst {
+			counts[b], errs[b] = cpuDecodeRepair(dst[b], check[b], fix[b], expectInput[b], input[b], k, m)
+		}
+		return counts, errs
+	}
+	B, n := len(dst), k+m
+	ins, outs, accs, fixes := newCArray(B*n), newCArray(B*n), newCArray(B*n), newCArray(B*n)
+	defer ins.free()
+	defer outs.free()
+	defer accs.free()
+	defer fixes.free()
+	sizes := make([]C.size_t, B)
+	status := make([]C.int, B)
+	expect := make([]C.uint8_t, B*n)
+	flat := make([]C.uint64_t, B*(n+1))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for b := range dst {
+		var S int
+		var err error
+		if len(check[b]) != n || len(dst[b]) != n || len(fix[b]) != n {
+			err = fmt.Errorf("erasure: failed to decode: %w", reedsolomon.ErrTooFewShards)
+		} else {
+			rows := make([][]byte, n)
+			for i := range rows {
+				rows[i] = dst[b][i]
+				if len(check[b][i]) > 0 {
+					rows[i] = check[b][i]
+				}
+			}
+			S, err = checkDecodeIdx(rows, expectInput[b], input[b], k, m)
+			for i := 0; err == nil && i < n; i++ {
+				if len(fix[b][i]) > 0 && len(fix[b][i]) != S {
+					err = fmt.Errorf("erasure: failed to decode: %w", reedsolomon.ErrShardSize)
+				}
+			}
+		}
+		if err != nil {
+			errs[b] = err
+			for i := 0; i < k && i < n; i++ { // a well-formed stripe with nothing to do for the library
+				expect[b*n+i] = 1
+			}
+			continue
+		}
+		sizes[b] = C.size_t(S)
+		for i := 0; i < n; i++ {
+			if expectInput[b][i] {
+				expect[b*n+i] = 1
+			}
+			if len(input[b][i]) > 0 {
+				pin.Pin(&input[b][i][0])
+				ins.set(b*n+i, unsafe.Pointer(&input[b][i][0]))
+			}
+			if len(dst[b][i]) > 0 {
+				pin.Pin(&dst[b][i][0])
+				outs.set(b*n+i, unsafe.Pointer(&dst[b][i][0]))
+			}
+			if len(check[b][i]) > 0 {
+				pin.Pin(&check[b][i][0])
+				accs.set(b*n+i, unsafe.Pointer(&check[b][i][0]))
+			}
+			if len(fix[b][i]) > 0 {
+				pin.Pin(&fix[b][i][0])
+				fixes.set(b*n+i, unsafe.Pointer(&fix[b][i][0]))
+			}
+		}
+	}
+	rc := C.rs_decode_repair_batch(gpuCtx, C.int(k), C.int(m), C.int(B), &sizes[0], outs.at(0), accs.at(0), fixes.at(0),
+		&expect[0], ins.at(0), 0, &status[0], &flat[0])
+	if rc != C.RS_OK && !hasStatus(status, rc) { // a call-level error: no status was written
+		for b := range errs {
+			if errs[b] == nil {
+				errs[b] = decodeIdxErr(rc)
+			}
+		}
+		return counts, errs
+	}
+	for b := range errs {
+		if errs[b] != nil {
+			continue
+		}
+		counts[b] = make([]uint64, n+1)
+		for i := range counts[b] {
+			counts[b][i] = uint64(flat[b*(n+1)+i])
+		}
+		if status[b] == C.RS_E_CORRUPT {
+			errs[b] = ErrShardCorrupted
+		} else {
+			errs[b] = decodeIdxErr(status[b])
+		}
+	}
+	return counts, errs
+}
+
 // Overwrite replaces bytes [offset, offset+len(data)) of the object whose n shards these are
 // (Encode's layout: object byte x in data shard x/S at column x%S) and brings the parity up to
 // date (rs_codec_overwrite): only the affected parity columns are read and rewritten, through

@@ -110,6 +110,60 @@ func cpuDecodeCheck(dst, check [][]byte, expectInput []bool, input [][]byte, fin
 	return nil
 }
 
+// cpuDecodeRepair is DecodeRepair on the CPU (DESIGN.md §5.16). The CPU codec has no locator
+// (the reference finds a bad shard by its checksum), so this form never repairs: it is the final
+// DecodeCheck, with every mismatching byte column counted as unexplained in counts[k+m], no fix
+// buffer touched, and ErrShardCorrupted where a column mismatches -- what the GPU form reports
+// for a stripe with fewer than three compared shards. A fix buffer at an index that is neither
+// expected nor compared is refused as the library refuses it.
+func cpuDecodeRepair(dst, check, fix [][]byte, expectInput []bool, input [][]byte, k, m int) ([]uint64, error) {
+	n := k + m
+	if len(fix) != n || len(check) != n || len(expectInput) != n {
+		return nil, fmt.Errorf("erasure: failed to decode: %w", reedsolomon.ErrTooFewShards)
+	}
+	rows := 0
+	for i := 0; i < n; i++ {
+		if len(fix[i]) > 0 && !expectInput[i] && len(check[i]) == 0 {
+			return nil, fmt.Errorf("erasure: failed to decode: %w", reedsolomon.ErrInvalidInput)
+		}
+		if i < len(dst) && (len(dst[i]) > 0 || len(check[i]) > 0) {
+			rows++
+		}
+	}
+	if rows > 16 {
+		return nil, fmt.Errorf("erasure: failed to decode: %d wanted and compared shards, at most 16", rows)
+	}
+	// the syndromes on copies: a final call writes no accumulator
+	acc := make([][]byte, n)
+	for i := range check {
+		if len(check[i]) > 0 {
+			acc[i] = append([]byte(nil), check[i]...)
+		}
+	}
+	if err := cpuDecodeCheck(dst, acc, expectInput, input, false, k, m); err != nil {
+		return nil, err
+	}
+	counts := make([]uint64, n+1)
+	S := 0
+	for i := range acc {
+		if len(acc[i]) > S {
+			S = len(acc[i])
+		}
+	}
+	for x := 0; x < S; x++ {
+		for i := range acc {
+			if x < len(acc[i]) && acc[i][x] != 0 {
+				counts[n]++
+				break
+			}
+		}
+	}
+	if counts[n] != 0 {
+		return counts, ErrShardCorrupted
+	}
+	return counts, nil
+}
+
 // overwriteStripes cuts an overwrite of object bytes [offset, offset+len(data)) into at most
 // three stripes over disjoint column intervals of the S-byte shards (csrc/overwrite_plan.hpp):
 // the range's first shard changes from its first column on, its last shard up to its last

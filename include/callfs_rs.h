@@ -357,6 +357,40 @@ int rs_decode_check_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* si
                           uint8_t* const* dst, uint8_t* const* check, const uint8_t* expect,
                           const uint8_t* const* input, unsigned flags, int* status);
 
+/* ---- Progressive repair, host memory --------------------------------
+ * The final rs_decode_check call that repairs what it flags: expect, input, dst, check, fix and
+ * flags (0 or RS_DECODE_IDX_STORE; the call is always final) exactly as for
+ * rs_plan_create_decode_repair (below), every buffer in host memory, and the same result: the
+ * wanted shards with the error of every explained column taken out, and the error values XORed
+ * into the fix buffers the caller gave (XOR in place: a zeroed buffer ends as the error row, the
+ * shard as delivered ends restored; fix[i] may be input[i]).
+ * counts: batch * (k+m+1) words, zeroed and filled by the call, NULL allowed: entry i of stripe b
+ *   is the number of byte columns blamed on shard i, entry k+m the number left unexplained.
+ * status[b] (rs_decode_repair's return value): RS_OK for a clean stripe and for a stripe whose
+ *   mismatching columns were all explained -- its counts say what was repaired; RS_E_CORRUPT when
+ *   a column is unexplained (always, with fewer than three compared shards), the wanted shards
+ *   delivered all the same as upstream Decode delivers them; the stripe's own refusal in the plan
+ *   constructor's order otherwise (the expect count; a misplaced pointer, fix included; more than
+ *   16 rows: RS_E_UNSUPPORTED; a zero size in the launch), the other stripes running.
+ * rs_decode_repair_batch: the profile, NULL arrays (fix included; counts may be NULL), batch < 0
+ *   and an unknown flag bit fail the call. A call in which no stripe is in the launch reaches no
+ *   device, moves no counter and returns RS_OK.
+ * Both are a run of rs_decode_check's staged pipeline. A chunk is a final decode-check chunk;
+ * the fix pointer table goes up in a copy of its own; the counts and the fix rows (one per
+ * expected and compared shard of an item) live in the chunk's device mirror alone, zeroed there:
+ * no fix row is uploaded. The status words and wanted rows come back in one D2H, the counts in a
+ * second, and then only the fix rows with a nonzero count whose buffer the caller gave, one copy
+ * each, XORed into the caller's buffer. `copies` of rs_host_counters: 4 per store chunk, 5 per
+ * merge chunk, plus one per fix row that came back. A stripe above CALLFS_RS_CHUNK_BYTES is cut
+ * into column parts: counts add and flags OR. The staged transport alone. */
+int rs_decode_repair(rs_ctx* ctx, int k, int m, size_t S, uint8_t* const* dst, uint8_t* const* check,
+                     uint8_t* const* fix, const uint8_t* expect, const uint8_t* const* input,
+                     unsigned flags, uint64_t* counts);
+int rs_decode_repair_batch(rs_ctx* ctx, int k, int m, int batch, const size_t* sizes,
+                           uint8_t* const* dst, uint8_t* const* check, uint8_t* const* fix,
+                           const uint8_t* expect, const uint8_t* const* input, unsigned flags,
+                           int* status, uint64_t* counts);
+
 /* ---- counters of the host-memory path -----------------------------------------------
  * Monotonic per-context counts (relaxed atomics; what an operator graphs, and what shows
  * that a batch cost one round trip):
@@ -726,6 +760,63 @@ int rs_plan_create_decode_check(rs_ctx* ctx, int device, int k, int m, int batch
                                 const size_t* sizes, const uint8_t* expect,
                                 const uint8_t* const* input, uint8_t* const* dst,
                                 uint8_t* const* check, unsigned flags, rs_plan** out);
+
+/* ---- decode-repair plans: progressive repair ------------------------
+ * Not in the reference API. A final decode-check plan flags a stripe whose shards do not lie on
+ * one codeword; by then its wanted rows were built from the corrupt shard. A decode-repair plan
+ * is that final plan -- the same sizes, expect, input, dst and check arrays under the same
+ * contracts, and it is ALWAYS FINAL -- whose launch also names the corrupt shard byte column by
+ * byte column, repairs the wanted rows within the launch and hands the error values back:
+ *   fix     (pointers) batch * (k+m); non-NULL is allowed at an expected or a compared index
+ *                      (RS_E_ARG anywhere else). It names S bytes the caller owns. XOR in place
+ *                      is the whole contract: a zeroed buffer ends up holding the shard's error
+ *                      row, a buffer holding the shard as delivered ends up holding the shard
+ *                      restored. Only damaged 16-byte vectors (and damaged tail bytes) are read and
+ *                      written. fix[i] may equal input[i] of the same plan, a shard repaired where
+ *                      it lies; otherwise dst's overlap contract applies.
+ *   flags              0 (merge) or RS_DECODE_IDX_STORE; any other bit is RS_E_ARG.
+ * Every row's final value is what the final decode-check launch forms (merge: the accumulator XOR
+ * the computed row; store: the computed row). Per byte column the r' check values are the
+ * syndromes and the correct plans' rule decides over them (locate_correct with rows = r', so a
+ * verdict needs r' >= 3: with fewer every mismatching column is unexplained):
+ *   expected shard V[j], value e   every wanted row r gets G[r][j] * e XORed in
+ *                                  (G = E[rows] * inv(E[V])); e is XORed into fix[V[j]]'s byte
+ *                                  when that pointer is given;
+ *   compared shard x, value s_x    the wanted rows are unchanged; s_x is XORed into fix[x]'s byte
+ *                                  when given;
+ *   unexplained                    the wanted rows are stored as computed; the column is counted.
+ * The wanted rows hold these values when the launch has finished on the stream. Within the
+ * launch a wanted row's 16-byte vector is stored as computed first and, in a vector with a
+ * repaired column, read back and stored again by the same lane: until the launch ends dst may
+ * hold the unrepaired bytes, as it may hold anything while a launch writes it.
+ * A check row is NOT WRITTEN. The stripe's status word is set for every stripe that had a
+ * mismatching column, repaired or not, as for correct plans. The plan holds batch * (k+m+1) counts
+ * that rs_plan_blame reads and clears, launches adding into them until the next read: entry i of
+ * stripe b is the number of columns blamed on shard i (whether or not fix[i] was given), entry
+ * k+m the number of unexplained columns.
+ * A LAUNCH WITH WANTED ROWS IN MERGE MODE IS NOT IDEMPOTENT, as every merge, and a launch with a
+ * fix row that finds damage is not either; A LAUNCH WITH NO WANTED AND NO FIX ROWS IS IDEMPOTENT
+ * (counts and the status word accumulate until read).
+ * A stripe has at most 16 rows, compared and wanted together: all syndromes and all wanted rows
+ * of a column meet in one block, and the plan has one launch group.
+ * An ordinary plan, as a final decode-check plan: rs_plan_launch[_timed] only enqueue
+ * (graph-capturable); rs_plan_status, rs_plan_stripe_status, rs_plan_blame and rs_plan_groups as
+ * on correct plans; rs_plan_bytes is the final decode-check plan's figure for the same flags (the
+ * few repaired bytes are not counted); rs_plan_forms reports RS_ORDER_DECODE_REPAIR +
+ * RS_ORDER_CONSECUTIVE; rs_plan_tune fills -1, rs_plan_set_orders takes -1 only and the ceiling
+ * launches return RS_E_ARG.
+ * Errors, in this order: the profile; a NULL sizes, expect, input, dst, check, fix or out,
+ * batch < 1, or an unknown flag bit (RS_E_ARG); the expect count (RS_E_TOO_FEW_SHARDS below k,
+ * RS_E_ARG above); a misplaced pointer -- rs_plan_create_decode_check's, or a fix at an index that
+ * is neither expected nor compared (RS_E_ARG); a stripe with more than 16 rows
+ * (RS_E_UNSUPPORTED); sizes[b] == 0 on a stripe in the launch (RS_E_NO_DATA). Each check runs
+ * over the whole batch before the next. Nothing is created on an error. */
+#define RS_ORDER_DECODE_REPAIR 131072
+int rs_plan_create_decode_repair(rs_ctx* ctx, int device, int k, int m, int batch,
+                                 const size_t* sizes, const uint8_t* expect,
+                                 const uint8_t* const* input, uint8_t* const* dst,
+                                 uint8_t* const* check, uint8_t* const* fix, unsigned flags,
+                                 rs_plan** out);
 
 /* ---- locate plans: which shard is corrupt --------------------------
  * Not in the reference API. Every other plan tells that a stripe's compared shards mismatch; a

@@ -528,6 +528,19 @@ shift
 timeout -k 10 400 python3 -u tools/decode_check_bench.py "$@" | tee $O/decode_check_bench.jsonl || exit $?
 }
 
+# The final decode-repair launch of the last survivor against the final decode-check launch of
+# the same shape, on clean data, with one bad 4 KiB sector per stripe and with one survivor
+# wholly corrupt (tools/decode_repair_bench.py): RS(10,4) with 1 wanted and 3
+# check rows and RS(10,6) with 3 + 3, 256 stripes of 1 MiB, planar. One JSON line per shape on
+# stdout and in <out dir>/decode_repair_bench.jsonl.
+# Usage: bash tools/jobs.sh decode_repair_bench <out dir> [decode_repair_bench.py args]
+job_decode_repair_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+O=${1:-decode_repair_out}; mkdir -p "$O" || exit $?
+shift
+timeout -k 10 400 python3 -u tools/decode_repair_bench.py "$@" | tee $O/decode_repair_bench.jsonl || exit $?
+}
+
 # Locate plans against the compare-only plan of the same batch and against batched SHA-256 of
 # every shard (tools/locate_bench.py): RS(10,4) x 256 stripes of 64 KiB..4 MiB
 # and RS(16,4) x 4,096 stripes of 1..16 KiB, clean and with one shard of every stripe wholly
