@@ -1,5 +1,6 @@
 """Every tile-map kernel kind (mixed, ragged, required, update pair and single, decode-idx merge
-and store, final decode-check merge and store, locate, locate2, correct) over one lattice of source
+and store, final decode-check merge and store, decode-repair merge and store, locate, locate2,
+correct) over one lattice of source
 counts and row counts, so that every instance (RT 4 for R <= 4, RT 8 for R 5..8, RT 16 for R 9..16)
 of every kind runs at the edges of its input ring (3 slots for RT <= 8, 5 for RT 16), of the early
 compare point (4 sources before the end) and of its row loops, in first and in second launch
@@ -32,7 +33,8 @@ CLASS_ROWS = {"rt4": 4, "rt8": 8, "rt16": 16}
 ROW_AXIS = {"rt4": (1, 2, 3, 4), "rt8": (5, 6, 7, 8), "rt16": (9, 10, 13, 16)}
 SECOND_GROUPS = (17, 21, 25, 32)  # at k = 5: second groups of 1, 5, 9 and 16 rows
 REBUILD = ("mixed", "ragged", "required")
-COUNTED = ("update-pair", "update-single", "merge", "merge-store", "check", "check-store")
+COUNTED = ("update-pair", "update-single", "merge", "merge-store", "check", "check-store", "repair", "repair-store")
+REPAIR = ("repair", "repair-store")
 LOCATE = ("locate", "locate2", "correct")
 KINDS = REBUILD + COUNTED + LOCATE
 
@@ -48,7 +50,7 @@ def _no_tuned_forms(native_lib):
 def _narrow(m):
     """Row counts below m for the stripes that run in a wider instance than they need: 1 and 9
     beside 16, 5 beside 8."""
-    return [w for w in (1, 9, 5, 13, 2, 7) if w < m]
+    return SL.narrow_rows(m)
 
 
 def _idx_sets(k, m, counts):
@@ -106,6 +108,10 @@ def _run_counted(kind, k, m, counts, seed):
         assert max(len(w) for w in wanted) == m
         SL.run_decode_idx(k, m, sizes, expect, wanted, SL.pick_sets(k, counts, seed),
                           store=kind == "merge-store", seed=seed)
+    elif kind in REPAIR:
+        store = kind == "repair-store"
+        md = SL.run_decode_repair(k, m, SL.repair_counted(k, m, counts, store, seed), store, seed=seed)
+        SL.check_repair_counted(md, k, m, counts, store)
     else:
         store = kind == "check-store"
         # the widest stripe, stripe 0, has the most sources; the last has none: its accumulators
@@ -163,11 +169,12 @@ def test_row_axis(native_lib, kind, cls):
                 _run_profile(kind, k, m, seed=100 * k + m)
 
 
-@pytest.mark.parametrize("kind", REBUILD + COUNTED)
+@pytest.mark.parametrize("kind", [kind for kind in REBUILD + COUNTED if kind not in REPAIR])
 def test_second_launch_groups(native_lib, kind):
     """RS(5, m) with m = 17, 21, 25, 32: a second launch group of 1, 5, 9 and 16 rows, so of every
     instance class. The mixed masks hold an encode and decode patterns; the decode-check stripes
-    have check rows on both sides of row 16."""
+    have check rows on both sides of row 16. (A decode-repair stripe has at most 16 rows and one
+    group: test_gpu_decode_repair.py holds the 17-row refusal.)"""
     for m in SECOND_GROUPS:
         if kind in COUNTED:
             _run_counted(kind, 5, m, (1, 3, 5, 4), seed=m)
@@ -213,6 +220,39 @@ def test_decode_check_five_to_eight_rows(native_lib, mode):
     assert {len(w) + len(c) for w, c in zip(wanted, compared)} == {5, 6, 7, 8}
     feeds = SL.pick_sets(k, nfeed, seed=58)
     SL.run_decode_check(k, m, sizes, expect, wanted, compared, feeds, store, damage, seed=58)
+
+
+# ---- decode-repair: its two row axes, and runs inside one 16-byte vector ------------------------
+
+@pytest.mark.parametrize("mode", ["merge", "store"])
+@pytest.mark.parametrize("shape", [s for cls in SL.REPAIR_ROWS.values() for s in cls], ids=lambda s: "%d+%d" % s)
+def test_repair_row_axes(native_lib, shape, mode):
+    """(check rows, wanted rows) at the edges of every instance class -- 5 and 9 rows, 16 check rows
+    and no wanted row -- at check-row counts that straddle a 4-row group and reach words 2 and 3 of
+    the packed accumulator, at k = 3 and k = 6: a clean stripe, an expected shard's byte in the
+    vector body, the last check row's compared shard (syndrome byte r' - 1) in the tail, the first
+    check row's compared shard."""
+    nchk, nwant = shape
+    for k in (3, 6):
+        seed = 100 * k + 16 * nchk + nwant
+        stripes = SL.repair_row_stripes(k, nchk, nwant, mode == "store", seed)
+        md = SL.run_decode_repair(k, nchk + nwant, stripes, mode == "store", seed=seed)
+        SL.check_repair_rows(md, nchk, nwant)
+
+
+@pytest.mark.parametrize("fix", ["zero", "mixed"])
+@pytest.mark.parametrize("mode", ["merge", "store"])
+@pytest.mark.parametrize("shape", SL.RUN_SHAPES, ids=lambda s: "%d+%d" % s)
+def test_repair_runs_within_a_vector(native_lib, shape, mode, fix):
+    """Several verdicts inside one 16-byte vector (SL.repair_run_stripes): the gathered error vector
+    is applied when the verdict changes, twice into one fix vector, after an unexplained column, in
+    every column in turn, at positions k - 1 and k, with the flush flags and run lengths differing
+    from lane to lane; in vector 0, lanes 63 and 64, the first vector of tile 1 and the last vector
+    before the tail. With A's fix pointer null the wanted rows and the counts are the same."""
+    store = mode == "store"
+    stripes, names = SL.repair_run_stripes(*shape, store, fix)
+    md = SL.run_decode_repair(10, sum(shape), stripes, store, seed=7 * shape[0] + shape[1])
+    SL.check_repair_runs(md, names, shape, fix)
 
 
 # ---- the > 64 KiB dynamic-LDS opt-in ---------------------------------------------------------
