@@ -47,6 +47,8 @@ RS_E_NOMEM = -12
 
 RS_DECODE_IDX_STORE = 1  # rs_plan_create_decode_idx / rs_decode_idx flags
 RS_DECODE_CHECK_FINAL = 2  # rs_plan_create_decode_check: test the check rows, write none
+RS_SESSION_CHECK = 0  # rs_session_open flags
+RS_SESSION_REPAIR = 1
 RS_ORDER_DECODE_CHECK = 65536  # rs_plan_forms of a final decode-check plan (+ consecutive)
 RS_ORDER_DECODE_REPAIR = 131072  # rs_plan_forms of a decode-repair plan (+ consecutive)
 
@@ -170,6 +172,16 @@ SIGNATURES = {
     "rs_plan_create_decode_repair": (_int, [_vp, _int, _int, _int, _int, ctypes.POINTER(_sz), _u8p,
                                             ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                             ctypes.POINTER(_vp), ctypes.c_uint, ctypes.POINTER(_vp)]),
+    "rs_feed_create": (_int, [_vp, _int, _int, _int, _sz, _u8p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                              ctypes.POINTER(_vp)]),
+    "rs_feed_launch": (_int, [_vp, _int, _vp, ctypes.c_uint, _vp]),
+    "rs_feed_destroy": (None, [_vp]),
+    "rs_session_open": (_int, [_vp, _int, _int, _sz, _u8p, _u8p, _u8p, ctypes.c_uint, ctypes.POINTER(_vp)]),
+    "rs_session_feed": (_int, [_vp, _int, _vp]),
+    "rs_session_peek": (_int, [_vp, _int, _vp, _sz]),
+    "rs_session_finish": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp),
+                                 ctypes.POINTER(ctypes.c_uint64)]),
+    "rs_session_close": (None, [_vp]),
     "rs_decode_check": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u8p,
                                ctypes.POINTER(_vp), ctypes.c_uint]),
     "rs_decode_check_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_sz), ctypes.POINTER(_vp),

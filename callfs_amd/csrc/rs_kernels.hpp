@@ -366,6 +366,36 @@ struct RepairArgs {
 hipError_t launch_decode_repair(ApplyArgs a, const RepairArgs& x, bool store, bool any_tail,
                                 hipStream_t stream, LaunchEvents ev = {});
 
+// ---- feed launches (rs_feed.hpp in rs_mixed.hip) -------------------------
+// One delivered shard of one stripe into the stripe's R <= 16 resident rows:
+//   row[r] ^= c[r] * src   (merge; a row with c[r] == 0 is neither read nor written)
+//   row[r]  = c[r] * src   (store: no row byte is read)
+// over [0, S), with c the column of the shard's table block. The kernel's second argument: the
+// source and, for instances of up to 8 rows, the row pointers by value (the 16-row instance reads
+// them from FeedArgs::row_tab).
+template <int RT>
+struct FeedRows {
+  const uint8_t* src;
+  uint8_t* row[RT > 8 ? 1 : RT];
+};
+
+struct FeedArgs {
+  const uint8_t* src;       // S bytes the device can read, any alignment
+  const uint32_t* tabs;     // device memory: the shard's block, [R][5] v_perm tables
+  uint8_t* const* row_tab;  // device memory: the R row pointers
+  uint8_t* const* rows;     // host memory: the same R pointers
+  uint64_t S;
+  int R;
+};
+
+// bytes of the source, and of every row, that one block of a feed launch covers
+constexpr uint32_t kFeedTileBytes = 4096;
+
+// Enqueues rs_feed (store: its STORE instances) in the smallest instance that holds R rows, on a
+// grid of ceil(S / kFeedTileBytes) blocks: one dispatch, no allocation, no copy, no sync. R == 0
+// enqueues nothing. A merge launch is NOT idempotent; a store launch is.
+hipError_t launch_feed(const FeedArgs& x, bool store, hipStream_t stream, LaunchEvents ev = {});
+
 // ---- locate launches (rs_mixed.hip) --------------------------------------
 // A required launch group in which every row is compared and none written, and a mismatching
 // byte column is classified instead of only flagged: locate_classify (locate_tables.hpp) turns

@@ -15,6 +15,8 @@
 // launches (§5.13) are locate launches that XOR the error value into the blamed shard's byte.
 // Decode-repair launches (§5.16, rs_repair.hpp) are final decode-check launches that classify a
 // mismatching column from their check rows and repair the wanted rows before storing them.
+// Feed launches (§5.17, rs_feed.hpp) deliver one shard of one stripe into its resident rows: the
+// v_perm form, selected by argument, with no tile map and no LDS.
 #include <algorithm>
 #include <array>
 
@@ -25,6 +27,7 @@
 #include "locate_tables.hpp"
 #include "rs_apply.hpp"
 #include "rs_check.hpp"
+#include "rs_feed.hpp"
 #include "rs_merge.hpp"
 #include "rs_update.hpp"
 
@@ -626,6 +629,22 @@ const std::array<std::array<RepairFn, 3>, 2> kRepair = {{
     {kRepairInstance<4, false>, kRepairInstance<8, false>, kRepairInstance<16, false>},
     {kRepairInstance<4, true>, kRepairInstance<8, true>, kRepairInstance<16, true>}}};
 
+// Feed launches (rs_feed.hpp): [store][0: R <= 4, 1: R 5..8, 2: R 9..16]
+template <int RT>
+using FeedFn = void (*)(ApplyArgs, FeedRows<RT>);
+template <int RT>
+constexpr std::array<FeedFn<RT>, 2> kFeed = {&dev::rs_feed<RT, false>, &dev::rs_feed<RT, true>};
+
+template <int RT>
+void dispatch_feed(const ApplyArgs& a, const FeedArgs& x, bool store, uint32_t grid, hipStream_t stream,
+                   const LaunchEvents& ev) {
+  FeedRows<RT> rows{};
+  rows.src = x.src;
+  if constexpr (RT <= 8)
+    for (int r = 0; r < a.R; ++r) rows.row[r] = x.rows[r];
+  dispatch(kFeed<RT>[store ? 1 : 0], dim3(grid), dim3(dev::kFeedBlock), 0, stream, ev, true, true, a, rows);
+}
+
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
 // per-device attribute (dispatch.hpp DeviceOnce), keyed by the 16-row instance it is set on
 enum class WideLds { kMixed, kRagged, kRaggedSome, kUpdate, kUpdatePair, kLocate, kLocate2, kCorrect,
@@ -760,6 +779,26 @@ hipError_t launch_decode_idx(ApplyArgs a, const MergeArgs& x, bool store, bool a
   return launch_tiles(kMerge[store ? 1 : 0][a.R > 8 ? 2 : a.R > 4 ? 1 : 0],
                       store ? WideLds::kMergeStore : WideLds::kMerge, x.u.ntiles, a, x,
                       a.K + (store ? 1 : 2) * a.R, stream, ev);
+}
+
+hipError_t launch_feed(const FeedArgs& x, bool store, hipStream_t stream, LaunchEvents ev) {
+  if (x.R < 0 || x.R > kMaxRowsPerLaunch || !x.src || !x.tabs || !x.row_tab || !x.rows || x.S == 0)
+    return hipErrorInvalidValue;
+  if (x.R == 0) return hipSuccess;  // no row to feed
+  const uint64_t grid = (x.S + kFeedTileBytes - 1) / kFeedTileBytes;
+  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
+  ApplyArgs a{};
+  a.out_tab = x.row_tab;
+  a.tabs = x.tabs;
+  a.S = x.S;
+  a.nvec = x.S / 16;
+  a.K = 1;
+  a.R = x.R;
+  a.batch = 1;
+  if (x.R > 8) dispatch_feed<16>(a, x, store, static_cast<uint32_t>(grid), stream, ev);
+  else if (x.R > 4) dispatch_feed<8>(a, x, store, static_cast<uint32_t>(grid), stream, ev);
+  else dispatch_feed<4>(a, x, store, static_cast<uint32_t>(grid), stream, ev);
+  return hipGetLastError();
 }
 
 hipError_t launch_decode_check(ApplyArgs a, const CheckArgs& x, bool store, bool any_tail,

@@ -10,6 +10,7 @@
 #include "decode_check_tables.hpp"
 #include "decode_idx_tables.hpp"
 #include "decode_repair_tables.hpp"
+#include "feed_tables.hpp"
 #include "locate_tables.hpp"
 #include "mixed_tables.hpp"
 #include "ragged_tables.hpp"
@@ -114,6 +115,19 @@ struct rs_plan {
   }
   ~rs_plan() {
     if (dmeta.p) (void)hipSetDevice(device);  // the buffer is freed on the plan's device
+  }
+};
+
+// A feed object (rs_feed_create): feed_tables.hpp's arena in one device buffer
+// behind the table of row pointers, uploaded once. A launch picks the delivered shard's block.
+struct rs_feed {
+  int device = 0;
+  size_t S = 0;
+  FeedTables t;
+  std::vector<uint8_t*> rows;  // compared, then wanted
+  DevBuf dmeta;                // [kFeedMaxRows] row pointers, then the arena
+  ~rs_feed() {
+    if (dmeta.p) (void)hipSetDevice(device);  // the buffer is freed on the object's device
   }
 };
 
@@ -1153,6 +1167,69 @@ int rs_plan_blame(rs_plan* plan, void* stream, uint64_t* counts) {
 uint64_t rs_plan_bytes(const rs_plan* plan) { return plan ? plan->bytes : 0; }
 
 int rs_plan_groups(const rs_plan* plan) { return plan ? static_cast<int>(plan_groups(*plan)) : 0; }
+
+// ---- feed objects -----------------------------------------------------------
+
+int rs_feed_create(rs_ctx* ctx, int device, int k, int m, size_t S, const uint8_t* expect, uint8_t* const* dst,
+                   uint8_t* const* check, rs_feed** out) {
+  DeviceGuard dg;
+  if (const int rc = check_profile(k, m)) return rc;
+  if (!ctx || !expect || !dst || !check || !out) return RS_E_ARG;
+  *out = nullptr;
+  const size_t n = static_cast<size_t>(k + m);
+  std::vector<uint8_t> have_dst(n), have_chk(n);
+  for (size_t i = 0; i < n; ++i) {
+    have_dst[i] = dst[i] != nullptr;
+    have_chk[i] = check[i] != nullptr;
+  }
+  auto feed = std::make_unique<rs_feed>();
+  switch (build_feed_tables(k, m, S, expect, have_dst.data(), have_chk.data(), feed->t)) {
+    case FeedError::kOk: break;
+    case FeedError::kArg: return RS_E_ARG;
+    case FeedError::kTooFewShards: return RS_E_TOO_FEW_SHARDS;
+    case FeedError::kUnsupported: return RS_E_UNSUPPORTED;
+    case FeedError::kNoData: return RS_E_NO_DATA;
+    case FeedError::kSingular: return RS_E_SINGULAR;
+  }
+  if (!ctx->device(device)) return RS_E_ARG;
+  feed->device = device;
+  feed->S = S;
+  for (int i : feed->t.rows) feed->rows.push_back(check[i] ? check[i] : dst[i]);
+  constexpr size_t kRowTabBytes = kFeedMaxRows * sizeof(uint8_t*);
+  std::vector<uint8_t> h(kRowTabBytes + feed->t.arena.size() * sizeof(uint32_t), 0);
+  if (!feed->rows.empty()) {
+    std::memcpy(h.data(), feed->rows.data(), feed->rows.size() * sizeof(uint8_t*));
+    std::memcpy(h.data() + kRowTabBytes, feed->t.arena.data(), feed->t.arena.size() * sizeof(uint32_t));
+  }
+  if (const int rc = upload(feed->dmeta, device, h.data(), h.size())) return rc;
+  *out = feed.release();
+  return RS_OK;
+}
+
+int rs_feed_launch(rs_feed* feed, int idx, const uint8_t* src, unsigned flags, void* stream) {
+  DeviceGuard dg;
+  if (!feed || !src || (flags & ~RS_DECODE_IDX_STORE)) return RS_E_ARG;
+  const int pos = feed->t.position(idx);
+  if (pos < 0) return RS_E_ARG;
+  if (feed->t.R() == 0) return RS_OK;  // no row: nothing to enqueue
+  HIPCHK(hipSetDevice(feed->device));
+  auto* d = static_cast<uint8_t*>(feed->dmeta.p);
+  FeedArgs x{};
+  x.src = src;
+  x.tabs = reinterpret_cast<const uint32_t*>(d + kFeedMaxRows * sizeof(uint8_t*)) +
+           static_cast<size_t>(pos) * feed->t.block_words();
+  x.row_tab = reinterpret_cast<uint8_t* const*>(d);
+  x.rows = feed->rows.data();
+  x.S = feed->S;
+  x.R = feed->t.R();
+  HIPCHK(launch_feed(x, (flags & RS_DECODE_IDX_STORE) != 0, static_cast<hipStream_t>(stream)));
+  return RS_OK;
+}
+
+void rs_feed_destroy(rs_feed* feed) {
+  DeviceGuard dg;
+  delete feed;
+}
 
 // ---- one-shot device calls ------------------------------------------------------------------------
 

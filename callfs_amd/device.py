@@ -646,6 +646,51 @@ class Plan:
             pass
 
 
+class Feed:
+    """rs_feed_create / rs_feed_launch: one stripe of S-byte shards whose k
+    expected, wanted and compared shards are fixed up front; every launch delivers one shard into
+    the resident rows. expect: k+m flags, exactly k set. dst, check: k+m device pointers, nonzero =
+    shard i is wanted / compared and this is its S-byte accumulator (neither at an expected index,
+    never both at one). At most 16 rows. The tables are built and uploaded once, here."""
+
+    def __init__(self, k: int, m: int, S: int, expect, dst, check, device: int = 0,
+                 context: Optional[N.Context] = None):
+        self.ctx = context or N.default_context()
+        n = k + m
+        if len(expect) != n or len(dst) != n or len(check) != n:
+            raise ValueError("need k+m expect flags, dst pointers and check pointers")
+        self.k, self.m, self.S, self.device = k, m, S, device
+        self.handle = None
+        flags = (ctypes.c_uint8 * n)(*[1 if f else 0 for f in expect])
+        arr = lambda p: (ctypes.c_void_p * n)(*[int(x) or None for x in p])  # noqa: E731
+        h = ctypes.c_void_p()
+        N.check(N.lib.rs_feed_create(self.ctx.handle, device, k, m, S, flags, arr(dst), arr(check),
+                                     ctypes.byref(h)), "rs_feed_create")
+        self.handle = h
+
+    def launch(self, idx: int, src: int, store: bool = False,
+               stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Delivers shard idx (expected or compared) from `src`, the address of S bytes the device
+        can read, at any alignment: every row ^= its coefficient times the shard, or = with
+        store=True (no row is read, every row is written). Only enqueues. A merge launch is NOT
+        idempotent."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        N.check(N.lib.rs_feed_launch(self.handle, idx, ctypes.c_void_p(int(src)),
+                                     N.RS_DECODE_IDX_STORE if store else 0,
+                                     ctypes.c_void_p(s.cuda_stream)), "rs_feed_launch")
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            N.lib.rs_feed_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HashPlan:
     """Batched SHA-256 (erasure.ShardChecksum, codec.go:81-84) of device-resident
     messages: rs_sha256_plan_* over `pointers`/`lengths` (device addresses, bytes)."""

@@ -261,6 +261,30 @@ class Codec:
             return out
         raise _decode_error(rc)
 
+    def decode_session(self, profile: ErasureProfile, original_size: int, expect: Sequence[int],
+                       compare: Sequence[int] = (), repair: bool = False) -> "ObjectDecodeSession":
+        """A progressive decode for a download that receives its shards one at
+        a time, Manager.RetrieveFile's case: expect names the k shard indices that will be fed,
+        compare the indices fetched beyond them that are checked against them (with repair=True:
+        and used to repair a corrupt one). feed(idx, shard) as each lands, from any thread;
+        finish() returns the object's original_size bytes, bit for bit what decode returns for
+        the same shards. The data shards outside expect are the ones rebuilt."""
+        k, m = profile.data_shards, profile.parity_shards
+        if k < 1 or m < 1:
+            raise ErrInvalidProfile()
+        if k + m > 256:
+            raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create decoder")
+        n = k + m
+        size = max(int(original_size), 0)
+        S = max(1, (size + k - 1) // k)
+        e, c = set(int(i) for i in expect), set(int(i) for i in compare)
+        if any(i < 0 or i >= n for i in e | c):
+            raise ErrInvalidShardIdx()
+        session = DecodeSession(k, m, S, [i in e for i in range(n)],
+                                [i < k and i not in e and i not in c for i in range(n)],
+                                [i in c for i in range(n)], repair, self.context)
+        return ObjectDecodeSession(session, size)
+
     def decode_heal(self, shards: List, profile: ErasureProfile,
                     original_size: int, max_errors: int = 1) -> Tuple[bytearray, List[int]]:
         """rs_codec_decode_heal: decode() that repairs what it can where
@@ -937,6 +961,170 @@ def decode_repair_batch(dst: Sequence[Sequence], check: Sequence[Sequence], fix:
     if rc != N.RS_OK and rc not in out:
         N.check(rc, "rs_decode_repair_batch")
     return out, [list(counts[b * (k + m + 1):(b + 1) * (k + m + 1)]) for b in range(B)]
+
+
+class DecodeSession:
+    """rs_session_open: a progressive decode of one stripe whose rows stay on the
+    device. expect, want and compare are k+m flags each: the k shards that will be fed, the shards
+    to rebuild, the shards fetched beyond the k that are checked against them. feed() delivers one
+    shard from host memory, from any thread and in any order; peek() reads a row's partial result;
+    finish() closes the decode -- with repair=True it also repairs what the compared shards
+    explain. A context manager: leaving it closes the session."""
+
+    def __init__(self, k: int, m: int, S: int, expect: Sequence[bool], want: Sequence[bool],
+                 compare: Optional[Sequence[bool]] = None, repair: bool = False,
+                 context: Optional[N.Context] = None):
+        self.ctx = context or N.default_context()
+        n = k + m
+        compare = [False] * n if compare is None else compare
+        if len(expect) != n or len(want) != n or len(compare) != n:
+            raise ErrTooFewShards()
+        self.k, self.m, self.S, self.repair = k, m, int(S), repair
+        self.want = [bool(w) for w in want]
+        self.handle = None
+        self.shards: List = [None] * n
+        flags = lambda v: (ctypes.c_uint8 * n)(*[1 if f else 0 for f in v])  # noqa: E731
+        h = ctypes.c_void_p()
+        rc = N.lib.rs_session_open(self.ctx.handle, k, m, self.S, flags(expect), flags(want), flags(compare),
+                                   N.RS_SESSION_REPAIR if repair else N.RS_SESSION_CHECK, ctypes.byref(h))
+        if rc == N.RS_E_ARG:
+            raise ErrInvalidInput()
+        if rc == N.RS_E_INVALID_PROFILE:
+            raise ErrInvalidProfile()
+        if rc != N.RS_OK:
+            raise _wrapped(rc, "decode_session")
+        self.handle = h
+
+    def feed(self, idx: int, shard) -> None:
+        """Delivers shard idx (S bytes), expected or compared, once. Returns when `shard` may be
+        reused."""
+        if len(shard) != self.S:
+            raise ErrShardSize()
+        rc = N.lib.rs_session_feed(self.handle, int(idx), ctypes.c_void_p(_addr(shard)))
+        if rc == N.RS_E_ARG:
+            raise ErrInvalidInput()
+        if rc != N.RS_OK:
+            raise _wrapped(rc, "decode_session feed")
+
+    def peek(self, idx: int, length: Optional[int] = None) -> bytearray:
+        """The first `length` (default S) bytes of the row of a wanted or compared shard, after
+        the feeds so far."""
+        out = bytearray(self.S if length is None else int(length))
+        one = bytearray(1)  # a zero-length peek still waits for the feeds
+        rc = N.lib.rs_session_peek(self.handle, int(idx), ctypes.c_void_p(_addr(out or one)), len(out))
+        if rc == N.RS_E_ARG:
+            raise ErrInvalidInput()
+        if rc != N.RS_OK:
+            raise _wrapped(rc, "decode_session peek")
+        return out
+
+    def finish(self, dst: Optional[Sequence] = None, dst_lens: Optional[Sequence[int]] = None,
+               fix: Optional[Sequence] = None) -> List[int]:
+        """Closes the decode. dst: k+m entries, a writable buffer per wanted shard (None: the
+        session allocates them); dst_lens: how many bytes each receives (default S). The wanted
+        shards are then in self.shards. fix (repair=True): k+m entries, writable S-byte buffers
+        at expected or fed compared indices into which the shards' error values are XORed.
+        Returns the k+m+1 counts (zeros without repair; also kept in self.counts). Raises ErrTooFewShards before the k-th
+        expected shard -- the session stays usable -- and ErrShardCorrupted, after the wanted
+        shards have been written, when the compared shards do not lie on the expected shards'
+        codeword (repair=True: when a column stays unexplained)."""
+        n = self.k + self.m
+        if dst is None:
+            dst = [bytearray(self.S) if w else None for w in self.want]
+        if len(dst) != n or (fix is not None and len(fix) != n) or (dst_lens is not None and len(dst_lens) != n):
+            raise ErrTooFewShards()
+        if any(d is not None and not _writable(d) for d in list(dst) + list(fix or [])):
+            raise ErrInvalidInput()
+        lens = None if dst_lens is None else (ctypes.c_size_t * n)(*[int(x) for x in dst_lens])
+        counts = (ctypes.c_uint64 * (n + 1))()
+        rc = N.lib.rs_session_finish(self.handle, _shard_ptrs(list(dst)), lens,
+                                     None if fix is None else _shard_ptrs(list(fix)), counts)
+        self.counts = list(counts)
+        if rc in (N.RS_OK, N.RS_E_CORRUPT):
+            self.shards = list(dst)
+        if rc == N.RS_E_ARG:
+            raise ErrInvalidInput()
+        if rc == N.RS_E_CORRUPT:
+            raise ErrShardCorrupted()
+        if rc == N.RS_E_TOO_FEW_SHARDS:
+            raise ErrTooFewShards()
+        if rc != N.RS_OK:
+            raise _wrapped(rc, "decode_session finish")
+        return list(counts)
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            N.lib.rs_session_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ObjectDecodeSession:
+    """Codec.decode_session's session: a DecodeSession whose result is the joined, trimmed object.
+    A delivered data shard is kept where it belongs in the object as it is fed; finish() points
+    the session's destinations at the gaps, the data shards that were not fetched."""
+
+    def __init__(self, session: DecodeSession, original_size: int):
+        self.session = session
+        self.size = int(original_size)
+        self.out = bytearray(self.size)
+        self._fed: List[int] = []
+
+    def _span(self, i: int):
+        S = self.session.S
+        return min(i * S, self.size), min((i + 1) * S, self.size)
+
+    def feed(self, idx: int, shard) -> None:
+        self.session.feed(idx, shard)
+        if idx < self.session.k:
+            a, b = self._span(idx)
+            self.out[a:b] = memoryview(shard).cast("B")[:b - a]
+            self._fed.append(idx)
+
+    def peek(self, idx: int, length: Optional[int] = None) -> bytearray:
+        return self.session.peek(idx, length)
+
+    def finish(self) -> bytearray:
+        """The object's original_size bytes. Errors as DecodeSession.finish; with repair=True a
+        delivered data shard the compared shards prove corrupt is restored in the object too."""
+        s = self.session
+        n, view = s.k + s.m, memoryview(self.out)
+        dst: List = [None] * n
+        lens = [0] * n
+        for i in range(n):
+            if s.want[i]:
+                a, b = self._span(i)
+                lens[i] = b - a
+                dst[i] = view[a:b] if b > a else None
+        fix = None
+        if s.repair:
+            fix = [bytearray(s.S) if i in self._fed else None for i in range(n)]
+        self.counts = s.finish(dst, lens, fix)
+        for i in self._fed if s.repair else ():
+            if self.counts[i]:
+                a, b = self._span(i)
+                np.frombuffer(view[a:b], dtype=np.uint8)[:] ^= np.frombuffer(fix[i], dtype=np.uint8)[:b - a]
+        return self.out
+
+    def close(self) -> None:
+        self.session.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def verify(shards: List, k: int, m: int, context: Optional[N.Context] = None) -> bool:

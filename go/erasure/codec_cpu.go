@@ -5,6 +5,7 @@ package erasure
 import (
 	"errors"
 	"fmt"
+	"sync"
 )
 
 // Builds without the GPU codec (the default CGO_ENABLED=0 release builds,
@@ -201,6 +202,46 @@ func (c *Codec) DecodeRepairBatch(dst, check, fix [][][]byte, expectInput [][]bo
 	}
 	return counts, errs
 }
+
+// DecodeSession (DESIGN.md §5.17) on builds without the GPU codec: it collects the shards as
+// they are fed and decodes them at Finish.
+type DecodeSession struct {
+	c       *Codec
+	profile ErasureProfile
+	size    int64
+	mu      sync.Mutex
+	fed     [][]byte
+}
+
+// DecodeSession opens a session; expect, compare and repair are the GPU codec's to use.
+func (c *Codec) DecodeSession(profile ErasureProfile, originalSize int64, expect, compare []int, repair bool) (*DecodeSession, error) {
+	if profile.DataShards < 1 || profile.ParityShards < 1 {
+		return nil, ErrInvalidProfile
+	}
+	return &DecodeSession{c: c, profile: profile, size: originalSize,
+		fed: make([][]byte, profile.DataShards+profile.ParityShards)}, nil
+}
+
+// Feed keeps a copy of shard idx.
+func (s *DecodeSession) Feed(idx int, shard []byte) error {
+	if idx < 0 || idx >= len(s.fed) {
+		return fmt.Errorf("erasure: shard index %d of %d", idx, len(s.fed))
+	}
+	s.mu.Lock()
+	defer s.mu.Unlock()
+	s.fed[idx] = append([]byte(nil), shard...)
+	return nil
+}
+
+// Finish is Decode of the shards fed so far.
+func (s *DecodeSession) Finish() ([]byte, error) {
+	s.mu.Lock()
+	defer s.mu.Unlock()
+	return s.c.Decode(s.fed, s.profile, s.size)
+}
+
+// Close frees nothing here.
+func (s *DecodeSession) Close() {}
 
 // ErrLocateUnavailable is what Locate reports on builds without the GPU codec: the CPU codec
 // has no locator (the reference finds a bad shard by its checksum, manager.go:250-320).

@@ -1308,6 +1308,183 @@ func (c *Codec) DecodeRepairBatch(dst, check, fix [][][]byte, expectInput [][]bo
 	return counts, errs
 }
 
+// ---- decode sessions (DESIGN.md §5.17) --------------------------------------------------------
+
+// DecodeSession is a progressive decode of one object whose rows stay on the device
+// (rs_session_open): Feed each shard as RetrieveFile's fetches deliver it, from any goroutine
+// and in any order, then Finish for the joined, trimmed object. On a profile or a machine the
+// GPU codec does not serve it collects the shards and decodes at Finish. Like the rest of this
+// package it has never been compiled where the library is developed. Not in the reference API.
+type DecodeSession struct {
+	c       *Codec
+	h       *C.rs_session
+	profile ErasureProfile
+	size    int64
+	S       int
+	want    []bool
+	repair  bool
+	mu      sync.Mutex
+	out     []byte
+	fed     [][]byte // the CPU form's shards; the GPU form's delivered data shards' indices are in out
+	gotData []bool
+}
+
+// DecodeSession opens a session for an object of originalSize bytes: expect names the k shard
+// indices that will be fed, compare the indices fetched beyond them, which Finish checks against
+// them (with repair: and uses to repair a corrupt one, given three or more).
+func (c *Codec) DecodeSession(profile ErasureProfile, originalSize int64, expect, compare []int, repair bool) (*DecodeSession, error) {
+	k, m := profile.DataShards, profile.ParityShards
+	if k < 1 || m < 1 {
+		return nil, ErrInvalidProfile
+	}
+	n := k + m
+	if originalSize < 0 {
+		originalSize = 0
+	}
+	S := int((originalSize + int64(k) - 1) / int64(k))
+	if S < 1 {
+		S = 1
+	}
+	s := &DecodeSession{c: c, profile: profile, size: originalSize, S: S, repair: repair,
+		want: make([]bool, n), out: make([]byte, originalSize), fed: make([][]byte, n), gotData: make([]bool, n)}
+	e, w, cm := make([]C.uint8_t, n), make([]C.uint8_t, n), make([]C.uint8_t, n)
+	for _, i := range expect {
+		if i < 0 || i >= n {
+			return nil, reedsolomon.ErrInvalidShardIdx
+		}
+		e[i] = 1
+	}
+	for _, i := range compare {
+		if i < 0 || i >= n {
+			return nil, reedsolomon.ErrInvalidShardIdx
+		}
+		cm[i] = 1
+	}
+	for i := 0; i < k; i++ {
+		if e[i] == 0 && cm[i] == 0 {
+			w[i] = 1
+			s.want[i] = true
+		}
+	}
+	if n > 256 || device() == nil {
+		return s, nil
+	}
+	flags := C.uint(C.RS_SESSION_CHECK)
+	if repair {
+		flags = C.RS_SESSION_REPAIR
+	}
+	if rc := C.rs_session_open(gpuCtx, C.int(k), C.int(m), C.size_t(S), &e[0], &w[0], &cm[0], flags, &s.h); rc != C.RS_OK {
+		return nil, decodeIdxErr(rc)
+	}
+	return s, nil
+}
+
+// span is where data shard i lies in the object: [a, b), empty for a shard that is all padding.
+func (s *DecodeSession) span(i int) (int64, int64) {
+	a, b := int64(i)*int64(s.S), int64(i+1)*int64(s.S)
+	if a > s.size {
+		a = s.size
+	}
+	if b > s.size {
+		b = s.size
+	}
+	return a, b
+}
+
+// Feed delivers shard idx, once; it returns when shard may be reused. A delivered data shard is
+// kept where it belongs in the object.
+func (s *DecodeSession) Feed(idx int, shard []byte) error {
+	n := s.profile.DataShards + s.profile.ParityShards
+	if idx < 0 || idx >= n {
+		return reedsolomon.ErrInvalidShardIdx
+	}
+	if len(shard) != s.S {
+		return fmt.Errorf("erasure: failed to decode: %w", reedsolomon.ErrShardSize)
+	}
+	if s.h == nil {
+		s.mu.Lock()
+		defer s.mu.Unlock()
+		s.fed[idx] = append([]byte(nil), shard...)
+		return nil
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&shard[0])
+	if rc := C.rs_session_feed(s.h, C.int(idx), (*C.uint8_t)(unsafe.Pointer(&shard[0]))); rc != C.RS_OK {
+		return decodeIdxErr(rc)
+	}
+	if idx < s.profile.DataShards {
+		a, b := s.span(idx)
+		s.mu.Lock()
+		copy(s.out[a:b], shard)
+		s.gotData[idx] = true
+		s.mu.Unlock()
+	}
+	return nil
+}
+
+// Finish closes the decode and returns the object. ErrShardCorrupted comes with the object's
+// bytes filled in all the same, as Decode delivers them before Verify fails; before the k-th
+// expected shard it is ErrTooFewShards and the session stays usable.
+func (s *DecodeSession) Finish() ([]byte, error) {
+	k, m := s.profile.DataShards, s.profile.ParityShards
+	n := k + m
+	if s.h == nil {
+		s.mu.Lock()
+		defer s.mu.Unlock()
+		return s.c.Decode(s.fed, s.profile, s.size)
+	}
+	dst, fix := newCArray(n), newCArray(n)
+	defer dst.free()
+	defer fix.free()
+	lens := make([]C.size_t, n)
+	counts := make([]C.uint64_t, n+1)
+	fixRows := make([][]byte, n)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for i := 0; i < k; i++ {
+		a, b := s.span(i)
+		if s.want[i] && b > a {
+			pin.Pin(&s.out[a])
+			dst.set(i, unsafe.Pointer(&s.out[a]))
+			lens[i] = C.size_t(b - a)
+		}
+		if s.repair && s.gotData[i] {
+			fixRows[i] = make([]byte, s.S)
+			pin.Pin(&fixRows[i][0])
+			fix.set(i, unsafe.Pointer(&fixRows[i][0]))
+		}
+	}
+	var fixp **C.uint8_t
+	if s.repair {
+		fixp = fix.at(0)
+	}
+	rc := C.rs_session_finish(s.h, dst.at(0), &lens[0], fixp, &counts[0])
+	if rc != C.RS_OK && rc != C.RS_E_CORRUPT {
+		return nil, decodeIdxErr(rc)
+	}
+	for i := 0; i < k; i++ { // a delivered data shard the compared shards prove corrupt: restored
+		if fixRows[i] != nil && counts[i] != 0 {
+			a, b := s.span(i)
+			for x := range s.out[a:b] {
+				s.out[a+int64(x)] ^= fixRows[i][x]
+			}
+		}
+	}
+	if rc == C.RS_E_CORRUPT {
+		return s.out, ErrShardCorrupted
+	}
+	return s.out, nil
+}
+
+// Close frees the session.
+func (s *DecodeSession) Close() {
+	if s.h != nil {
+		C.rs_session_close(s.h)
+		s.h = nil
+	}
+}
+
 // Overwrite replaces bytes [offset, offset+len(data)) of the object whose n shards these are
 // (Encode's layout: object byte x in data shard x/S at column x%S) and brings the parity up to
 // date (rs_codec_overwrite): only the affected parity columns are read and rewritten, through

@@ -818,6 +818,110 @@ int rs_plan_create_decode_repair(rs_ctx* ctx, int device, int k, int m, int batc
                                  uint8_t* const* check, uint8_t* const* fix, unsigned flags,
                                  rs_plan** out);
 
+/* ---- feed objects: one shard per launch, rows resident ---------------
+ * A decode-check plan fixes its delivered set when it is created, so a download that receives its
+ * shards one at a time needs a plan per arrival. A feed object fixes only what is known before the
+ * first shard lands -- one stripe of S-byte shards, its k expected shards, its wanted and its
+ * compared shards -- and every launch then delivers one shard, named by argument:
+ *   expect  (flags)    k+m entries, exactly k set: fewer is RS_E_TOO_FEW_SHARDS, more RS_E_ARG.
+ *   dst     (pointers) k+m entries, non-NULL = shard i is wanted; not at an expected index.
+ *   check   (pointers) k+m entries, non-NULL = shard i is compared; not at an expected index and
+ *                      not where dst is given.
+ * dst[i] and check[i] name S-byte device accumulators owned by the caller, under the overlap
+ * contract of decode-check plans: no byte of one overlaps another or any source. The rows are the
+ * compared indices in ascending order, then the wanted indices in ascending order -- a
+ * decode-repair plan's order, so a final decode-check or decode-repair plan with nothing delivered
+ * can take the same pointers and close the decode. At most 16 rows (RS_E_UNSUPPORTED above).
+ * rs_feed_launch(feed, idx, src, flags, stream) delivers shard idx, which must be expected or
+ * compared (RS_E_ARG otherwise; also for a NULL feed or src or a flag bit other than
+ * RS_DECODE_IDX_STORE). src is S bytes the device can read -- device memory or host-coherent
+ * pinned memory -- at any alignment. Its effect on every row is exactly that of a non-final
+ * decode-check plan with that one input, with C = E[rows] * inv(E[V]) as there:
+ *     expected idx:  row (^)= C[row][idx] * src   for every row
+ *     compared idx:  check[idx] (^)= src          and no other row is touched
+ * with ^= for flags 0 and = under RS_DECODE_IDX_STORE. A store launch reads no row and writes
+ * every row; rows other than a compared shard's own then receive zeros. So the first launch of a
+ * decode stores and the later ones merge, in any order of arrival.
+ * A MERGE LAUNCH IS NOT IDEMPOTENT: it adds the terms to the rows' current bytes, and a second
+ * launch adds them again, which restores what the first started from. A store launch is
+ * idempotent.
+ * The launch only enqueues one kernel on `stream`: no allocation, no copy, no sync;
+ * graph-capturable (the arguments go by value). The coefficient tables are built once, in
+ * rs_feed_create, with one k x k inversion, and uploaded once.
+ * Errors of rs_feed_create, in this order: the profile (RS_E_INVALID_PROFILE, RS_E_UNSUPPORTED);
+ * a NULL ctx, expect, dst, check or out (RS_E_ARG); the expect count; a misplaced pointer -- a dst
+ * or a check at an expected index, a check and a dst at one index (RS_E_ARG); more than 16 rows
+ * (RS_E_UNSUPPORTED); S == 0 (RS_E_NO_DATA); then an unknown device (RS_E_ARG). Each check runs
+ * before the next. Nothing is created on an error. */
+typedef struct rs_feed rs_feed;
+int rs_feed_create(rs_ctx* ctx, int device, int k, int m, size_t S, const uint8_t* expect,
+                   uint8_t* const* dst, uint8_t* const* check, rs_feed** out);
+int rs_feed_launch(rs_feed* feed, int idx, const uint8_t* src, unsigned flags, void* stream);
+void rs_feed_destroy(rs_feed* feed);
+
+/* ---- decode sessions: shards fed from host memory as they land -------
+ * The host route over a feed object, for a download that receives its shards one at a time in
+ * host memory. rs_decode_check keeps nothing on the device between calls: every arrival uploads
+ * and downloads every row. A session keeps one stripe's rows -- the syndrome accumulators of the
+ * compared shards and the wanted shards -- on one device from open to close, so an arrival moves
+ * its own S bytes and nothing else, and builds its tables once.
+ * rs_session_open: expect, want and compare are k+m flags each (nonzero = set) under
+ *   rs_feed_create's rules: exactly k expected, a wanted or compared index never expected, never
+ *   both, at most 16 of them together. flags: RS_SESSION_CHECK (finish flags a mismatch) or
+ *   RS_SESSION_REPAIR (finish also repairs it). Allocates the rows (zeroed, at a pitch of S rounded
+ *   up to 256), a stream, a ring of CALLFS_RS_SESSION_SLOTS source slots (default 3) and the feed
+ *   object, on the context's next device in round-robin order. A session holds none of the
+ *   context's lanes: a long download does not starve the other host calls. Errors in
+ *   rs_feed_create's order, an unknown flag bit counting with the NULL arrays.
+ * rs_session_feed: delivers shard idx, expected or compared, from S bytes of host memory. Calls
+ *   on one session are serialised by a mutex and may come from any thread, in any order of
+ *   arrival; the first feed stores, the later ones merge. It returns once `shard` may be reused,
+ *   and blocks only while every slot of the ring holds a shard whose launch has not finished. A
+ *   second feed of one index, an index that is neither expected nor compared, and any feed after
+ *   finish are RS_E_ARG. Two routes into the one kernel, chosen by CALLFS_RS_SESSION_INPLACE_MAX
+ *   (bytes per shard, read at open; default 2 MiB):
+ *     in place  up to that size: the shard is copied into a host-coherent slot and the kernel
+ *               reads it over PCIe; a shard inside an rs_host_alloc buffer is read where it lies,
+ *               with no host copy at all, and the call then returns when the kernel has read it;
+ *     staged    above it: one H2D from staging into a device slot, then the launch.
+ *   rs_host_counters per feed: calls 1, launches 1, copies 0 in place and 1 staged.
+ * rs_session_peek: waits for the feeds enqueued so far and copies the first len <= S bytes of
+ *   the accumulator of a wanted or compared index (RS_E_ARG for any other): the partial result.
+ *   Before the first feed the rows read zero.
+ * rs_session_finish: RS_E_TOO_FEW_SHARDS while fewer than k expected shards have been fed; the
+ *   session stays open and usable. Otherwise the decode is closed: compared shards that were
+ *   never fed are left out (check = NULL in the final plan); when a compared shard was delivered
+ *   one final plan runs over the resident rows with nothing delivered -- under RS_SESSION_CHECK
+ *   rs_plan_create_decode_check with RS_DECODE_CHECK_FINAL and without the wanted rows, under
+ *   RS_SESSION_REPAIR rs_plan_create_decode_repair -- and then the wanted rows are copied out.
+ *     dst      k+m pointers: dst[i] of a wanted index receives dst_lens[i] <= S bytes (dst_lens
+ *              NULL: S bytes; dst[i] NULL: skipped), so a caller joins and trims by pointing dst
+ *              into its object buffer. A destination inside an rs_host_alloc buffer takes its D2H
+ *              directly; the others share one D2H of the wanted rows' span.
+ *     fix      RS_SESSION_REPAIR: k+m pointers or NULL; fix[i] is allowed at an expected index and
+ *              at a compared index that was fed (RS_E_ARG elsewhere, and under RS_SESSION_CHECK).
+ *              XOR in place, as rs_decode_repair: the device fix rows are allocated and zeroed
+ *              here, and a row comes back, to be XORed into fix[i], only when the status word is
+ *              set and the shard was blamed.
+ *     counts   NULL or k+m+1 words as rs_plan_blame fills them (zero under RS_SESSION_CHECK).
+ *   The dst bytes, the fix bytes, counts and the return value are bit for bit those of one
+ *   rs_decode_check call with RS_DECODE_CHECK_FINAL | RS_DECODE_IDX_STORE (RS_SESSION_REPAIR:
+ *   one rs_decode_repair call with RS_DECODE_IDX_STORE) given all delivered shards at once:
+ *   RS_E_CORRUPT still delivers the wanted rows. After a finish that ran, further feeds and
+ *   finishes are RS_E_ARG; peek still works.
+ * rs_session_close waits for the session's stream and frees everything. */
+#define RS_SESSION_CHECK 0u
+#define RS_SESSION_REPAIR 1u
+typedef struct rs_session rs_session;
+int rs_session_open(rs_ctx* ctx, int k, int m, size_t S, const uint8_t* expect,
+                    const uint8_t* want, const uint8_t* compare, unsigned flags,
+                    rs_session** out);
+int rs_session_feed(rs_session* session, int idx, const uint8_t* shard);
+int rs_session_peek(rs_session* session, int idx, uint8_t* out, size_t len);
+int rs_session_finish(rs_session* session, uint8_t* const* dst, const size_t* dst_lens,
+                      uint8_t* const* fix, uint64_t* counts);
+void rs_session_close(rs_session* session);
+
 /* ---- locate plans: which shard is corrupt --------------------------
  * Not in the reference API. Every other plan tells that a stripe's compared shards mismatch; a
  * locate plan tells where. sizes, present and shards as for rs_plan_create_ragged, but present

@@ -541,6 +541,19 @@ shift
 timeout -k 10 400 python3 -u tools/decode_repair_bench.py "$@" | tee $O/decode_repair_bench.jsonl || exit $?
 }
 
+# Feed launches and decode sessions against what they replace (tools/session_bench.py, DESIGN.md
+# §5.17), RS(10,4): (a) rs_feed_launch against the decode-idx plan launch over the same buffers,
+# (b) rs_session_feed per arrival on both routes against the rs_decode_check host call, (c) the
+# last arrival plus finish against one-shot rs_codec_decode. One JSON line per section and size on
+# stdout and in <out dir>/session_bench.jsonl (the lines kept in profiles/r34/session/).
+# Usage: bash tools/jobs.sh session_bench <out dir> [session_bench.py args]
+job_session_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+O=${1:-session_out}; mkdir -p "$O" || exit $?
+shift
+timeout -k 10 500 python3 -u tools/session_bench.py "$@" | tee $O/session_bench.jsonl || exit $?
+}
+
 # Locate plans against the compare-only plan of the same batch and against batched SHA-256 of
 # every shard (tools/locate_bench.py): RS(10,4) x 256 stripes of 64 KiB..4 MiB
 # and RS(16,4) x 4,096 stripes of 1..16 KiB, clean and with one shard of every stripe wholly
