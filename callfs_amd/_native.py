@@ -182,6 +182,14 @@ SIGNATURES = {
     "rs_session_finish": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp),
                                  ctypes.POINTER(ctypes.c_uint64)]),
     "rs_session_close": (None, [_vp]),
+    "rs_absorb_create": (_int, [_vp, _int, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rs_absorb_launch": (_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp]),
+    "rs_absorb_destroy": (None, [_vp]),
+    "rs_encode_session_open": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp)]),
+    "rs_encode_session_feed": (_int, [_vp, ctypes.c_uint64, _vp, _sz]),
+    "rs_encode_session_peek": (_int, [_vp, _int, _vp, _sz]),
+    "rs_encode_session_finish": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz)]),
+    "rs_encode_session_close": (None, [_vp]),
     "rs_decode_check": (_int, [_vp, _int, _int, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u8p,
                                ctypes.POINTER(_vp), ctypes.c_uint]),
     "rs_decode_check_batch": (_int, [_vp, _int, _int, _int, ctypes.POINTER(_sz), ctypes.POINTER(_vp),

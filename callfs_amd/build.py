@@ -27,7 +27,7 @@ LIB_AB = os.path.join(os.path.dirname(HERE), "build", "ab", "libcallfs_rs_ab.so"
 # kernel's speed depends on its waves per SIMD.
 RESOURCES = os.path.join(HERE, "kernel_resources.json")
 SOURCES = ["rs_kernels.hip", "rs_mixed.hip", "sha256.hip", "rs_context.cpp", "rs_host.cpp", "rs_plan.cpp",
-           "rs_session.cpp", "bitslice.cpp"]
+           "rs_session.cpp", "rs_encode_session.cpp", "bitslice.cpp"]
 # every header in csrc/ (a new one cannot be forgotten) and the C ABI's
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [
     os.path.join("..", "..", "include", "callfs_rs.h")]

@@ -6,6 +6,7 @@
 #include <vector>
 #include <cstdint>
 
+#include "absorb_tables.hpp"
 #include "order_code.hpp"
 
 // 1: also build the measurement-only kernel forms (the 6-bit triple lookups, the 64-vector
@@ -395,6 +396,37 @@ constexpr uint32_t kFeedTileBytes = 4096;
 // grid of ceil(S / kFeedTileBytes) blocks: one dispatch, no allocation, no copy, no sync. R == 0
 // enqueues nothing. A merge launch is NOT idempotent; a store launch is.
 hipError_t launch_feed(const FeedArgs& x, bool store, hipStream_t stream, LaunchEvents ev = {});
+
+// ---- absorb launches (rs_absorb.hpp in rs_mixed.hip) ----------------------
+// One range [off, off + len) of an object's body into the object's R <= 16 resident parity rows:
+//   row[j][c] ^= P[j][i] * src[i * S + c - off]   for every byte (shard i, column c) of the range
+// and nothing else. The kernel's second argument: the source, the range's first byte, the plan's
+// intervals and block counts and, for instances of up to 8 rows, the row pointers, all by value
+// (the 16-row instance reads the pointers from AbsorbArgs::row_tab).
+template <int RT>
+struct AbsorbRows {
+  const uint8_t* src;
+  uint64_t off;
+  AbsorbInterval iv[kAbsorbMaxIntervals];
+  uint32_t end[kAbsorbMaxIntervals];
+  uint8_t* row[RT > 8 ? 1 : RT];
+};
+
+struct AbsorbArgs {
+  const uint8_t* src;       // len bytes the device can read, any alignment: body byte off + b at src[b]
+  const uint32_t* tabs;     // device memory: the arena, [K][R][5] v_perm tables
+  uint8_t* const* row_tab;  // device memory: the R row pointers
+  uint8_t* const* rows;     // host memory: the same R pointers
+  uint64_t S, off, len;
+  int K, R;
+  AbsorbPlan plan;          // absorb_plan(K, S, off, len)
+};
+
+// Enqueues rs_absorb in the smallest instance that holds R rows, on a grid of the plan's blocks
+// (the sum of the intervals' ceil(columns / kFeedTileBytes)): one dispatch, no allocation, no
+// copy, no sync. The plan is checked against K, S, off and len before anything is enqueued. NOT
+// idempotent.
+hipError_t launch_absorb(const AbsorbArgs& x, hipStream_t stream, LaunchEvents ev = {});
 
 // ---- locate launches (rs_mixed.hip) --------------------------------------
 // A required launch group in which every row is compared and none written, and a mismatching

@@ -17,6 +17,8 @@
 // mismatching column from their check rows and repair the wanted rows before storing them.
 // Feed launches (§5.17, rs_feed.hpp) deliver one shard of one stripe into its resident rows: the
 // v_perm form, selected by argument, with no tile map and no LDS.
+// Absorb launches (§5.18, rs_absorb.hpp) fold one byte range of an object's body into its resident
+// parity rows: the same form with a loop over the shards the range covers at a column.
 #include <algorithm>
 #include <array>
 
@@ -27,6 +29,7 @@
 #include "locate_tables.hpp"
 #include "rs_apply.hpp"
 #include "rs_check.hpp"
+#include "rs_absorb.hpp"
 #include "rs_feed.hpp"
 #include "rs_merge.hpp"
 #include "rs_update.hpp"
@@ -645,6 +648,21 @@ void dispatch_feed(const ApplyArgs& a, const FeedArgs& x, bool store, uint32_t g
   dispatch(kFeed<RT>[store ? 1 : 0], dim3(grid), dim3(dev::kFeedBlock), 0, stream, ev, true, true, a, rows);
 }
 
+// Absorb launches (rs_absorb.hpp)
+template <int RT>
+void dispatch_absorb(const ApplyArgs& a, const AbsorbArgs& x, hipStream_t stream, const LaunchEvents& ev) {
+  AbsorbRows<RT> rows{};
+  rows.src = x.src;
+  rows.off = x.off;
+  for (int q = 0; q < kAbsorbMaxIntervals; ++q) {
+    rows.iv[q] = x.plan.iv[q];
+    rows.end[q] = x.plan.end[q];
+  }
+  if constexpr (RT <= 8)
+    for (int r = 0; r < a.R; ++r) rows.row[r] = x.rows[r];
+  dispatch(&dev::rs_absorb<RT>, dim3(x.plan.grid()), dim3(dev::kFeedBlock), 0, stream, ev, true, true, a, rows);
+}
+
 // 16-row groups with more than 64 KiB of tables (k > 128) need the dynamic-LDS opt-in, a
 // per-device attribute (dispatch.hpp DeviceOnce), keyed by the 16-row instance it is set on
 enum class WideLds { kMixed, kRagged, kRaggedSome, kUpdate, kUpdatePair, kLocate, kLocate2, kCorrect,
@@ -798,6 +816,40 @@ hipError_t launch_feed(const FeedArgs& x, bool store, hipStream_t stream, Launch
   if (x.R > 8) dispatch_feed<16>(a, x, store, static_cast<uint32_t>(grid), stream, ev);
   else if (x.R > 4) dispatch_feed<8>(a, x, store, static_cast<uint32_t>(grid), stream, ev);
   else dispatch_feed<4>(a, x, store, static_cast<uint32_t>(grid), stream, ev);
+  return hipGetLastError();
+}
+
+hipError_t launch_absorb(const AbsorbArgs& x, hipStream_t stream, LaunchEvents ev) {
+  if (x.R < 1 || x.R > kMaxRowsPerLaunch || x.K < 1 || x.K > kMaxK || !x.src || !x.tabs || !x.row_tab || !x.rows ||
+      x.S == 0 || x.len == 0)
+    return hipErrorInvalidValue;
+  // the plan is the range's: every interval inside [0, S) x [0, K) with its bytes inside the range,
+  // and the block counts those of its columns
+  const AbsorbPlan& p = x.plan;
+  if (p.n < 1 || p.n > kAbsorbMaxIntervals) return hipErrorInvalidValue;
+  uint64_t blocks = 0;
+  for (int q = 0; q < kAbsorbMaxIntervals; ++q) {
+    if (q < p.n) {
+      const AbsorbInterval& v = p.iv[q];
+      if (v.col0 >= v.col1 || v.col1 > x.S || v.shard0 < 0 || v.shard0 > v.shard1 || v.shard1 >= x.K ||
+          static_cast<uint64_t>(v.shard0) * x.S + v.col0 < x.off ||
+          static_cast<uint64_t>(v.shard1) * x.S + v.col1 > x.off + x.len)
+        return hipErrorInvalidValue;
+      blocks += (v.col1 - v.col0 + kFeedTileBytes - 1) / kFeedTileBytes;
+    }
+    if (blocks > 0x7fffffffull || p.end[q] != blocks) return hipErrorInvalidValue;
+  }
+  ApplyArgs a{};
+  a.out_tab = x.row_tab;
+  a.tabs = x.tabs;
+  a.S = x.S;
+  a.nvec = x.S / 16;
+  a.K = x.K;
+  a.R = x.R;
+  a.batch = 1;
+  if (x.R > 8) dispatch_absorb<16>(a, x, stream, ev);
+  else if (x.R > 4) dispatch_absorb<8>(a, x, stream, ev);
+  else dispatch_absorb<4>(a, x, stream, ev);
   return hipGetLastError();
 }
 

@@ -131,6 +131,22 @@ struct rs_feed {
   }
 };
 
+// An absorb object (rs_absorb_create): absorb_tables.hpp's arena in one device
+// buffer behind the table of row pointers, uploaded once. A launch plans its range on the host
+// and passes the plan by value.
+struct rs_absorb {
+  int device = 0;
+  size_t S = 0;
+  AbsorbTables t;
+  std::vector<uint8_t*> rows;  // parity row j
+  DevBuf dmeta;                // [kAbsorbMaxRows] row pointers, then the arena
+  std::mutex mu;               // guards scratch
+  std::vector<OverwriteInterval> scratch;
+  ~rs_absorb() {
+    if (dmeta.p) (void)hipSetDevice(device);  // the buffer is freed on the object's device
+  }
+};
+
 namespace {
 
 // ---- what differs between uniform, mixed and ragged plans -------------------------------
@@ -1229,6 +1245,66 @@ int rs_feed_launch(rs_feed* feed, int idx, const uint8_t* src, unsigned flags, v
 void rs_feed_destroy(rs_feed* feed) {
   DeviceGuard dg;
   delete feed;
+}
+
+// ---- absorb objects ---------------------------------------------------------
+
+int rs_absorb_create(rs_ctx* ctx, int device, int k, int m, size_t S, uint8_t* const* rows, rs_absorb** out) {
+  DeviceGuard dg;
+  if (const int rc = check_profile(k, m)) return rc;
+  if (!ctx || !rows || !out) return RS_E_ARG;
+  *out = nullptr;
+  if (m <= kAbsorbMaxRows)
+    for (int j = 0; j < m; ++j)
+      if (!rows[j]) return RS_E_ARG;
+  auto ab = std::make_unique<rs_absorb>();
+  switch (build_absorb_tables(k, m, S, ab->t)) {
+    case AbsorbError::kOk: break;
+    case AbsorbError::kUnsupported: return RS_E_UNSUPPORTED;
+    case AbsorbError::kNoData: return RS_E_NO_DATA;
+    case AbsorbError::kSingular: return RS_E_SINGULAR;
+  }
+  if (!ctx->device(device)) return RS_E_ARG;
+  ab->device = device;
+  ab->S = S;
+  ab->rows.assign(rows, rows + m);
+  ab->scratch.reserve(kAbsorbMaxIntervals);
+  constexpr size_t kRowTabBytes = kAbsorbMaxRows * sizeof(uint8_t*);
+  std::vector<uint8_t> h(kRowTabBytes + ab->t.arena.size() * sizeof(uint32_t), 0);
+  std::memcpy(h.data(), ab->rows.data(), ab->rows.size() * sizeof(uint8_t*));
+  std::memcpy(h.data() + kRowTabBytes, ab->t.arena.data(), ab->t.arena.size() * sizeof(uint32_t));
+  if (const int rc = upload(ab->dmeta, device, h.data(), h.size())) return rc;
+  *out = ab.release();
+  return RS_OK;
+}
+
+int rs_absorb_launch(rs_absorb* ab, uint64_t off, uint64_t len, const uint8_t* src, void* stream) {
+  DeviceGuard dg;
+  if (!ab || !src) return RS_E_ARG;
+  AbsorbArgs x{};
+  {
+    // the plan's scratch vector is the object's: launches of one object may come from any thread
+    std::lock_guard<std::mutex> g(ab->mu);
+    if (!absorb_plan(ab->t.k, ab->S, off, len, x.plan, ab->scratch)) return RS_E_ARG;
+  }
+  HIPCHK(hipSetDevice(ab->device));
+  auto* d = static_cast<uint8_t*>(ab->dmeta.p);
+  x.src = src;
+  x.tabs = reinterpret_cast<const uint32_t*>(d + kAbsorbMaxRows * sizeof(uint8_t*));
+  x.row_tab = reinterpret_cast<uint8_t* const*>(d);
+  x.rows = ab->rows.data();
+  x.S = ab->S;
+  x.off = off;
+  x.len = len;
+  x.K = ab->t.k;
+  x.R = ab->t.m;
+  HIPCHK(launch_absorb(x, static_cast<hipStream_t>(stream)));
+  return RS_OK;
+}
+
+void rs_absorb_destroy(rs_absorb* ab) {
+  DeviceGuard dg;
+  delete ab;
 }
 
 // ---- one-shot device calls ------------------------------------------------------------------------

@@ -691,6 +691,47 @@ class Feed:
             pass
 
 
+class Absorb:
+    """rs_absorb_create / rs_absorb_launch: the m parity rows of one object of k
+    data shards of S bytes, resident on the device; every launch folds one byte range of the
+    object's body in. rows: m device pointers to S-byte accumulators, zero before the first
+    launch. At most 16 rows. The tables are built and uploaded once, here."""
+
+    def __init__(self, k: int, m: int, S: int, rows, device: int = 0,
+                 context: Optional[N.Context] = None):
+        self.ctx = context or N.default_context()
+        if len(rows) != m:
+            raise ValueError("need m row pointers")
+        self.k, self.m, self.S, self.device = k, m, S, device
+        self.handle = None
+        arr = (ctypes.c_void_p * m)(*[int(x) or None for x in rows])
+        h = ctypes.c_void_p()
+        N.check(N.lib.rs_absorb_create(self.ctx.handle, device, k, m, S, arr, ctypes.byref(h)),
+                "rs_absorb_create")
+        self.handle = h
+
+    def launch(self, off: int, length: int, src: int,
+               stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Folds body bytes [off, off + length) in from `src`, the address of `length` bytes the
+        device can read, at any alignment: row j ^= P[j][i] * byte for every byte (shard i, column
+        c) of the range, at column c. Only enqueues one kernel. NOT idempotent: every body byte
+        is fed exactly once."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        N.check(N.lib.rs_absorb_launch(self.handle, off, length, ctypes.c_void_p(int(src)),
+                                       ctypes.c_void_p(s.cuda_stream)), "rs_absorb_launch")
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            N.lib.rs_absorb_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class HashPlan:
     """Batched SHA-256 (erasure.ShardChecksum, codec.go:81-84) of device-resident
     messages: rs_sha256_plan_* over `pointers`/`lengths` (device addresses, bytes)."""

@@ -285,6 +285,20 @@ class Codec:
                                 [i in c for i in range(n)], repair, self.context)
         return ObjectDecodeSession(session, size)
 
+    def encode_session(self, profile: ErasureProfile, size: int) -> "ObjectEncodeSession":
+        """A progressive encode for an upload whose body arrives in pieces,
+        Manager.StoreFile's case with the request body read as it comes: feed(off, data) or
+        write(data) each piece, from any thread, every byte exactly once; finish() returns the
+        shards, bit for bit what encode returns for the whole body. Errors as encode."""
+        k, m = profile.data_shards, profile.parity_shards
+        if k < 1 or m < 1:
+            raise ErrInvalidProfile()
+        if int(size) <= 0:
+            raise ErrShortData(f"erasure: failed to split data: {ErrShortData.text}")
+        if k + m > 256:
+            raise _wrapped(N.RS_E_UNSUPPORTED, "erasure: failed to create encoder")
+        return ObjectEncodeSession(EncodeSession(k, m, int(size), self.context))
+
     def decode_heal(self, shards: List, profile: ErasureProfile,
                     original_size: int, max_errors: int = 1) -> Tuple[bytearray, List[int]]:
         """rs_codec_decode_heal: decode() that repairs what it can where
@@ -1116,6 +1130,131 @@ class ObjectDecodeSession:
                 a, b = self._span(i)
                 np.frombuffer(view[a:b], dtype=np.uint8)[:] ^= np.frombuffer(fix[i], dtype=np.uint8)[:b - a]
         return self.out
+
+    def close(self) -> None:
+        self.session.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class EncodeSession:
+    """rs_encode_session_open: a progressive encode of one object of `size` bytes
+    whose m parity rows stay on the device. feed(off, data) folds body bytes [off, off + len(data))
+    in, from any thread and in any order, every byte exactly once; peek() reads a row's partial
+    result; finish() returns the m parity shards once [0, size) is covered. A context manager:
+    leaving it closes the session."""
+
+    def __init__(self, k: int, m: int, size: int, context: Optional[N.Context] = None):
+        self.ctx = context or N.default_context()
+        self.k, self.m, self.size = k, m, int(size)
+        self.S = (self.size + k - 1) // k if k >= 1 else 0
+        self.handle = None
+        h = ctypes.c_void_p()
+        rc = N.lib.rs_encode_session_open(self.ctx.handle, k, m, max(self.size, 0), ctypes.byref(h))
+        if rc == N.RS_E_ARG:
+            raise ErrInvalidInput()
+        if rc == N.RS_E_INVALID_PROFILE:
+            raise ErrInvalidProfile()
+        if rc != N.RS_OK:
+            raise _wrapped(rc, "encode_session")
+        self.handle = h
+
+    def feed(self, off: int, data) -> None:
+        """Folds body bytes [off, off + len(data)) in. Returns when `data` may be reused. A range
+        that is empty, reaches past the object, overlaps anything fed before or comes after a
+        finish raises ErrInvalidInput, and nothing is launched for it."""
+        view = memoryview(data).cast("B")
+        if off < 0 or len(view) == 0:
+            raise ErrInvalidInput()
+        rc = N.lib.rs_encode_session_feed(self.handle, int(off), ctypes.c_void_p(_addr(view)), len(view))
+        if rc == N.RS_E_ARG:
+            raise ErrInvalidInput()
+        if rc != N.RS_OK:
+            raise _wrapped(rc, "encode_session feed")
+
+    def peek(self, j: int, length: Optional[int] = None) -> bytearray:
+        """The first `length` (default S) bytes of parity row j, after the feeds so far."""
+        out = bytearray(self.S if length is None else int(length))
+        one = bytearray(1)  # a zero-length peek still waits for the feeds
+        rc = N.lib.rs_encode_session_peek(self.handle, int(j), ctypes.c_void_p(_addr(out or one)), len(out))
+        if rc == N.RS_E_ARG:
+            raise ErrInvalidInput()
+        if rc != N.RS_OK:
+            raise _wrapped(rc, "encode_session peek")
+        return out
+
+    def finish(self, parity: Optional[Sequence] = None) -> List:
+        """The m parity shards, S bytes each, into `parity` (m writable buffers; None: the session
+        allocates them). Raises ErrShortData while [0, size) is not covered -- the session stays
+        usable. May be repeated."""
+        if parity is None:
+            parity = [bytearray(self.S) for _ in range(self.m)]
+        if len(parity) != self.m or any(p is None or not _writable(p) or len(p) < self.S for p in parity):
+            raise ErrInvalidInput()
+        ss = ctypes.c_size_t(0)
+        rc = N.lib.rs_encode_session_finish(self.handle, _shard_ptrs(list(parity)), ctypes.byref(ss))
+        if rc == N.RS_E_ARG:
+            raise ErrInvalidInput()
+        if rc != N.RS_OK:
+            raise _wrapped(rc, "encode_session finish")
+        assert ss.value == self.S
+        return list(parity)
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            N.lib.rs_encode_session_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ObjectEncodeSession:
+    """Codec.encode_session's session: an EncodeSession that also keeps the fed bytes, in one
+    buffer of k * S zero-initialised bytes, so that finish() can return the k + m shards as
+    Codec.encode does. write(data) feeds at the running offset."""
+
+    def __init__(self, session: EncodeSession):
+        self.session = session
+        self.body = bytearray(session.k * session.S)
+        self.offset = 0
+
+    def feed(self, off: int, data) -> None:
+        view = memoryview(data).cast("B")
+        self.session.feed(off, view)
+        self.body[off:off + len(view)] = view
+
+    def write(self, data) -> int:
+        """Feeds `data` at the running offset, as an io.Writer takes a request body."""
+        n = len(memoryview(data).cast("B"))
+        self.feed(self.offset, data)
+        self.offset += n
+        return n
+
+    def peek(self, j: int, length: Optional[int] = None) -> bytearray:
+        return self.session.peek(j, length)
+
+    def finish(self) -> List[memoryview]:
+        """data_shards + parity_shards shards of S bytes, bit for bit Codec.encode's for the
+        body. Errors as EncodeSession.finish."""
+        s = self.session
+        parity = bytearray(s.S * s.m)
+        bv, pv = memoryview(self.body), memoryview(parity)
+        s.finish([pv[j * s.S:(j + 1) * s.S] for j in range(s.m)])
+        return [bv[i * s.S:(i + 1) * s.S] for i in range(s.k)] + [pv[j * s.S:(j + 1) * s.S] for j in range(s.m)]
 
     def close(self) -> None:
         self.session.close()

@@ -243,6 +243,60 @@ func (s *DecodeSession) Finish() ([]byte, error) {
 // Close frees nothing here.
 func (s *DecodeSession) Close() {}
 
+// EncodeSession (DESIGN.md §5.18) on builds without the GPU codec: it buffers the body as it is
+// fed and encodes it at Finish.
+type EncodeSession struct {
+	c       *Codec
+	profile ErasureProfile
+	size    int64
+	mu      sync.Mutex
+	body    []byte
+	fed     int64
+	off     int64
+}
+
+// EncodeSession opens a session for a body of size bytes.
+func (c *Codec) EncodeSession(profile ErasureProfile, size int64) (*EncodeSession, error) {
+	if profile.DataShards < 1 || profile.ParityShards < 1 {
+		return nil, ErrInvalidProfile
+	}
+	if size < 0 {
+		size = 0
+	}
+	return &EncodeSession{c: c, profile: profile, size: size, body: make([]byte, size)}, nil
+}
+
+// Feed keeps body bytes [off, off+len(data)).
+func (s *EncodeSession) Feed(off int64, data []byte) error {
+	if off < 0 || off+int64(len(data)) > s.size {
+		return fmt.Errorf("erasure: body range [%d, %d) of %d", off, off+int64(len(data)), s.size)
+	}
+	s.mu.Lock()
+	defer s.mu.Unlock()
+	copy(s.body[off:], data)
+	s.fed += int64(len(data))
+	return nil
+}
+
+// Write feeds p at the running offset.
+func (s *EncodeSession) Write(p []byte) (int, error) {
+	if err := s.Feed(s.off, p); err != nil {
+		return 0, err
+	}
+	s.off += int64(len(p))
+	return len(p), nil
+}
+
+// Finish is Encode of the buffered body.
+func (s *EncodeSession) Finish() ([][]byte, error) {
+	s.mu.Lock()
+	defer s.mu.Unlock()
+	return s.c.cpuEncode(s.body, s.profile)
+}
+
+// Close frees nothing here.
+func (s *EncodeSession) Close() {}
+
 // ErrLocateUnavailable is what Locate reports on builds without the GPU codec: the CPU codec
 // has no locator (the reference finds a bad shard by its checksum, manager.go:250-320).
 var ErrLocateUnavailable = errors.New("erasure: locating corrupt shards needs the GPU codec")

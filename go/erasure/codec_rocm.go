@@ -1485,6 +1485,117 @@ func (s *DecodeSession) Close() {
 	}
 }
 
+// ---- encode sessions (DESIGN.md §5.18) --------------------------------------------------------
+
+// EncodeSession is a progressive encode of one object whose parity rows stay on the device
+// (rs_encode_session_open): Write (or Feed) each piece of the request body as it is read, then
+// Finish for the n shards Encode would return. The body is kept, in Split's layout, in one
+// buffer of n*S bytes whose tail receives the parity, so Finish copies nothing but the parity.
+// On a profile or a machine the GPU codec does not serve it buffers the body and encodes at
+// Finish. Like the rest of this package it has never been compiled where the library is
+// developed. Not in the reference API.
+type EncodeSession struct {
+	c       *Codec
+	h       *C.rs_encode_session
+	profile ErasureProfile
+	size    int64
+	S       int
+	mu      sync.Mutex
+	buf     []byte // k*S body bytes, zero padded, then m*S parity bytes
+	off     int64  // Write's running offset
+}
+
+// EncodeSession opens a session for a body of size bytes (the request's Content-Length).
+func (c *Codec) EncodeSession(profile ErasureProfile, size int64) (*EncodeSession, error) {
+	k, m := profile.DataShards, profile.ParityShards
+	if k < 1 || m < 1 {
+		return nil, ErrInvalidProfile
+	}
+	if size <= 0 {
+		return nil, fmt.Errorf("erasure: failed to split data: %w", reedsolomon.ErrShortData)
+	}
+	S := int((size + int64(k) - 1) / int64(k))
+	s := &EncodeSession{c: c, profile: profile, size: size, S: S, buf: make([]byte, (k+m)*S)}
+	if k+m > 256 || m > 16 || size < int64(gpuMinBytes) || device() == nil {
+		return s, nil
+	}
+	if rc := C.rs_encode_session_open(gpuCtx, C.int(k), C.int(m), C.size_t(size), &s.h); rc != C.RS_OK {
+		return nil, fmt.Errorf("erasure: failed to create encoder: %w", upstreamErr(rc))
+	}
+	return s, nil
+}
+
+// Feed folds body bytes [off, off+len(data)) in, every byte exactly once, from any goroutine and
+// in any order; it returns when data may be reused.
+func (s *EncodeSession) Feed(off int64, data []byte) error {
+	if off < 0 || len(data) == 0 || off+int64(len(data)) > s.size {
+		return fmt.Errorf("erasure: body range [%d, %d) of %d", off, off+int64(len(data)), s.size)
+	}
+	if s.h != nil {
+		var pin runtime.Pinner
+		defer pin.Unpin()
+		pin.Pin(&data[0])
+		if rc := C.rs_encode_session_feed(s.h, C.uint64_t(off), (*C.uint8_t)(unsafe.Pointer(&data[0])), C.size_t(len(data))); rc != C.RS_OK {
+			return fmt.Errorf("erasure: failed to encode parity: %w", upstreamErr(rc))
+		}
+	}
+	s.mu.Lock()
+	copy(s.buf[off:], data)
+	s.mu.Unlock()
+	return nil
+}
+
+// Write feeds p at the running offset: an io.Writer for io.Copy from the request body.
+func (s *EncodeSession) Write(p []byte) (int, error) {
+	if len(p) == 0 {
+		return 0, nil
+	}
+	if err := s.Feed(s.off, p); err != nil {
+		return 0, err
+	}
+	s.off += int64(len(p))
+	return len(p), nil
+}
+
+// Finish returns the n shards, bit for bit Encode's for the body. Before the whole body has been
+// fed it is ErrShortData and the session stays usable.
+func (s *EncodeSession) Finish() ([][]byte, error) {
+	k, m := s.profile.DataShards, s.profile.ParityShards
+	if s.h == nil {
+		s.mu.Lock()
+		defer s.mu.Unlock()
+		if s.off != s.size {
+			return nil, fmt.Errorf("erasure: failed to split data: %w", reedsolomon.ErrShortData)
+		}
+		return s.c.cpuEncode(s.buf[:s.size], s.profile)
+	}
+	ptrs := newCArray(m)
+	defer ptrs.free()
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	shards := make([][]byte, k+m)
+	for i := range shards {
+		shards[i] = s.buf[i*s.S : (i+1)*s.S : (i+1)*s.S]
+		if i >= k {
+			pin.Pin(&shards[i][0])
+			ptrs.set(i-k, unsafe.Pointer(&shards[i][0]))
+		}
+	}
+	var ss C.size_t
+	if rc := C.rs_encode_session_finish(s.h, ptrs.at(0), &ss); rc != C.RS_OK {
+		return nil, fmt.Errorf("erasure: failed to encode parity: %w", upstreamErr(rc))
+	}
+	return shards, nil
+}
+
+// Close frees the session.
+func (s *EncodeSession) Close() {
+	if s.h != nil {
+		C.rs_encode_session_close(s.h)
+		s.h = nil
+	}
+}
+
 // Overwrite replaces bytes [offset, offset+len(data)) of the object whose n shards these are
 // (Encode's layout: object byte x in data shard x/S at column x%S) and brings the parity up to
 // date (rs_codec_overwrite): only the affected parity columns are read and rewritten, through

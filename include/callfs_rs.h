@@ -922,6 +922,86 @@ int rs_session_finish(rs_session* session, uint8_t* const* dst, const size_t* ds
                       uint8_t* const* fix, uint64_t* counts);
 void rs_session_close(rs_session* session);
 
+/* ---- absorb objects: body ranges into resident parity rows -----------
+ * The upload twin of a feed object. An object of L bytes under RS(k,m) has S = ceil(L / k)
+ * (rs_shard_size); object byte x is byte x % S of data shard x / S, as Split lays it out. An
+ * absorb object fixes k, m, S and the m parity rows: rows[j] names an S-byte device accumulator
+ * owned by the caller (no byte of one overlaps another or any source), zero before the first
+ * launch. At most 16 rows (RS_E_UNSUPPORTED above).
+ * rs_absorb_launch(absorb, off, len, src, stream) folds the body range [off, off + len) in: src
+ * is len bytes the device can read -- device memory or host-coherent pinned memory -- at any
+ * alignment, body byte off + b at src[b]. Its effect is exactly
+ *     rows[j][c] ^= P[j][i] * body[i * S + c]    for every fed byte (i, c) and every j
+ * with P the parity rows of the encoding matrix, and nothing else: no byte of a row outside the
+ * columns the range touches is read or written. When every byte of [0, L) has been fed exactly
+ * once, in any order, the rows are bit for bit the parity shards rs_codec_encode writes for the
+ * body; bytes L .. k*S-1 are Split's zero padding and need not be fed.
+ * A LAUNCH IS NOT IDEMPOTENT: it adds the range's terms to the rows' current bytes, and a second
+ * launch of the same range adds them again, which restores what the first started from. Launches
+ * of disjoint ranges commute; launches on one stream, or otherwise ordered, never race.
+ * The launch only enqueues one kernel on `stream`, however many shards the range covers: no
+ * allocation, no copy, no sync; graph-capturable (the arguments go by value). The coefficient
+ * tables are built once, in rs_absorb_create, and uploaded once.
+ * Errors of rs_absorb_create, in this order: the profile (RS_E_INVALID_PROFILE,
+ * RS_E_UNSUPPORTED); a NULL ctx, rows, out or row pointer (RS_E_ARG); more than 16 rows
+ * (RS_E_UNSUPPORTED); S == 0 (RS_E_NO_DATA); then an unknown device (RS_E_ARG). Each check runs
+ * before the next. Nothing is created on an error. rs_absorb_launch returns RS_E_ARG for a NULL
+ * absorb or src, len == 0 and a range that does not lie inside [0, k*S). */
+typedef struct rs_absorb rs_absorb;
+int rs_absorb_create(rs_ctx* ctx, int device, int k, int m, size_t S, uint8_t* const* rows,
+                     rs_absorb** out);
+int rs_absorb_launch(rs_absorb* absorb, uint64_t off, uint64_t len, const uint8_t* src,
+                     void* stream);
+void rs_absorb_destroy(rs_absorb* absorb);
+
+/* ---- encode sessions: the body fed from host memory as it arrives ----
+ * The host route over an absorb object, for an upload whose body arrives in reads that ignore
+ * shard boundaries. rs_codec_encode starts when the last body byte is in host memory and then
+ * pays the H2D of k*S, the kernel and the D2H of m*S. A session keeps the m parity rows on one
+ * device from open to close; every piece of the body goes up once, as it arrives, and after the
+ * last byte only the D2H of m*S is left.
+ * rs_encode_session_open(ctx, k, m, len, &session): an object of len bytes, S =
+ *   ceil(len / k) (rs_shard_size). Allocates the rows (zeroed, at a pitch of S rounded up to 256), a
+ *   stream, a ring of CALLFS_RS_SESSION_SLOTS source slots (default 3) of min(len,
+ *   CALLFS_RS_ENCODE_SESSION_CHUNK) bytes each (default 4 MiB) and the absorb object, on the
+ *   context's next device in round-robin order. A session holds none of the context's lanes.
+ *   Errors, in this order: the profile; a NULL ctx or session (RS_E_ARG); len == 0
+ *   (RS_E_SHORT_DATA, as rs_codec_encode); m > 16 (RS_E_UNSUPPORTED).
+ * rs_encode_session_feed(session, off, bytes, n): body bytes [off, off + n) from host memory.
+ *   Calls on one session are serialised by a mutex and may come from any thread, in any order.
+ *   A FEED IS NOT IDEMPOTENT, so every body byte is fed exactly once: a range that is empty,
+ *   reaches past len, overlaps anything fed before or comes after a finish is RS_E_ARG, and
+ *   nothing is launched for it. It returns once `bytes` may be reused and blocks only while every
+ *   slot of the ring holds a piece whose launch has not finished. A feed larger than a slot is cut
+ *   into slot-sized pieces, one launch each. Per piece one of three routes into the one kernel,
+ *   chosen by CALLFS_RS_SESSION_INPLACE_MAX (bytes per piece, read at open; default 2 MiB):
+ *     in place  up to that size: the piece is copied into a host-coherent slot and the kernel
+ *               reads it over PCIe;
+ *     direct    up to that size and inside an rs_host_alloc buffer: read where it lies, with no
+ *               host copy at all; the call then returns when the kernel has read it;
+ *     staged    above it: one H2D from staging into a device slot, then the launch.
+ *   rs_host_counters: calls 1 per feed; per piece launches 1, copies 0 in place and direct and 1
+ *   staged.
+ * rs_encode_session_peek(session, j, out, n): waits for the feeds so far and copies the first
+ *   n <= S bytes of parity row j, 0 <= j < m (RS_E_ARG otherwise): the parity of the body with
+ *   every byte not yet fed taken as zero.
+ * rs_encode_session_finish(session, parity, &shard_size): RS_E_SHORT_DATA while [0, len) is not
+ *   covered; the session stays open and usable. Otherwise it waits for the stream and copies the
+ *   m rows out, S bytes each into parity[j]; a destination inside an rs_host_alloc buffer takes
+ *   its D2H directly, the others share one D2H through pinned staging. *shard_size (may be NULL)
+ *   receives S. The bytes are those rs_codec_encode writes for the body. A finish may be repeated:
+ *   it changes nothing. Feeds after it are RS_E_ARG. The data shards are the caller's body; the
+ *   session never copies them back.
+ * rs_encode_session_close waits for the session's stream and frees everything. */
+typedef struct rs_encode_session rs_encode_session;
+int rs_encode_session_open(rs_ctx* ctx, int k, int m, size_t len, rs_encode_session** out);
+int rs_encode_session_feed(rs_encode_session* session, uint64_t off, const uint8_t* bytes,
+                           size_t n);
+int rs_encode_session_peek(rs_encode_session* session, int j, uint8_t* out, size_t n);
+int rs_encode_session_finish(rs_encode_session* session, uint8_t* const* parity,
+                             size_t* shard_size);
+void rs_encode_session_close(rs_encode_session* session);
+
 /* ---- locate plans: which shard is corrupt --------------------------
  * Not in the reference API. Every other plan tells that a stripe's compared shards mismatch; a
  * locate plan tells where. sizes, present and shards as for rs_plan_create_ragged, but present

@@ -554,6 +554,20 @@ shift
 timeout -k 10 500 python3 -u tools/session_bench.py "$@" | tee $O/session_bench.jsonl || exit $?
 }
 
+# Absorb launches and encode sessions against what they replace (tools/encode_session_bench.py,
+# DESIGN.md §5.18), RS(10,4): (a) rs_absorb_launch of a piece over 1, 4 and 10 shards against the
+# uniform encode plan launch over the same input bytes, (b) rs_encode_session_feed per 64 KiB and
+# 1 MiB piece on the three routes against rs_encode_idx, (c) the last feed plus finish against
+# one-shot rs_codec_encode. One JSON line per section and size on stdout and in
+# <out dir>/encode_session_bench.jsonl (the lines kept in profiles/r35/encode_session/).
+# Usage: bash tools/jobs.sh encode_session_bench <out dir> [encode_session_bench.py args]
+job_encode_session_bench() {
+cd "$(dirname "$JOBS")/.." || exit $?
+O=${1:-encode_session_out}; mkdir -p "$O" || exit $?
+shift
+timeout -k 10 500 python3 -u tools/encode_session_bench.py "$@" | tee $O/encode_session_bench.jsonl || exit $?
+}
+
 # Locate plans against the compare-only plan of the same batch and against batched SHA-256 of
 # every shard (tools/locate_bench.py): RS(10,4) x 256 stripes of 64 KiB..4 MiB
 # and RS(16,4) x 4,096 stripes of 1..16 KiB, clean and with one shard of every stripe wholly
